@@ -2,7 +2,7 @@
 """Headline benchmark: SD1.5 512x512, 50-step DPM++2M (51 UNet evals, CFG 7.5) images/sec on
 N MI355X of one node (BASELINE.json metric; config 2: batch 8 per GPU, bf16 compute).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N>1: either `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` or the plain line
    above, which then starts its own N ranks through the same launcher; fewer than N GPUs on the node = exit code 2)
 
@@ -19,11 +19,16 @@ images, all inputs resident in HBM.  Rank 0 prints ONE JSON line.
     GPU, both text towers random-init at their real sizes) | inpaint768 (configs[2]: 9-channel SD1.5 UNet grafted onto the base UNet, 768x768,
     VAE encode of the init image, 4 images) - the extra configs are for builder / judge runs, the driver uses the default.
 
+A plain run sets up, warms up, times the --steps steps, writes the last timed step's outputs if --dump-outputs DIR is given
+(DIR/images.npy and DIR/latents.npy, float32, inputs seeded so that two builds compare output for output) and prints the line:
+value, ms_per_step, latency_p50_s and step_mfma_frac all come from the timed steps alone.  Everything else is --full:
+
 roofline: the MFMA kernel classes (8-wave GEMM/conv tiles, attention) are timed live with HIP events on the launch stream
 during the timed region (gyre_prof_* in the C ABI); the class with the largest total is reported: achieved = algorithmic
 FLOPs of its launches / their summed duration, against the 2.5 PFLOP/s dense bf16 MFMA peak; traffic = PMC-derived HBM
 bytes per launch from profiles/traffic.json.  kernel_classes / roofline_hbm come from ONE extra, fully instrumented step
 run AFTER the timed region (every launch bracketed by events costs a few percent, so it is kept out of `value`).
+Also: shader clock / power during the timed region, the one-image and split-request latencies, value_checked_attention.
 cpu_baseline: the fp32 oracle (same ATen CPU ops as the reference's CPU path) on the host cores: 1 warm-up + median of 3
 CFG UNet evaluations (= one step of BASELINE configs[0]: batch 1, 512x512) and one VAE decode, combined into the
 20-step Euler-a image of configs[0] and the 51-evaluation image of configs[1].
@@ -48,6 +53,22 @@ HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E spec (6.3 TB/s achi
 # kernel classes timed live during the timed region; the one with the largest total is reported as the dominant kernel
 CANDIDATES = ["k_gemm8<", "k_gemm4s<", "k_attn", "k_xattn"]
 HBM_CLASSES = ["k_gn_", "k_layernorm"]
+DUMP_BYTES = 63 << 20           # --dump-outputs stays under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  Past DUMP_BYTES in all, every array keeps the same share of its
+    elements: a fixed stride from a seeded offset over the flattened array, so the files of two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() for a in arrays.values()) * 4
+    stride = total // DUMP_BYTES + 1
+    for name, a in arrays.items():
+        a = a.detach().float().cpu()
+        if stride > 1:
+            off = int(torch.randint(stride, (1,), generator=torch.Generator().manual_seed(0)))
+            a = a.reshape(-1)[off::stride]
+        np.save(os.path.join(out_dir, name + ".npy"), a.contiguous().numpy())
 
 
 def fill_synthetic_on_device(module, seed):
@@ -190,14 +211,22 @@ def main():
     ap.add_argument("--ablation", type=lambda v: int(v, 0), default=0,
                     help="gyre_debug_gemm_ablation bits for same-box A/B runs of the whole step (0x80 = shortcuts as their own launches, "
                          "0x2000 = three-launch cross-attention; include/gyre_hip.h lists the rest); printed in the line when non-zero")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline, clock / power, "
+                    "request latencies, checked attention, per-class table, CPU baseline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's images and latents as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--sync-debug", action="store_true", help="dev: torch.cuda.set_sync_debug_mode('warn') over the timed region - every "
                     "host-device synchronisation of a step is reported on stderr with the line that caused it")
     ap.add_argument("--trace-markers", action="store_true", help="dev: bracket the timed region with a fill<complex128> launch, the marker "
                     "tools/c5_trace.py / tools/trace_sequence.py cut a rocprofv3 kernel trace at")
-    ap.add_argument("--no-class-table", action="store_true", help="skip the extra instrumented step after the timed region")
-    ap.add_argument("--profile-all", action="store_true", help="time every kernel class INSIDE the timed region (adds event overhead)")
+    ap.add_argument("--no-class-table", action="store_true", help="--full without the extra instrumented step after the timed region")
+    ap.add_argument("--profile-all", action="store_true", help="--full: time every kernel class INSIDE the timed region (adds event overhead)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.profile_all and not args.full:
+        ap.error("--profile-all reports the kernel classes of a --full run: add --full")
     defaults = {"sd15": (8, 50, 512), "sdxl": (2, 30, 1024), "inpaint768": (4, 50, 768), "tomeclip": (8, 50, 512)}[args.config]
     B = args.batch or defaults[0]
     n_steps = args.inference_steps or defaults[1]
@@ -362,12 +391,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Warm-up.  The last warm-up step runs with every MFMA kernel family instrumented to find the DOMINANT class; the timed
-    # region then carries HIP events around that class's launches only (events around all ~16 k launches of a step cost ~7 %:
-    # 0.99 s vs 1.07 s per request on the same box - that overhead belongs to the measurement, not to `value`).
+    # Warm-up.  --full: the last warm-up step runs with every MFMA kernel family instrumented to find the DOMINANT class; the
+    # timed region then carries HIP events around that class's launches only (events around all ~16 k launches of a step cost
+    # ~7 %: 0.99 s vs 1.07 s per request on the same box - that overhead belongs to the measurement, not to `value`).  A plain
+    # run carries no events at all.
     dom_prefix = None
     for i in range(args.warmup):
-        last = i == args.warmup - 1
+        last = args.full and i == args.warmup - 1
         if last and not args.profile_all:
             _lib.prof_enable(CANDIDATES)
         step(-1 - i)
@@ -378,9 +408,10 @@ def main():
             if pre:
                 dom_prefix = max(pre, key=lambda k: pre[k]["ms"])
     barrier()
-    _lib.prof_enable(None if args.profile_all else ([dom_prefix] if dom_prefix else CANDIDATES))
+    if args.full:
+        _lib.prof_enable(None if args.profile_all else ([dom_prefix] if dom_prefix else CANDIDATES))
     step_times = []
-    clocks = ClockSampler() if rank == 0 else None
+    clocks = ClockSampler() if rank == 0 and args.full else None
     if clocks:
         clocks.start()
     redo0 = _lib.lib().gyre_debug_attn_redo_count()
@@ -410,18 +441,23 @@ def main():
         torch.cuda.synchronize()
     clock_info = clocks.stop() if clocks else None
     redo1 = _lib.lib().gyre_debug_attn_redo_count()
-    prof = _lib.prof_collect()
-    _lib.prof_enable([])
+    prof = {}
+    if args.full:
+        prof = _lib.prof_collect()
+        _lib.prof_enable([])
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the pipeline: what a caller of the timed path received from its last step
+        dump_outputs(args.dump_outputs, {"latents": latents, **({"images": images} if images is not None else {})})
     if images is not None:
         assert bool(torch.isfinite(images).all()), "non-finite output"
     evals = getattr(pipe, "last_unet_evals", 0)
 
-    # ---- the latency half of the metric (after the timed region; never part of `value`) -------------------------------------
+    # ---- the latency half of the metric (--full, after the timed region; never part of `value`) -----------------------------
     # (a) one image alone: UNet batch 2 (CFG), the per-image latency floor of a single GPU
     # (b) ONE batch-of-B request split over all ranks with the reference's batched_seeds rule (= --scaling strong): what a
     #     Gyre client sees when the node's GPUs serve its request together.  Every rank takes part (all_gather of the latents).
     latency = {}
-    if args.config == "sd15" and args.scaling == "weak":
+    if args.full and args.config == "sd15" and args.scaling == "weak":
         def one_request(rlo, rhi, total):
             n = rhi - rlo
             if n > 0:
@@ -468,7 +504,7 @@ def main():
     # results either way), so on data whose logits trip the bound the default can cost up to checked + optimistic; this is the
     # data-INDEPENDENT figure, `attn_redo_count` says how far the timed region was from it (0 = no workgroup repeated anything)
     checked = None
-    if args.config == "sd15":
+    if args.full and args.config == "sd15":
         n_chk = min(2, args.steps)
         old_variant = _lib.lib().gyre_debug_force_attn_variant(7)
         try:
@@ -489,7 +525,7 @@ def main():
 
     # one extra, fully instrumented step (outside the timed region): the per-class table
     classes = None
-    if not args.no_class_table and not args.profile_all:
+    if args.full and not args.no_class_table and not args.profile_all:
         # EVERY rank runs the extra step (it contains the all_gather of the finished latents - a collective that only rank 0
         # entered would hang the job); only rank 0 instruments it
         if rank == 0:
@@ -560,7 +596,7 @@ def main():
             "latency_p50_s": round(statistics.median(step_times), 4),
             "latency_note": ("wall time of ONE request of %d images split over %d GPUs (rank 0)" % (B, world)) if args.scaling == "strong"
                             else "wall time of one batch-of-%d request on rank 0 (per-image latency at batch %d)" % (B, B),
-            "roofline": roof,
+            **({"roofline": roof} if args.full else {}),
         }
         out.update(latency)
         if args.ablation:
@@ -630,10 +666,8 @@ def main():
                                        "share_of_step_time": round(hb[k]["ms"] / tot, 4)}
         if clock_info:
             out["clock_power"] = clock_info
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            out["cpu_baseline"] = cpu_baseline() if world == 1 and not args.no_cpu_baseline else None
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
