@@ -22,7 +22,25 @@ const bf16_t* gemm_zero_page_for_current_device();
 
 int launch_splitk_reduce(hipStream_t st, const GemmParams& p, int splits);   // kernels_gemm.hip
 
-// kernels_gemm4s.hip: tile configs 20 (192x320), 21 (256x256), 22 (128x320), 23 (128x256)
+// The tile configs (GemmParams::force_cfg ids) and what each kernel can do (table in kernels_gemm.hip).  Every fusion goes through
+// an epilogue that needs gemm_staged_epilogue_ok(p): the 8-wave kernels' LDS-staged one; the pipelined, A-resident and
+// small-problem kernels take only problems that satisfy it.
+enum GemmKind { GEMM_K_4W, GEMM_K_8W, GEMM_K_4S, GEMM_K_AR, GEMM_K_SM };   // register-staged 4-wave, LDS-DMA 8-wave, pipelined,
+                                                                             // A-resident, small-problem
+struct GemmTile {
+    int id, bm, bn; GemmKind kind;
+    bool geglu;          // pairs GEGLU value / gate columns (an even fragment count per wave)
+    int vt_align;        // fused Q|K|V: the V columns start on a multiple of this wave-tile width (0: no transposing epilogue)
+    int cs_rows;         // column statistics of the unsplit kernel: rows per row block (0: none)
+    bool rowstats;       // row statistics: one partial per bn-wide N tile (A-resident kernel: per N-range split, gemm_ar_nsplit)
+    bool ln_fold;        // folded LayerNorm (ln_colsum)
+    bool per_sample_w;   // per-sample weights (w_sample_stride)
+    bool shortcut;       // folded 1x1 shortcut (sc_*)
+    bool w_block;        // reads the blocked weight copy (W_blk)
+};
+const GemmTile* gemm_tile(int cfg);     // nullptr: no such config
+
+// kernels_gemm4s.hip: tile configs 20 - 24
 bool gemm4s_supports(const GemmParams& p, int cfg);
 int launch_gemm4s(hipStream_t st, const GemmParams& p, int cfg, int splits);
 

@@ -45,8 +45,32 @@ int gn_pick_chunks(int B, int HW, int C);
 int gemm_set_batch_invariant(int canonical_samples);
 int gemm_get_batch_invariant();
 // everything thread-local the planner's choices depend on (tuning flags, forced config, batch-invariant size, packed-weight
-// scratch) folded into one value: callers that memoise plans key on it
+// scratch) folded into one value: callers that memoise plans key on it.  The low 32 bits are the tuning switches below.
 long gemm_planner_state();
+// Tuning switches tested on the host (gyre_debug_gemm_ablation, include/gyre_hip.h; per calling thread).  Results stay valid.
+enum : int {
+    GEMM_DBG_NO_SM            = 0x20,        // bit 5: no small-problem kernel (config 32): small linear problems go to the 4-wave tiles
+    GEMM_DBG_SM_NO_SPLITK     = 0x40,        // bit 6: the small-problem kernel does not take the long-K few-row problems from split K
+    GEMM_DBG_NO_SC_FOLD       = 0x80,        // bit 7: the 1x1 shortcut stays its own launch instead of riding inside conv2
+    GEMM_DBG_CONV_ZERO_PAGE   = 0x200,       // bit 9: conv zero padding from a zero page in the pipelined kernel
+    GEMM_DBG_NO_4S            = 0x400,       // bit 10: no pipelined (32x32x16) tile configs
+    GEMM_DBG_NO_LN_FOLD       = 0x800,       // bit 11: LayerNorm as a separate pass (no fold into the consuming GEMM)
+    GEMM_DBG_NO_GN_FOLD       = 0x1000,      // bit 12: the Transformer2D GroupNorm keeps its apply pass (no fold into proj_in)
+    GEMM_DBG_NO_XATTN         = 0x2000,      // bit 13: no fused cross-attention kernel: the three-launch chain
+    GEMM_DBG_NO_GEGLU_4S      = 0x4000,      // bit 14: the GEGLU FF1 does not take the pipelined 256x320 tile
+    GEMM_DBG_LN_STATS_PASS    = 0x8000,      // bit 15: folded LayerNorm takes its row statistics from a separate pass
+    GEMM_DBG_GEGLU_NO_LN_FOLD = 0x10000,     // bit 16: the GEGLU FF1 keeps its separate LayerNorm
+    GEMM_DBG_GN_STATS_PASS    = 0x20000,     // bit 17: GroupNorm keeps its own statistics pass (no producer column statistics)
+    GEMM_DBG_NO_128x160       = 0x40000,     // bit 18: no 128x160 (config 8) and 256x128 (config 12) tiles
+    GEMM_DBG_NO_CS_128x160    = 0x100000,    // bit 20: no statistics epilogue on the 128x160 tile
+    GEMM_DBG_NO_AR            = 0x200000,    // bit 21: no A-resident kernel (config 30)
+    GEMM_DBG_AR_ALL           = 0x400000,    // bit 22: A-resident kernel also for the C x C projections (N < 3 K)
+    GEMM_DBG_NO_4S_128_TILES  = 0x800000,    // bit 23: no pipelined 256x320 tile for 3x3 convs whose grid of it has 128 - 159 workgroups
+    GEMM_DBG_TWO_STAGE_LINEAR = 0x1000000,   // bit 24: the two-stage K loop in the 8-wave kernels' linear mode
+    GEMM_DBG_DEEP_RING        = 0x2000000,   // bit 25: the deep ring at one workgroup per CU also where two 2-stage workgroups fit
+    GEMM_DBG_NO_W_BLOCK       = 0x4000000,   // bit 26: row-major weights everywhere (no blocked weight copies)
+    GEMM_DBG_TWO_STAGE_CONV   = 0x8000000,   // bit 27: the two-stage K loop for the 128x160 / 256x128 tiles' 3x3 convolutions
+};
 int launch_groupnorm_stats(hipStream_t st, const GnParams& p);   // partial sums + finalize -> scale_shift
 int launch_groupnorm_apply(hipStream_t st, const GnParams& p);   // y = act(a*x+b)
 bool gn_use_small(int HW, int C, int C1, int G);                 // one-launch path for small feature maps
@@ -111,7 +135,7 @@ struct GemmParams {
     // for every layer of the UNet; profiles/README.md.)
     const float* ln_colsum = nullptr; const float* ln_stats = nullptr;
     // Statistics straight from the kernel that PRODUCED the rows: rowstat_out (8-wave kernels, staged epilogue, no GEGLU /
-    // split-K / fused V^T; gemm_rowstat_parts() > 0) receives [tiles_n][M][2] = per row the sum and the sum of squares of the
+    // split-K / fused V^T; GemmPlan::rowstat_parts > 0) receives [tiles_n][M][2] = per row the sum and the sum of squares of the
     // bf16-rounded outputs of each N tile, reduced in a fixed order (lanes -> waves -> tile).  A consumer with the folded
     // LayerNorm takes them as ln_parts / ln_nparts instead of ln_stats and finishes mean / rstd in its epilogue
     // (variance as E[x^2] - mean^2 in fp32): the separate statistics pass disappears.
@@ -121,7 +145,7 @@ struct GemmParams {
     // colstat_out [M / colstat_rows][N / colstat_unit][2] = per block of colstat_rows consecutive output rows and per unit of
     // colstat_unit consecutive channels the sum and the sum of squares of the bf16-rounded outputs, reduced in a fixed order
     // (rows of a 16- / 32-row slab -> slabs -> wave tiles -> channels of the unit; no atomics).  colstat_rows is dictated by
-    // the kernel the planner picks: gemm_colstat_rows(p) (0: this problem cannot; the consumer then runs its own statistics
+    // the kernel the planner picks: GemmPlan::colstat_rows (0: this problem cannot; the consumer then runs its own statistics
     // pass).  The row blocks never straddle a sample (rows_per_sample % colstat_rows == 0 is part of the condition), so a
     // GroupNorm over the tensor - alone or as one source of a skip concat - finishes mean / rstd from these partials
     // (GnParams::cs_x / cs_x2) and the statistics pass over the tensor disappears.
@@ -139,32 +163,22 @@ struct GemmParams {
     // know the layout ignore the field and read W.  (launch_w_block makes the copy; the model runtime caches one per weight.)
     const bf16_t* W_blk = nullptr;
     // per-SAMPLE weights (8-wave tile configs 4 - 8, linear mode): rows of sample b = row / rows_per_sample read W + b *
-    // w_sample_stride (elements); row blocks never straddle a sample (gemm_per_sample_w_ok).  The GroupNorm folded into a
+    // w_sample_stride (elements); row blocks never straddle a sample (GemmPlan::per_sample_w).  The GroupNorm folded into a
     // Transformer2D's proj_in (launch_gn_fold); the per-sample bias travels as `rowbias`
     size_t w_sample_stride = 0;
     // 1x1 SHORTCUT folded into a 3x3 convolution as extra K steps (round 6; pipelined 256x320 tile only, stride 1, pad 1, no upsample):
     //   out = conv3x3(A | A2) + (S | S2) Wsc^T + bias        (the resnet's conv2 + conv_shortcut of a channel-changing / concat block)
     // Behind the nine taps of every 64-channel chunk of the conv input the K loop walks sc_K more channels of a second image pair
     // (same H x W as the output, split at sc_C1 like A | A2) through the CENTRE tap.  W holds [N][9 Cin + sc_K] rows (the conv's rows
-    // followed by the shortcut's: launch_concat_rows), K = 9 Cin + sc_K, bias = the sum of the two biases.  gemm_conv_shortcut_ok(p)
+    // followed by the shortcut's: launch_concat_rows), K = 9 Cin + sc_K, bias = the sum of the two biases.  GemmPlan::shortcut_fold
     // says whether launch_gemm would run `p` on a kernel that knows the form.
     const bf16_t* sc_A = nullptr; const bf16_t* sc_A2 = nullptr; int sc_lda = 0, sc_lda2 = 0, sc_C1 = 0, sc_K = 0;
     // conv: circular instead of zero padding along x (bit 0) / y (bit 1) - the reference's request option "tiling"
     // (unified_pipeline.py:1671-1712 patches every Conv2d's own padding to F.pad(mode="circular")); 4-wave tile configs only
     int wrap = 0;
 };
-// rows per colstat_out row block launch_gemm would use for `p` (p.colstat_unit and p.rows_per_sample set); 0: unsupported
-int gemm_colstat_rows(const GemmParams& p);
-// number of N tiles (= partial sums per row) launch_gemm would emit into rowstat_out for `p`; 0: this problem cannot
-int gemm_rowstat_parts(const GemmParams& p);
-// true when launch_gemm would run `p` on a kernel that reads per-sample weights (w_sample_stride; rows_per_sample set)
-bool gemm_per_sample_w_ok(const GemmParams& p);
-// true when launch_gemm would run `p` (sc_* set) on the kernel that folds the 1x1 shortcut into the 3x3 convolution
-bool gemm_conv_shortcut_ok(const GemmParams& p);
 // out[n][0:K1] = a[n][0:K1], out[n][K1:K1+K2] = b[n][0:K2] (bf16 rows; K1, K2 multiples of 8): the folded conv + shortcut weight
 int launch_concat_rows(hipStream_t st, const bf16_t* a, int K1, const bf16_t* b, int K2, int N, bf16_t* out);
-// true when launch_gemm would run `p` (ln_colsum set or not) on a kernel that supports the folded LayerNorm
-bool gemm_ln_fusable(const GemmParams& p);
 // W'[n][k] = bf16(W[n][k] * gamma[k]); colsum[n] = sum_k W'[n][k]; bias_out[n] = sum_k beta[k] * W[n][k] + (bias ? bias[n] : 0)
 int launch_ln_fold(hipStream_t st, const bf16_t* W, int N, int K, const float* gamma, const float* beta, const float* bias,
                    bf16_t* Wf, float* colsum, float* bias_out);
@@ -172,17 +186,30 @@ int launch_ln_fold(hipStream_t st, const bf16_t* W, int N, int K, const float* g
 size_t gemm_ar_packed_bytes(int N, int K);
 int launch_ar_pack(hipStream_t st, const bf16_t* W, int N, int K, void* out);
 int launch_w_block(hipStream_t st, const bf16_t* W, int N, int K, bf16_t* out);   // out: N * K elements (GemmParams::W_blk)
-bool gemm_w_block_wanted(const GemmParams& p);      // the planner's kernel for `p` reads a blocked copy and the shape gains from one
-// Pure function of the problem shape: tile configuration, K splits and the split-K workspace it needs.
-// The caller allocates `ws_bytes` (or passes none: the launch then falls back to a single split).
-struct GemmPlan { int cfg; int splits; size_t ws_bytes; };
 // 3x3 / stride 1 / zero padding 1 convolution of NHWC bf16 x [B][H][W][C] into O <= 16 channels, written as NCHW of the given
 // runtime dtype (kernels_conv_out.hip): W [O][3][3][C] bf16, bias [O] or null.  conv_out_supports: C % 64 == 0 and the weights fit LDS.
 bool conv_out_supports(int C, int O);
 int launch_conv_out(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, const bf16_t* Wt, const float* bias, int O,
                     void* out, int out_dtype);
+// What launch_gemm will do with `p`: a pure function of the problem (and of this thread's planner state, gemm_planner_state()).
+// The caller provides `ws_bytes` of split-K slabs (or none: the launch then falls back to the best single-split config).  The
+// remaining fields answer the caller's questions about fusions; with a forced tile config or batch-invariant planning every
+// fusion answer is "no".
+struct GemmPlan {
+    int cfg = 3, splits = 1;          // tile config (GemmParams::force_cfg ids) and K slices
+    size_t ws_bytes = 0;
+    int colstat_rows = 0;             // rows per colstat_out row block for p.colstat_unit (0: the consumer runs its own statistics pass)
+    int rowstat_parts = 0;            // partial sums per row the launch leaves in rowstat_out (0: this problem cannot)
+    bool ln_fold = false;             // the kernel folds a LayerNorm (ln_colsum)
+    bool per_sample_w = false;        // the kernel reads per-sample weights (w_sample_stride; row blocks never straddle a sample)
+    bool shortcut_fold = false;       // the kernel folds the 1x1 shortcut into the 3x3 convolution (sc_*)
+    bool w_block = false;             // the kernel reads a blocked weight copy (W_blk) and the shape gains from one
+    bool ar_pack = false;             // the A-resident kernel: it needs the packed weight copy (w_packed)
+    int vt_align = 0;                 // fused Q|K|V: vt_col0 must be a multiple of this (0: the kernel has no transposing epilogue)
+};
 GemmPlan gemm_plan(const GemmParams& p);
-int launch_gemm(hipStream_t st, const GemmParams& p);
+int launch_gemm(hipStream_t st, const GemmParams& p);                          // plans `p`, then runs that plan
+int launch_gemm(hipStream_t st, const GemmParams& p, const GemmPlan& plan);    // plan: gemm_plan(p)
 
 
 // ---- flash-style attention (kernels_attn.hip) ------------------------------------

@@ -1257,11 +1257,11 @@ static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int s
     // (tuning bit 24: the two-stage loop everywhere; bit 25: the deep ring also where two 2-stage workgroups would fit)
     const size_t stage = (size_t)(BM + (BN + 63) / 64 * 64) * 128;
     int nst = 2;
-    const bool conv_ring = ((BM == 128 && BN == 160) || (BM == 256 && BN == 128)) && p.mode == GEMM_CONV3 && p.Cin % BK == 0 && p.C1 % BK == 0 && p.K % BK == 0 && !(p.debug & 0x8000000);
-    if ((p.mode == GEMM_LINEAR && !(p.debug & 0x1000000)) || conv_ring) {
+    const bool conv_ring = ((BM == 128 && BN == 160) || (BM == 256 && BN == 128)) && p.mode == GEMM_CONV3 && p.Cin % BK == 0 && p.C1 % BK == 0 && p.K % BK == 0 && !(p.debug & GEMM_DBG_TWO_STAGE_CONV);
+    if ((p.mode == GEMM_LINEAR && !(p.debug & GEMM_DBG_TWO_STAGE_LINEAR)) || conv_ring) {
         const int fit1 = (int)std::min<size_t>(4, (size_t)160 * 1024 / stage);
         const bool two_fit = 4 * stage <= (size_t)160 * 1024;
-        if (grid <= 256 || !two_fit || (p.debug & 0x2000000)) nst = fit1;
+        if (grid <= 256 || !two_fit || (p.debug & GEMM_DBG_DEEP_RING)) nst = fit1;
         const int steps = ((p.K + BK - 1) / BK + splits - 1) / splits;
         if (nst > steps) nst = steps < 2 ? 2 : steps;
         if (nst < 2) nst = 2;
@@ -1300,7 +1300,7 @@ static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int s
             else GYRE_GEMM8_CS(GEMM_CONV3, false);
 #undef GYRE_GEMM8_CS
         } else {
-            GYRE_FAIL(-6, "gemm: column statistics exist for the 320- and 160-wide tiles only (see gemm_colstat_rows)");
+            GYRE_FAIL(-6, "gemm: column statistics exist for the 320- and 160-wide tiles only (see GemmPlan::colstat_rows)");
         }
     } else if (p.mode == GEMM_LINEAR && p.rowstat_out) {
         auto kern = k_gemm8<BM, BN, WM, WN, GEMM_LINEAR, true, false, true>;
@@ -1327,8 +1327,31 @@ static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int s
     return 0;
 }
 
-// Tile-config ids (GemmParams::force_cfg): 1 = 4w 128x128, 2 = 4w 256x64, 3 = 4w 64x64,
-// 4 = 8w 256x320, 5 = 8w 128x320, 6 = 8w 256x256, 7 = 8w 128x256, 8 = 8w 128x160.
+// Tile configs (GemmParams::force_cfg ids): the one place that records what each kernel can do.
+static const GemmTile g_tiles[] = {
+    //  id   bm   bn  kind        geglu  vt_align cs_rows rowstats ln_fold per_sample_w shortcut w_block
+    {   1, 128, 128, GEMM_K_4W,  true,    0,   0,     false,   false,  false,       false,   false },
+    {   2, 256,  64, GEMM_K_4W,  true,    0,   0,     false,   false,  false,       false,   false },
+    {   3,  64,  64, GEMM_K_4W,  true,    0,   0,     false,   false,  false,       false,   false },
+    {   4, 256, 320, GEMM_K_8W,  false, 160, 256,     true,    true,   true,        false,   true  },
+    {   5, 128, 320, GEMM_K_8W,  false,  80, 128,     true,    true,   true,        false,   true  },
+    {   6, 256, 256, GEMM_K_8W,  true,  128,   0,     true,    true,   true,        false,   true  },
+    {   7, 128, 256, GEMM_K_8W,  true,   64,   0,     true,    true,   true,        false,   true  },
+    {   8, 128, 160, GEMM_K_8W,  false,  80, 128,     true,    true,   true,        false,   true  },   // cs: tuning bit 20 off
+    {  12, 256, 128, GEMM_K_8W,  true,    0,   0,     false,   false,  false,       false,   true  },   // 3x3 convolutions only
+    {  20, 192, 320, GEMM_K_4S,  true,    0,   0,     false,   false,  false,       false,   true  },
+    {  21, 256, 256, GEMM_K_4S,  true,    0,   0,     false,   false,  false,       false,   true  },
+    {  22, 128, 320, GEMM_K_4S,  true,    0,   0,     false,   false,  false,       false,   true  },
+    {  23, 128, 256, GEMM_K_4S,  true,    0,   0,     false,   false,  false,       false,   true  },
+    {  24, 256, 320, GEMM_K_4S,  true,    0, 256,     false,   true,   false,       true,    true  },   // cs: 3x3 convolutions only
+    {  30, 256,  64, GEMM_K_AR,  true,   64,   0,     true,    true,   false,       false,   false },   // bn: K = 320 (32 at K = 640)
+    {  32,  64,  64, GEMM_K_SM,  false,  64,   0,     false,   false,  false,       false,   true  },
+};
+const GemmTile* gemm_tile(int cfg) {
+    for (const GemmTile& t : g_tiles)
+        if (t.id == cfg) return &t;
+    return nullptr;
+}
 static thread_local void* g_dbg_ar_ws = nullptr;       // gyre_debug_set_ar_workspace: packed-weight scratch of bare gyre_op_* calls
 static thread_local size_t g_dbg_ar_ws_bytes = 0;
 // smallest grid the A-resident kernel is taken for (GYRE_AR_GRID_MIN: tuning override, read once)
@@ -1340,20 +1363,22 @@ static int pick_cfg(const GemmParams& p, int* splits_out) {
     *splits_out = 1;
     const bool trans = p.out_mode == OUT_BF16_T;
     auto tiles = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
+    auto tiles_of = [&](int id) { const GemmTile* t = gemm_tile(id); return tiles(t->bm, t->bn); };
     // wave-quantisation efficiency on 256 CUs with `slots` resident workgroups per CU
     auto eff = [&](long t, int slots) { long cap = 256L * slots; long waves = (t + cap - 1) / cap; return (double)t / (double)(waves * cap); };
     // padding efficiency along N and along M (a 256-row tile on 128 rows does half its work on padding)
     auto neff = [&](int bn) { long nt = (p.N + bn - 1) / bn; return (double)p.N / (double)(nt * bn); };
     auto meff = [&](int bm) { long mt = (p.M + bm - 1) / bm; return (double)p.M / (double)(mt * bm); };
     double best = -1; int cfg = 3;
-    auto consider = [&](int id, double speed, int bm, int bn, int slots) {
-        double s = speed * eff(tiles(bm, bn), slots) * neff(bn) * meff(bm);
+    auto consider = [&](int id, double speed, int slots) {
+        const GemmTile* t = gemm_tile(id);
+        double s = speed * eff(tiles(t->bm, t->bn), slots) * neff(t->bn) * meff(t->bm);
         if (s > best) { best = s; cfg = id; }
     };
     // relative speeds measured with tools/opbench.py on MI355X (TFLOP/s at full occupancy / 1000)
-    consider(3, 0.30, 64, 64, 4);
-    consider(1, 0.55, 128, 128, 2);
-    consider(2, 0.50, 256, 64, 2);
+    consider(3, 0.30, 4);
+    consider(1, 0.55, 2);
+    consider(2, 0.50, 2);
     // circular padding exists in the 4-wave register-staged gather only (a niche request option: correctness over speed)
     const bool wrap_only4 = p.mode == GEMM_CONV3 && p.wrap != 0;
     // A-resident kernel (kernels_gemm_ar.hip): K = 320 / 640 linear problems with enough rows to cover the chip keep their
@@ -1361,43 +1386,43 @@ static int pick_cfg(const GemmParams& p, int* splits_out) {
     // Taken where the N sweep is long enough to amortise the slab load (GEGLU FF1: N = 8 C, 216 -> 129 us at 64x64, 163 -> 124
     // at 32x32; a plain N = 3 C: 80 -> 62 us).  The C x C projections (5 N tiles per workgroup) are HBM-bound either way and
     // measured 5 - 7 % slower here (33 -> 35 us): they stay on the 8-wave tiles unless tuning bit 22 asks for them.
-    if (!trans && p.batch <= 1 && (p.ar_ok || p.w_packed || g_dbg_ar_ws) && !p.no_ar && !(p.debug & 0x200000) && p.M >= 4096 &&
-        (p.N >= 3 * p.K || (p.debug & 0x400000)) && gemm_ar_supports(p) &&
+    if (!trans && p.batch <= 1 && (p.ar_ok || p.w_packed || g_dbg_ar_ws) && !p.no_ar && !(p.debug & GEMM_DBG_NO_AR) && p.M >= 4096 &&
+        (p.N >= 3 * p.K || (p.debug & GEMM_DBG_AR_ALL)) && gemm_ar_supports(p) &&
         // ... and only where its grid (256-row blocks x N-range splits of at least four tiles) covers most of the chip: the fused Q|K|V
         // at batch 2 (M = 8192, 15 N tiles -> 64 workgroups) took 31 us there against 18 us on the 8-wave tile
-        ((long)((p.M + 255) / 256) * gemm_ar_nsplit(p) >= ar_grid_min() || (p.debug & 0x400000)))
+        ((long)((p.M + 255) / 256) * gemm_ar_nsplit(p) >= ar_grid_min() || (p.debug & GEMM_DBG_AR_ALL)))
         return 30;
     if (!trans && p.batch <= 1 && !wrap_only4) {
         // the 1-workgroup-per-CU big tiles only pay when the grid covers most of the chip: with few tiles the
         // serial K loop of each workgroup dominates and the small tiles' extra parallelism wins
-        auto big = [&](int id, double speed, int bm, int bn) { if (tiles(bm, bn) >= 160) consider(id, speed, bm, bn, 1); };
-        if (!p.geglu && p.N % 320 == 0) { big(4, 0.92, 256, 320); big(5, 0.88, 128, 320); }
+        auto big = [&](int id, double speed) { if (tiles_of(id) >= 160) consider(id, speed, 1); };
+        if (!p.geglu && p.N % 320 == 0) { big(4, 0.92); big(5, 0.88); }
         // 128x160: for the problems whose 128x256 / 128x320 tiling leaves CUs idle (16x16 level: M = 4096, N = 1280 is 160 /
         // 128 tiles of those, 256 of this one).  71 FLOP per pipe byte against 85 / 91, but every CU works and two workgroups
         // fit a CU (74 KB of LDS, < 128 registers): tuning bit 18 turns it off
         // (tools/gemm_sweep.py 16 64 sd15 8, cold and producer-warm regimes: beats the 128x320 tile wherever that one is
         //  chosen - 32x32 projections 34.7 -> 28.2 us, K = 2560 84 -> 66 us - and loses to 256x320 / 256x256 where those fill
         //  the chip, M = 65536: 41 vs 38 us)
-        if (!p.geglu && p.N % 160 == 0 && !(p.debug & 0x40000)) big(8, 0.90, 128, 160);
-        if (p.N % 256 == 0) { big(6, 0.95, 256, 256); big(7, 0.62, 128, 256); }
+        if (!p.geglu && p.N % 160 == 0 && !(p.debug & GEMM_DBG_NO_128x160)) big(8, 0.90);
+        if (p.N % 256 == 0) { big(6, 0.95); big(7, 0.62); }
         // 256x128 (config 12): 3x3 convs into 128 channels - the 512x512 level of the VAE decoder, 25 % of a decode - had no 8-wave
         // tile (N = 128 is no multiple of 160 / 256 / 320) and ran on the register-staged 128x128 tile at 0.20 - 0.22 of the MFMA peak
-        if (p.mode == GEMM_CONV3 && !p.geglu && p.N % 128 == 0 && p.N % 256 != 0 && p.N % 160 != 0 && !(p.debug & 0x40000)) big(12, 0.90, 256, 128);
+        if (p.mode == GEMM_CONV3 && !p.geglu && p.N % 128 == 0 && p.N % 256 != 0 && p.N % 160 != 0 && !(p.debug & GEMM_DBG_NO_128x160)) big(12, 0.90);
         // pipelined 32x32x16 kernel (kernels_gemm4s.hip), 8 waves on the 256x320 tile: better main loop (barrier off the
         // critical path, requests issued from the MFMA gaps), heavier two-pass epilogue -> long reductions only.
         // Measured in the UNet (tools/unet_layers.py, r02): 3x3 convs at 64x64 -3...-7 % time, K = 2560 linears -19 %, the
         // K = 1280 / N = 320 linear +13 % (not taken).  The 4-wave one-wave-per-SIMD forms (configs 20-23) win isolated
         // benchmarks (8192^3: 1325 vs 1048 TFLOP/s) but lose 4-15 % inside the UNet; they stay test / tuning configs.
         const int nk_ = (p.K + BK - 1) / BK;
-        if (!(p.debug & 0x400) && p.N % 320 == 0 && (p.mode == GEMM_CONV3 ? nk_ >= 20 : nk_ >= 32) && gemm4s_supports(p, 24)) {
-            big(24, 1.00, 256, 320);
+        if (!(p.debug & GEMM_DBG_NO_4S) && p.N % 320 == 0 && (p.mode == GEMM_CONV3 ? nk_ >= 20 : nk_ >= 32) && gemm4s_supports(p, 24)) {
+            big(24, 1.00);
             // 3x3 convs with K >= 2880 whose 256x320 tiling has 128 - 159 tiles (the 48x48 level of a 768 px request at batch 8:
             // M = 18432, N = 640 -> 144 tiles; no split factor fits): the pipelined tile on 56 % of the CUs still beats the 128x160
             // tile on all of them by 20 - 30 % (tools/gemm_sweep.py 8 96 sd15, round 4: K = 5760 218 -> 174 us, K = 11520 403 -> 302;
             // UNet forward at 96x96 latents, batch 8: 26.96 -> 26.38 ms).  Lowering the 128x160 tile's constant for ALL long convs
             // instead was measured too: no gain at 96x96 and an extra split-K launch at 64x64 - not adopted
             // (tuning bit 23: rule off)
-            if (!(p.debug & 0x800000) && p.mode == GEMM_CONV3 && nk_ >= 45 && tiles(256, 320) >= 128 && tiles(256, 320) < 160) consider(24, 1.25, 256, 320, 1);
+            if (!(p.debug & GEMM_DBG_NO_4S_128_TILES) && p.mode == GEMM_CONV3 && nk_ >= 45 && tiles_of(24) >= 128 && tiles_of(24) < 160) consider(24, 1.25, 1);
         }
         // GEGLU FF1 (N = 8C, K = C): the 320-wide 8-wave tile of the 16x16x32 kernel has an odd fragment count per wave and
         // cannot pair value / gate columns, the pipelined kernel's 32-wide fragments can.  Taken only where the WEIGHTS are
@@ -1406,13 +1431,14 @@ static int pick_cfg(const GemmParams& p, int* splits_out) {
         // comparison (COLD=1 tools/geglu_compare.py).  At 64x64 / 32x32 the activations dominate and are still in the
         // Infinity Cache behind their producer - the warm regime, where the 256x256 tile wins: with the pipelined tile on all
         // three levels the forward went 19.56 -> 19.83 ms (debug bit 14 = this rule off).
-        else if (!(p.debug & 0x4400) && p.geglu && (long)p.N > (long)p.M && p.N % 320 == 0 && gemm4s_supports(p, 24))
-            big(24, 1.00, 256, 320);
+        else if (!(p.debug & (GEMM_DBG_NO_4S | GEMM_DBG_NO_GEGLU_4S)) && p.geglu && (long)p.N > (long)p.M && p.N % 320 == 0 && gemm4s_supports(p, 24))
+            big(24, 1.00);
         // few output tiles but a long reduction (the 8x8 / 16x16 UNet levels: K = 9*Cin up to 23040): cut K into
         // slices so that tiles x slices covers the chip; fp32 slabs are reduced by k_splitk_reduce
         const int nk = (p.K + BK - 1) / BK;
         if (p.out_mode == OUT_BF16 && !p.geglu && p.K >= 2048 && p.N % 4 == 0) {
-            auto tryk = [&](int id, double speed, int bm, int bn) {
+            auto tryk = [&](int id, double speed) {
+                const int bm = gemm_tile(id)->bm, bn = gemm_tile(id)->bn;
                 long t = tiles(bm, bn);
                 if (t >= 160 || t < 1) return;
                 int sp = (int)((id == 8 ? 512 : 256) / t);          // two 128x160 workgroups fit a CU
@@ -1425,30 +1451,30 @@ static int pick_cfg(const GemmParams& p, int* splits_out) {
                 double sc = speed * eff(t * sp, 1) * neff(bn) * 0.85;
                 if (sc > best) { best = sc; cfg = id; *splits_out = sp; }
             };
-            if (p.N % 320 == 0) tryk(5, 0.88, 128, 320);
-            if (p.N % 160 == 0 && !(p.debug & 0x40000)) tryk(8, 0.92, 128, 160);     // 8x8 convs: 60 -> 57 us (sweep)
-            if (p.N % 256 == 0) tryk(7, 0.62, 128, 256);
+            if (p.N % 320 == 0) tryk(5, 0.88);
+            if (p.N % 160 == 0 && !(p.debug & GEMM_DBG_NO_128x160)) tryk(8, 0.92);     // 8x8 convs: 60 -> 57 us (sweep)
+            if (p.N % 256 == 0) tryk(7, 0.62);
             // very long reductions (3x3 convs over 1280+ channels at 32x32 / 16x16): the 256x320 tile's better
             // operand reuse outweighs the larger slabs - measured +3 % (K = 11520) to +10 % (K = 17280 / 23040)
             // (same-box A/B: UNet forward 20.56 -> 20.12 ms)
             // (cold-cache sweep, tools/gemm_sweep.py with COLD=1 - the regime inside the UNet: from K = 5120 on, e.g. the
             //  32x32 convs 640 -> 640: 128x320 unsplit 150 us, 256x320 in 2 slices 133 us)
             if (p.N % 320 == 0 && p.K >= 5000) {
-                tryk(4, 1.05, 256, 320);
+                tryk(4, 1.05);
                 // the pipelined main loop also wins with split K (tools/gemm_sweep.py, r02: 16x16 convs K = 11520 ... 23040,
                 // 4 slices: 133 -> 127, 182 -> 170, 227 -> 216 us)
-                if (!(p.debug & 0x400) && gemm4s_supports(p, 24)) tryk(24, 1.10, 256, 320);
+                if (!(p.debug & GEMM_DBG_NO_4S) && gemm4s_supports(p, 24)) tryk(24, 1.10);
             }
         }
     }
     // small problems (the planner's answer is one of the register-staged 4-wave tiles): the 4-stage LDS-DMA ring of
     // kernels_gemm_sm.hip hides the per-K-step memory latency those kernels expose (tuning bit 5: off)
-    if (!trans && !(p.debug & 0x20) && gemm_sm_supports(p)) {
+    if (!trans && !(p.debug & GEMM_DBG_NO_SM) && gemm_sm_supports(p)) {
         if (cfg <= 3 && *splits_out == 1) cfg = 32;
         // ... and the long-K linear problems with few rows (FF2 of the deep levels at batch 1 - 2: M = 2048, K = 2560 -> 320 tiles of
         // 64x64; M = 512, K = 5120 -> 160) that were cut into K slices: one launch instead of slices + reduction, 30.8 -> 26.4 us
         // and 32.0 -> 25.2 us (tools/sm_bench.py, FORCE=32); with more tiles the 128x160 slices win (M = 4096: 27.9 vs 32.1)
-        else if (*splits_out > 1 && p.mode == GEMM_LINEAR && tiles(64, 64) <= 512 && !(p.debug & 0x40)) { cfg = 32; *splits_out = 1; }
+        else if (*splits_out > 1 && p.mode == GEMM_LINEAR && tiles_of(32) <= 512 && !(p.debug & GEMM_DBG_SM_NO_SPLITK)) { cfg = 32; *splits_out = 1; }
     }
     return cfg;
 }
@@ -1494,116 +1520,67 @@ static int plan_cfg(const GemmParams& p, int* splits) {
     return pick_cfg(p, splits);
 }
 
-// the condition under which k_gemm8 takes its LDS-staged epilogue (the only one that knows the folded LayerNorm)
+// the condition under which k_gemm8 takes its LDS-staged epilogue, the one every fusion goes through (gemm_shared.h GemmTile)
 static bool gemm_staged_epilogue_ok(const GemmParams& p) {
     const int n_out = p.geglu ? p.N / 2 : p.N;
     return p.out_mode == OUT_BF16 && (n_out % 8) == 0 && (p.ldc % 8) == 0 && (!p.residual || (p.ldr % 8) == 0) &&
            (((size_t)p.out | (size_t)p.residual) & 15) == 0;
 }
-bool gemm_per_sample_w_ok(const GemmParams& p0) {
+// `p` as the planner and the launch see it: this thread's tuning switches and forced config, the defaults of a single source
+static GemmParams gemm_normalised(const GemmParams& p0) {
     GemmParams p = p0;
+    if (!p.force_cfg) p.force_cfg = g_force_cfg;
     p.debug = g_gemm_debug;
-    if (g_force_cfg || p.force_cfg || (p.debug & 0x1000) || g_invariant_batch > 0) return false;   // bit 12: GroupNorm keeps its apply pass
-    if (p.mode != GEMM_LINEAR || p.A2 || p.batch > 1 || p.geglu || p.vt_out || p.ln_colsum || p.rows_per_sample <= 0 ||
-        p.M % p.rows_per_sample || p.K % 8 || p.N % 8)
-        return false;
-    if (!gemm_staged_epilogue_ok(p)) return false;
-    int splits = 1;
-    const int cfg = plan_cfg(p, &splits);
-    if (cfg < 4 || cfg > 8 || splits > 1) return false;
-    const int bm = (cfg == 4 || cfg == 6) ? 256 : 128;
-    return p.rows_per_sample % bm == 0;
-}
-bool gemm_conv_shortcut_ok(const GemmParams& p0) {
-    GemmParams p = p0;
-    p.debug = g_gemm_debug;
-    if (g_force_cfg || p.force_cfg || (p.debug & 0x80)) return false;        // tuning bit 7: the shortcut stays its own launch
-    // batch-invariant planning: whether the conv gets the pipelined tile depends on M = batch x rows, and the folded form rounds once
-    // where the two launches round twice - so that mode keeps the two launches for every batch size (as it keeps the separate LayerNorm)
-    if (g_invariant_batch > 0) return false;
-    if (p.mode != GEMM_CONV3 || !p.sc_K || p.sc_K % BK || p.Cin % BK || p.K != 9 * p.Cin + p.sc_K || p.stride != 1 || p.pad != 1 || p.ups ||
-        p.Hi != p.Ho || p.Wi != p.Wo || p.wrap || p.batch > 1 || p.out_mode != OUT_BF16)
-        return false;
-    if (!p.A2) { p.C1 = p.Cin; p.A2 = p.A; p.lda2 = p.lda; }
-    if (p.C1 % BK) return false;
+    if (!p.A2) { p.C1 = p.mode == GEMM_LINEAR ? p.K : p.Cin; p.A2 = p.A; p.lda2 = p.lda; }
     if (p.rows_per_sample <= 0) p.rows_per_sample = 1;
-    int splits = 1;
-    const int cfg = plan_cfg(p, &splits);
-    return cfg == 24 && gemm4s_supports(p, 24);
-}
-bool gemm_ln_fusable(const GemmParams& p0) {
-    GemmParams p = p0;
-    p.debug = g_gemm_debug;
-    if (g_force_cfg || p.force_cfg || (p.debug & 0x800)) return false;      // tuning runs keep the separate LayerNorm (bit 11: off)
-    // batch-invariant planning: whether a shape gets an 8-wave tile depends on M = batch x rows, and the folded and the
-    // separate LayerNorm round differently - so that mode keeps the separate pass for every batch size
-    if (g_invariant_batch > 0) return false;
-    // tuning bit 16: GEGLU FF1 keeps its separate LayerNorm (its GELU epilogue is VALU-bound and the fold adds ~15 % to it:
-    // forward 19.14 ms folded, 19.26 not, 19.52 with no fold at all - same box)
-    if (p.geglu && (p.debug & 0x10000)) return false;
-    if (p.mode != GEMM_LINEAR || p.A2 || p.rowbias || p.batch > 1 || p.M <= 0 || p.K % 8 || p.N % 4) return false;
-    if (!gemm_staged_epilogue_ok(p)) return false;
-    int splits = 1;
-    const int cfg = plan_cfg(p, &splits);
-    if (cfg == 24) return splits == 1 && gemm4s_supports(p, 24);      // pipelined 256x320 tile (kernels_gemm4s.hip)
-    if (cfg == 30) return true;                                        // A-resident kernel (kernels_gemm_ar.hip)
-    // (the small-problem kernel, config 32, had the fold and the row statistics behind a tuning bit in round 4: 47 launches fewer per
-    //  UNet call at batch 2 and the call 6.01 -> 6.10 ms - the LayerNorm launches it removed are cheaper than the statistics loops
-    //  and folded epilogues it added; the form was deleted in round 5)
-    if (cfg == 32) return false;
-    if (cfg < 4 || cfg > 8 || splits > 1) return false;
-    if (p.geglu && (cfg == 4 || cfg == 5 || cfg == 8)) return false;
-    if (p.vt_out) {
-        const int tn = cfg == 4 ? 160 : (cfg == 5 || cfg == 8) ? 80 : cfg == 6 ? 128 : 64;
-        if (p.vt_col0 % tn) return false;
-    }
-    return true;
-}
-
-int gemm_rowstat_parts(const GemmParams& p0) {
-    GemmParams p = p0;
-    p.debug = g_gemm_debug;
-    if (g_force_cfg || p.force_cfg || (p.debug & 0x8800) || g_invariant_batch > 0) return 0;    // bit 15: separate statistics pass
-    if (p.mode != GEMM_LINEAR || p.A2 || p.geglu || p.vt_out || p.ln_colsum || p.batch > 1 || p.M <= 0 || p.K % 8 || p.N % 8)
-        return 0;
-    if (!gemm_staged_epilogue_ok(p)) return 0;
-    int splits = 1;
-    const int cfg = plan_cfg(p, &splits);
-    if (cfg == 30) return gemm_ar_nsplit(p);          // A-resident kernel: one partial per N-range split of the row block
-    if (cfg == 32) return 0;                          // the small-problem kernel leaves no row statistics
-    if (cfg < 4 || cfg > 8 || splits > 1) return 0;
-    const int bn = (cfg == 4 || cfg == 5) ? 320 : cfg == 8 ? 160 : 256;
-    return (p.N + bn - 1) / bn;
-}
-
-// Which kernel would emit the column statistics of `p`, and with what row-block size.  Mirrors launch_gemm's decisions.
-int gemm_colstat_rows(const GemmParams& p0) {
-    GemmParams p = p0;
-    p.debug = g_gemm_debug;
-    const int unit = p.colstat_unit;
-    if (unit <= 0 || g_force_cfg || p.force_cfg || (p.debug & 0x20000) || g_invariant_batch > 0) return 0;   // bit 17: separate statistics pass
-    if (p.out_mode != OUT_BF16 || p.geglu || p.vt_out || p.ln_colsum || p.rowstat_out || p.batch > 1 || p.M <= 0 || p.K % 8 || p.N % 8) return 0;
-    if (p.N % unit || 320 % unit || p.rows_per_sample <= 0 || p.M % p.rows_per_sample) return 0;
-    if (!gemm_staged_epilogue_ok(p)) return 0;
-    int splits = 1;
-    const int cfg = plan_cfg(p, &splits);
-    int rows = 0;
-    if (splits > 1) rows = (cs_red_colblock(p.N, unit) <= 2048) ? cs_red_rows(p.rows_per_sample) : 0;     // k_splitk_reduce_cs
-    else if (cfg == 4) rows = 256;
-    else if (cfg == 5) rows = 128;
-    else if (cfg == 8 && p.N % 160 == 0 && 160 % unit == 0 && !(p.debug & 0x100000)) rows = 128;   // (bit 20: as before this tile had the epilogue)
-    else if (cfg == 24 && p.mode == GEMM_CONV3) rows = 256;                    // pipelined 256x320 tile (kernels_gemm4s.hip)
-    if (!rows || p.rows_per_sample % rows) return 0;
-    return rows;
+    if (p.sc_K && (!p.sc_A2 || p.sc_A2 == p.sc_A)) { p.sc_A2 = p.sc_A; p.sc_lda2 = p.sc_lda; p.sc_C1 = p.sc_K; }
+    return p;
 }
 
 GemmPlan gemm_plan(const GemmParams& p0) {
-    GemmParams p = p0;
-    p.debug = g_gemm_debug;      // same planner inputs as launch_gemm
-    GemmPlan pl{3, 1, 0};
+    const GemmParams p = gemm_normalised(p0);
+    GemmPlan pl;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return pl;
-    pl.cfg = plan_cfg(p, &pl.splits);
+    if (p.force_cfg) { pl.cfg = p.force_cfg & 0xff; pl.splits = std::max(1, (p.force_cfg >> 8) & 0xff); }
+    else pl.cfg = plan_cfg(p, &pl.splits);
     if (pl.splits > 1) pl.ws_bytes = (size_t)pl.splits * p.M * p.N * sizeof(float);
+    const GemmTile* t = gemm_tile(pl.cfg);
+    if (!t) return pl;
+    pl.vt_align = t->vt_align;
+    pl.ar_pack = t->kind == GEMM_K_AR;
+    // a request of 8 weight rows spans 16 K bytes: beyond 16 KB it leaves the fast path of the load unit (K > 1024); the conv K
+    // order walks whole 64-channel chunks
+    pl.w_block = t->w_block && !(p.debug & GEMM_DBG_NO_W_BLOCK) && p.K % 64 == 0 && p.N % 8 == 0 && p.K > 1024 && p.batch <= 1 &&
+                 !p.w_sample_stride && p.out_mode != OUT_BF16_T && (p.mode != GEMM_CONV3 || (p.Cin % 64 == 0 && p.C1 % 64 == 0));
+    // Fusions.  None for tuning runs with a forced config, and none with batch-invariant planning: whether a shape gets a fusing
+    // kernel depends on M = batch x rows, and the fused and the separate forms round differently - so that mode keeps the separate
+    // passes for every batch size.
+    if (p.force_cfg || g_invariant_batch > 0 || p.batch > 1 || !gemm_staged_epilogue_ok(p)) return pl;
+    const bool one_split = pl.splits == 1;
+    const bool plain_linear = p.mode == GEMM_LINEAR && !p0.A2 && p.K % 8 == 0;      // (p0: a second source, even A2 == A, is not)
+    pl.per_sample_w = t->per_sample_w && one_split && plain_linear && !(p.debug & GEMM_DBG_NO_GN_FOLD) && !p.geglu && !p.vt_out &&
+                      !p.ln_colsum && p.N % 8 == 0 && p.M % p.rows_per_sample == 0 && p.rows_per_sample % t->bm == 0;
+    pl.shortcut_fold = t->shortcut && !(p.debug & GEMM_DBG_NO_SC_FOLD) && p.mode == GEMM_CONV3 && p.sc_K && p.sc_K % BK == 0 &&
+                       p.Cin % BK == 0 && p.C1 % BK == 0 && p.K == 9 * p.Cin + p.sc_K && p.stride == 1 && p.pad == 1 && !p.ups &&
+                       p.Hi == p.Ho && p.Wi == p.Wo && !p.wrap;
+    // (bit 16: the GEGLU FF1's GELU epilogue is VALU-bound and the fold adds ~15 % to it: forward 19.14 ms folded, 19.26 not,
+    //  19.52 with no fold at all - same box)
+    pl.ln_fold = t->ln_fold && one_split && plain_linear && !(p.debug & GEMM_DBG_NO_LN_FOLD) &&
+                 !(p.geglu && ((p.debug & GEMM_DBG_GEGLU_NO_LN_FOLD) || !t->geglu)) && !p.rowbias && p.N % 4 == 0 &&
+                 (!p.vt_out || (t->vt_align && p.vt_col0 % t->vt_align == 0));
+    if (t->rowstats && one_split && plain_linear && !(p.debug & (GEMM_DBG_LN_STATS_PASS | GEMM_DBG_NO_LN_FOLD)) && !p.geglu &&
+        !p.vt_out && !p.ln_colsum && p.N % 8 == 0)
+        pl.rowstat_parts = t->kind == GEMM_K_AR ? gemm_ar_nsplit(p) : (p.N + t->bn - 1) / t->bn;
+    // column statistics: the unsplit kernel's row blocks, or those of the statistics-emitting split-K reduction (k_splitk_reduce_cs)
+    const int unit = p.colstat_unit;
+    if (unit > 0 && !(p.debug & GEMM_DBG_GN_STATS_PASS) && !p.geglu && !p.vt_out && !p.ln_colsum && !p.rowstat_out && p.K % 8 == 0 &&
+        p.N % 8 == 0 && p.N % unit == 0 && 320 % unit == 0 && p.M % p.rows_per_sample == 0) {
+        int rows = 0;
+        if (!one_split) rows = cs_red_colblock(p.N, unit) <= 2048 ? cs_red_rows(p.rows_per_sample) : 0;
+        else if (t->bn % unit == 0 && (t->kind != GEMM_K_4S || p.mode == GEMM_CONV3) && !(pl.cfg == 8 && (p.debug & GEMM_DBG_NO_CS_128x160)))
+            rows = t->cs_rows;
+        if (rows && p.rows_per_sample % rows == 0) pl.colstat_rows = rows;
+    }
     return pl;
 }
 
@@ -1627,35 +1604,17 @@ int launch_w_block(hipStream_t st, const bf16_t* W, int N, int K, bf16_t* out) {
 static thread_local bf16_t* g_dbg_blk_ws = nullptr;
 static thread_local size_t g_dbg_blk_ws_bytes = 0;
 extern "C" int gyre_debug_set_wblk_workspace(void* ws, size_t bytes) { g_dbg_blk_ws = (bf16_t*)ws; g_dbg_blk_ws_bytes = bytes; return 0; }
-static bool w_block_cfg(int cfg) { return (cfg >= 4 && cfg <= 8) || cfg == 12 || (cfg >= 20 && cfg <= 24) || cfg == 32; }
-bool gemm_w_block_wanted(const GemmParams& p0) {
-    GemmParams p = p0;
-    p.debug = g_gemm_debug;
-    if (!p.force_cfg) p.force_cfg = g_force_cfg;
-    if (p.debug & 0x4000000) return false;                    // tuning bit 26: row-major weights everywhere
-    // a request of 8 weight rows spans 16 K bytes: beyond 16 KB it leaves the fast path of the load unit (K > 1024)
-    if (p.K % 64 || p.N % 8 || p.K <= 1024 || p.batch > 1 || p.w_sample_stride || p.out_mode == OUT_BF16_T) return false;
-    if (!p.A2) { p.C1 = p.mode == GEMM_LINEAR ? p.K : p.Cin; p.A2 = p.A; p.lda2 = p.lda; }
-    if (p.mode == GEMM_CONV3 && (p.Cin % 64 || p.C1 % 64)) return false;      // (the conv K order walks whole 64-channel chunks)
-    if (p.rows_per_sample <= 0) p.rows_per_sample = 1;
-    int splits = 1;
-    const int cfg = p.force_cfg ? (p.force_cfg & 0xff) : plan_cfg(p, &splits);
-    return w_block_cfg(cfg);
-}
-
 // (Round 5: a weight PREFETCHER was built and removed again - per handle, the sequence of weight buffers a call's GEMM launches read
 //  was recorded and replayed one <= N MB group ahead by a one-dword-per-line kernel on a second low-priority stream, ordered behind
 //  events on the main stream, so that every launch would find its weights in the Infinity Cache instead of cold in HBM.  Results
 //  bit-identical, and SLOWER at every group size (16 / 48 / 128 MB): UNet call 5.70 -> 6.41 - 6.54 ms at batch 2, 16.85 -> 17.36 at
 //  batch 16 (profiles/r05_weight_prefetch_ab.txt): the extra 1.7 GB of requests per call queue in front of the latency-bound loads
 //  of the launches they were meant to help, and an Infinity-Cache hit is not enough faster than HBM to pay that back.)
-int launch_gemm(hipStream_t st, const GemmParams& p0) {
-    GemmParams p = p0;
-    if (!p.force_cfg) p.force_cfg = g_force_cfg;
-    p.debug = g_gemm_debug;
+int launch_gemm(hipStream_t st, const GemmParams& p0) { return launch_gemm(st, p0, gemm_plan(p0)); }
+int launch_gemm(hipStream_t st, const GemmParams& p0, const GemmPlan& plan) {
+    GemmParams p = gemm_normalised(p0);
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) GYRE_FAIL(-1, "gemm: empty problem");
     if (p.K % 8) GYRE_FAIL(-1, "gemm: K must be a multiple of 8");
-    if (!p.A2) { p.C1 = p.mode == GEMM_LINEAR ? p.K : p.Cin; p.A2 = p.A; p.lda2 = p.lda; }
     if (p.C1 % 8) GYRE_FAIL(-1, "gemm: source split must be a multiple of 8");
     if (p.mode == GEMM_CONV3) {
         if (p.Cin % 8 || p.K != 9 * p.Cin + p.sc_K) GYRE_FAIL(-1, "conv3x3: Cin must be a multiple of 8 and K == 9*Cin (+ the folded shortcut's channels)");
@@ -1666,7 +1625,6 @@ int launch_gemm(hipStream_t st, const GemmParams& p0) {
     if (p.out_mode == OUT_BF16 && (p.N % 4 || p.ldc % 4 || (p.residual && p.ldr % 4)))
         GYRE_FAIL(-1, "gemm: N / ldc / ldr must be multiples of 4 for bf16 row-major output");
     if (p.geglu && (p.N % 32)) GYRE_FAIL(-1, "gemm: GEGLU needs N % 32 == 0");
-    if (p.rows_per_sample <= 0) p.rows_per_sample = 1;
     if (p.out_mode == OUT_BF16_T && p.tokens_per_batch <= 0) GYRE_FAIL(-1, "gemm: tokens_per_batch required");
     if (p.batch > 1 && (p.mode != GEMM_LINEAR || p.out_mode != OUT_BF16 || p.bias || p.residual || p.rowbias || p.geglu || p.vt_out))
         GYRE_FAIL(-1, "gemm: the batched form is a plain bf16 matrix product");
@@ -1680,18 +1638,15 @@ int launch_gemm(hipStream_t st, const GemmParams& p0) {
     if (p.ln_colsum && (p.mode != GEMM_LINEAR || p0.A2 || !p.bias || (!p.ln_stats && p.ln_nparts <= 0) || (p.ln_nparts > 0 && !p.ln_parts) ||
                         p.rowbias || p.out_mode != OUT_BF16 || p.batch > 1))
         GYRE_FAIL(-1, "gemm: the folded LayerNorm needs a single-source linear problem with row statistics, bias and bf16 row-major output");
-    if (p.sc_K && (!p.sc_A2 || p.sc_A2 == p.sc_A)) { p.sc_A2 = p.sc_A; p.sc_lda2 = p.sc_lda; p.sc_C1 = p.sc_K; }
-    int splits = 1;
-    int cfg = plan_cfg(p, &splits);
     {   // tuning aid (tools/gemm_sweep.py): GYRE_GEMM_DUMP=1 prints every problem shape with the planner's choice
         static const bool dump = getenv("GYRE_GEMM_DUMP") != nullptr;
         if (dump)
             fprintf(stderr, "GYRE_GEMM mode=%d M=%d N=%d K=%d Cin=%d C1=%d Hi=%d Wi=%d stride=%d ups=%d geglu=%d res=%d rowbias=%d "
                             "out=%d vt=%d batch=%d samples=%d cfg=%d splits=%d\n", p.mode, p.M, p.N, p.K, p.Cin, p.C1, p.Hi, p.Wi,
                     p.stride, p.ups, p.geglu, p.residual ? 1 : 0, p.rowbias ? 1 : 0, p.out_mode, p.vt_out ? 1 : 0, p.batch, p.samples,
-                    cfg, splits);
+                    plan.cfg, plan.splits);
     }
-    if (p.force_cfg) { cfg = p.force_cfg & 0xff; splits = (p.force_cfg >> 8) & 0xff; if (splits < 1) splits = 1; }
+    int cfg = plan.cfg, splits = plan.splits;
     if (splits > 1) {
         if (!p.splitk_ws) { p.splitk_ws = g_dbg_ws; p.splitk_ws_bytes = g_dbg_ws_bytes; }
         if (!p.splitk_ws || p.splitk_ws_bytes < (size_t)splits * p.M * p.N * sizeof(float)) {
@@ -1699,32 +1654,24 @@ int launch_gemm(hipStream_t st, const GemmParams& p0) {
             cfg = pick_cfg_nosplit(p);
         }
     }
-    if (p.vt_out) {
-        const int tn = cfg == 4 ? 160 : (cfg == 5 || cfg == 8) ? 80 : cfg == 6 ? 128 : (cfg == 7 || cfg == 30 || cfg == 32) ? 64 : 0;
-        if (!tn || splits > 1 || p.vt_col0 % tn) GYRE_FAIL(-6, "gemm: fused Q|K|V needs an 8-wave tile config whose wave tiles align with the V columns");
-    }
-    if (p.colstat_out) {
-        GemmParams q = p0;
-        q.splitk_ws = nullptr;
-        const int rows = gemm_colstat_rows(q);
-        const int want = splits > 1 ? cs_red_rows(p.rows_per_sample) : cfg == 4 ? 256 : (cfg == 5 || cfg == 8) ? 128 : (cfg == 24 && p.mode == GEMM_CONV3) ? 256 : -1;
-        if (rows <= 0 || rows != want)
-            GYRE_FAIL(-6, "gemm: column statistics are not available for this problem / tile configuration (see gemm_colstat_rows)");
-    }
-    if (p.w_sample_stride) {
-        const int bm = (cfg == 4 || cfg == 6) ? 256 : 128;
-        if (cfg < 4 || cfg > 8 || splits > 1 || p.mode != GEMM_LINEAR || p.rows_per_sample % bm || p.M % p.rows_per_sample)
-            GYRE_FAIL(-6, "gemm: per-sample weights need an unsplit 8-wave tile config whose row blocks do not straddle samples (gemm_per_sample_w_ok)");
-    }
-    if (p.mode == GEMM_CONV3 && p.wrap && cfg > 3) GYRE_FAIL(-6, "gemm: circular padding (tiling) exists in the 4-wave tile configs only");
-    if (p.sc_K && cfg != 24) GYRE_FAIL(-6, "gemm: the folded shortcut exists in the pipelined 256x320 tile only (see gemm_conv_shortcut_ok)");
-    if (!p.W_blk && g_dbg_blk_ws && gemm_w_block_wanted(p0) && g_dbg_blk_ws_bytes >= (size_t)p.N * p.K * 2) {   // tests / tuning
+    const GemmTile* t = gemm_tile(cfg);
+    if (!t) GYRE_FAIL(-1, "gemm: unknown tile config");
+    // features the planned kernel lacks (the plan's answers hold for plan.cfg / plan.splits only)
+    if (p.vt_out && (!t->vt_align || splits > 1 || p.vt_col0 % t->vt_align))
+        GYRE_FAIL(-6, "gemm: fused Q|K|V needs an 8-wave tile config whose wave tiles align with the V columns");
+    if (p.colstat_out && (plan.colstat_rows <= 0 || splits != plan.splits))
+        GYRE_FAIL(-6, "gemm: column statistics are not available for this problem / tile configuration (see GemmPlan::colstat_rows)");
+    if (p.w_sample_stride && (!t->per_sample_w || splits > 1 || p.mode != GEMM_LINEAR || p.rows_per_sample % t->bm || p.M % p.rows_per_sample))
+        GYRE_FAIL(-6, "gemm: per-sample weights need an unsplit 8-wave tile config whose row blocks do not straddle samples (GemmPlan::per_sample_w)");
+    if (p.mode == GEMM_CONV3 && p.wrap && t->kind != GEMM_K_4W) GYRE_FAIL(-6, "gemm: circular padding (tiling) exists in the 4-wave tile configs only");
+    if (p.sc_K && !t->shortcut) GYRE_FAIL(-6, "gemm: the folded shortcut exists in the pipelined 256x320 tile only (see GemmPlan::shortcut_fold)");
+    if (!p.W_blk && g_dbg_blk_ws && plan.w_block && g_dbg_blk_ws_bytes >= (size_t)p.N * p.K * 2) {   // tests / tuning
         int rc = launch_w_block(st, p.W, p.N, p.K, g_dbg_blk_ws);
         if (rc) return rc;
         p.W_blk = g_dbg_blk_ws;
     }
-    if (p.W_blk && (!w_block_cfg(cfg) || p.K % 64 || p.N % 8 || p.w_sample_stride || (p.mode == GEMM_CONV3 && (p.Cin % 64 || p.C1 % 64)))) p.W_blk = nullptr;
-    if (cfg == 30) {
+    if (p.W_blk && (!t->w_block || p.K % 64 || p.N % 8 || p.w_sample_stride || (p.mode == GEMM_CONV3 && (p.Cin % 64 || p.C1 % 64)))) p.W_blk = nullptr;
+    if (t->kind == GEMM_K_AR) {
         if (splits > 1 || !gemm_ar_supports(p)) GYRE_FAIL(-6, "gemm: problem outside the A-resident kernel's domain (K = 320 / 640 linear, bf16 row-major output)");
         const void* wpk = p.w_packed;
         if (!wpk) {       // tests / tuning: pack into the caller's scratch buffer on the fly
@@ -1736,17 +1683,17 @@ int launch_gemm(hipStream_t st, const GemmParams& p0) {
         }
         return launch_gemm_ar(st, p, wpk);
     }
-    if (cfg == 32) {
+    if (t->kind == GEMM_K_SM) {
         if (splits > 1) GYRE_FAIL(-6, "gemm: the small-problem kernel has no split-K form");
         return launch_gemm_sm(st, p);
     }
-    if (p.rowstat_out && (cfg < 4 || cfg > 8 || splits > 1 || !gemm_staged_epilogue_ok(p)))
-        GYRE_FAIL(-6, "gemm: row statistics need an unsplit 8-wave tile config with the staged epilogue (see gemm_rowstat_parts)");
-    if (p.ln_colsum && ((cfg != 24 && (cfg < 4 || cfg > 8)) || splits > 1 || !gemm_staged_epilogue_ok(p)))
-        GYRE_FAIL(-6, "gemm: the folded LayerNorm needs an unsplit 8-wave tile config with the staged epilogue (see gemm_ln_fusable)");
-    if (cfg >= 4) {
+    if (p.rowstat_out && (!t->rowstats || splits > 1 || !gemm_staged_epilogue_ok(p)))
+        GYRE_FAIL(-6, "gemm: row statistics need an unsplit 8-wave tile config with the staged epilogue (see GemmPlan::rowstat_parts)");
+    if (p.ln_colsum && (!t->ln_fold || splits > 1 || !gemm_staged_epilogue_ok(p)))
+        GYRE_FAIL(-6, "gemm: the folded LayerNorm needs an unsplit 8-wave tile config with the staged epilogue (see GemmPlan::ln_fold)");
+    if (t->kind != GEMM_K_4W) {
         if (p.out_mode == OUT_BF16_T) GYRE_FAIL(-6, "gemm: transposed output needs a 4-wave config");
-        if (p.geglu && (cfg == 4 || cfg == 5 || cfg == 8)) GYRE_FAIL(-6, "gemm: GEGLU needs an even fragment count per wave");
+        if (p.geglu && !t->geglu) GYRE_FAIL(-6, "gemm: GEGLU needs an even fragment count per wave");
         p.zero_page = gemm_zero_page_for_current_device();
         if (!p.zero_page) GYRE_FAIL(-5, "gemm: cannot allocate the zero page");
     }
@@ -1762,7 +1709,6 @@ int launch_gemm(hipStream_t st, const GemmParams& p0) {
             return launch_cfg8<256, 128, 4, 2>(st, p, KC_G8_X1, splits);
         case 7: return launch_cfg8<128, 256, 2, 4>(st, p, KC_G8_CONV_128x256, splits);
         case 8: return launch_cfg8<128, 160, 4, 2>(st, p, KC_G8_CONV_128x160, splits);
-        case 20: case 21: case 22: case 23: case 24: return launch_gemm4s(st, p, cfg, splits);
-        default: GYRE_FAIL(-1, "gemm: unknown tile config");
+        default: return launch_gemm4s(st, p, cfg, splits);
     }
 }

@@ -564,8 +564,9 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
 // Shapes the 4s kernels take: bf16 row-major output (or split-K slabs), 16-byte addressable rows, K steps that are
 // whole 64-channel chunks of one source (so a step never needs zero fill along K), at least one K step per split.
 bool gemm4s_supports(const GemmParams& p, int cfg) {
-    if (cfg < 20 || cfg > 24) return false;
-    const int bn = (cfg == 20 || cfg == 22 || cfg == 24) ? 320 : 256;
+    const GemmTile* t = gemm_tile(cfg);
+    if (!t || t->kind != GEMM_K_4S) return false;
+    const int bn = t->bn;
     if (p.out_mode != OUT_BF16 || p.vt_out) return false;
     const int n_out = p.geglu ? p.N / 2 : p.N;
     if (n_out % 8 || p.ldc % 8 || (p.residual && p.ldr % 8) || (((size_t)p.out | (size_t)p.residual) & 15)) return false;
@@ -638,7 +639,7 @@ static int launch_cfg4s(hipStream_t st, const GemmParams& p, int kcls_base, int 
         }
     } else if (p.mode == GEMM_LINEAR) GYRE_GEMM4S_GO(GEMM_LINEAR, 0);
 #ifndef GYRE_GEMM_ABLATIONS
-    else if (p.debug & 0x200) GYRE_GEMM4S_GO(GEMM_CONV3, 1);
+    else if (p.debug & GEMM_DBG_CONV_ZERO_PAGE) GYRE_GEMM4S_GO(GEMM_CONV3, 1);
 #endif
     else GYRE_GEMM4S_GO(GEMM_CONV3, 0);
 #undef GYRE_GEMM4S_GO

@@ -474,7 +474,7 @@ int gyre_op_conv3x3_shortcut(void* st, const void* x, int B, int H, int W, int C
     p.sc_A = (const bf16_t*)sx; p.sc_lda = C1; p.sc_C1 = C1; p.sc_K = C1 + C2;
     if (C2 > 0) { p.sc_A2 = (const bf16_t*)sx2; p.sc_lda2 = C2; }
     p.K = 9 * Cin + p.sc_K;
-    if (!gemm_conv_shortcut_ok(p)) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "conv3x3_shortcut: the planner's kernel for this shape does not fold the shortcut");
+    if (!gemm_plan(p).shortcut_fold) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "conv3x3_shortcut: the planner's kernel for this shape does not fold the shortcut");
     const size_t wbytes = align_up((size_t)Cout * p.K * 2, 256);
     if (ws_bytes < wbytes + align_up((size_t)Cout * 4, 256)) GYRE_FAIL(GYRE_ERR_WORKSPACE, "conv3x3_shortcut: workspace too small");
     bf16_t* wcat = (bf16_t*)ws;
@@ -505,11 +505,11 @@ static int op_colstats_go(hipStream_t st, GemmParams& p, int unit, int rps, floa
     if (unit <= 0 || rps <= 0 || p.M <= 0 || p.N <= 0 || p.M % rps || p.N % unit)
         GYRE_FAIL(GYRE_ERR_INVALID, "colstats: unit and rows per sample must be positive and divide N and M");
     p.colstat_unit = unit; p.rows_per_sample = rps;
-    const int rows = gemm_colstat_rows(p);
+    const GemmPlan pl = gemm_plan(p);
+    const int rows = pl.colstat_rows;
     if (rows_out) *rows_out = rows;
     if (rows <= 0) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "colstats: the planner's kernel for this shape cannot emit column statistics");
     if (stats_bytes < (size_t)(p.M / rows) * (p.N / unit) * 2 * sizeof(float)) GYRE_FAIL(GYRE_ERR_WORKSPACE, "colstats: stats buffer too small");
-    GemmPlan pl = gemm_plan(p);
     if (pl.ws_bytes) {
         if (!ws || ws_bytes < pl.ws_bytes) GYRE_FAIL(GYRE_ERR_WORKSPACE, "colstats: split-K workspace too small");
         p.splitk_ws = (float*)ws; p.splitk_ws_bytes = ws_bytes;
@@ -594,7 +594,7 @@ int gyre_op_linear_rowstats_parts(int M, int K, int N, int has_residual) {
     GemmParams p;
     p.lda = K; p.mode = GEMM_LINEAR; p.K = K; p.N = N; p.M = M; p.ldr = N; p.ldc = N; p.out_mode = OUT_BF16;
     if (has_residual) p.residual = (const bf16_t*)(uintptr_t)256;      // shape query only: any aligned non-null value
-    return gemm_rowstat_parts(p);
+    return gemm_plan(p).rowstat_parts;
 }
 int gyre_op_linear_rowstats(void* st, const void* x, int M, int K, const void* w, int N, const float* bias, const void* residual,
                             void* y, float* stats_out) {
@@ -603,7 +603,7 @@ int gyre_op_linear_rowstats(void* st, const void* x, int M, int K, const void* w
     p.A = (const bf16_t*)x; p.lda = K; p.mode = GEMM_LINEAR; p.W = (const bf16_t*)w; p.K = K;
     p.N = N; p.M = M; p.bias = bias; p.residual = (const bf16_t*)residual; p.ldr = N;
     p.out = y; p.ldc = N; p.out_mode = OUT_BF16;
-    if (gemm_rowstat_parts(p) <= 0) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "linear_rowstats: the planner's kernel for this shape cannot emit row statistics");
+    if (gemm_plan(p).rowstat_parts <= 0) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "linear_rowstats: the planner's kernel for this shape cannot emit row statistics");
     p.rowstat_out = stats_out;
     return launch_gemm((hipStream_t)st, p);
 }
@@ -622,7 +622,7 @@ int gyre_op_ln_linear(void* st, const void* x, int M, int K, const float* gamma,
         p.N = geglu ? 2 * N : N; p.ldc = N; p.geglu = geglu;
     }
     if (ws_bytes < gyre_op_ln_linear_workspace(p.N, K, M)) GYRE_FAIL(GYRE_ERR_WORKSPACE, "ln_linear: workspace too small");
-    if (!gemm_ln_fusable(p)) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "ln_linear: the planner's kernel for this shape cannot fold the LayerNorm");
+    if (!gemm_plan(p).ln_fold) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "ln_linear: the planner's kernel for this shape cannot fold the LayerNorm");
     bf16_t* wf = (bf16_t*)ws;
     float* cs = (float*)((char*)ws + align_up((size_t)p.N * K * 2, 256));
     float* bb = (float*)((char*)cs + align_up((size_t)p.N * 4, 256));

@@ -350,7 +350,7 @@ struct Exec {
         if (!p.samples) p.samples = batch;
         GemmParams q = p;
         q.colstat_unit = cs_unit; q.rows_per_sample = rps;
-        const int rows = gemm_colstat_rows(q);
+        const int rows = gemm_plan(q).colstat_rows;
         if (rows <= 0 || rps / rows > 64) return 0;        // the apply prologue of every workgroup re-reads all chunks
         y.cs_chunks = rps / rows; y.cs_unit = cs_unit;
         y.cs_bytes = (size_t)y.B * y.cs_chunks * (p.N / cs_unit) * 2 * sizeof(float);
@@ -410,22 +410,19 @@ struct Exec {
         free(ws);
         return 0;
     }
-    // runs one GEMM launch, giving it split-K slab space from the arena when the planner wants it
     // A-resident kernel (tile config 30): the packed weight copy, made per handle on first use (and after any weight change)
-    int prep_ar(GemmParams& p) {
-        if (dry()) return 0;
-        const int cfg = gemm_plan(p).cfg;
-        if (cfg != 30) return 0;
+    int prep_ar(GemmParams& p, const GemmPlan& pl) {
+        if (dry() || !pl.ar_pack) return 0;
         bool fresh = false;
-        void* pk = store ? store->ar_lookup(p.W, gemm_ar_packed_bytes(p.N, p.K), &fresh, cfg) : nullptr;
+        void* pk = store ? store->ar_lookup(p.W, gemm_ar_packed_bytes(p.N, p.K), &fresh, pl.cfg) : nullptr;
         if (!pk) GYRE_FAIL(GYRE_ERR_HIP, "cannot allocate the packed weight copy of the A-resident GEMM");
         if (!fresh) TRY(launch_ar_pack(st, p.W, p.N, p.K, pk));
         p.w_packed = pk;
         return 0;
     }
     // blocked weight copy for the LDS-DMA tile kernels (GemmParams::W_blk), made per handle on first use (and after any weight change)
-    int prep_blk(GemmParams& p) {
-        if (dry() || !store || p.W_blk || !gemm_w_block_wanted(p)) return 0;
+    int prep_blk(GemmParams& p, const GemmPlan& pl) {
+        if (dry() || !store || p.W_blk || !pl.w_block) return 0;
         bool fresh = false;
         bf16_t* b = store->blk_lookup(p.W, (size_t)p.N * p.K * 2, &fresh);
         if (!b) { (void)hipGetLastError(); return 0; }           // no memory for the copy: the kernels read the row-major weights (W_blk stays null)
@@ -433,17 +430,18 @@ struct Exec {
         p.W_blk = b;
         return 0;
     }
+    // runs one GEMM launch on one plan: weight copies, split-K slab space from the arena when the planner wants it
     int run_gemm(GemmParams& p) {
         if (!p.samples) p.samples = batch;
-        GemmPlan pl = gemm_plan(p);
-        TRY(prep_ar(p));
-        TRY(prep_blk(p));
+        const GemmPlan pl = gemm_plan(p);
+        TRY(prep_ar(p, pl));
+        TRY(prep_blk(p, pl));
         Tn ws;
         if (pl.ws_bytes) {
             TRY(alloc_raw(ws, pl.ws_bytes));
             p.splitk_ws = (float*)ws.p; p.splitk_ws_bytes = pl.ws_bytes;
         }
-        int rc = dry() ? 0 : launch_gemm(st, p);
+        int rc = dry() ? 0 : launch_gemm(st, p, pl);
         free(ws);
         return rc;
     }
@@ -504,7 +502,7 @@ struct Exec {
         if (dry()) p.A = (const bf16_t*)(uintptr_t)256;
         fill_shortcut(p, sx, sskip);
         if (dry()) { p.sc_A = (const bf16_t*)(uintptr_t)256; if (sskip) p.sc_A2 = (const bf16_t*)(uintptr_t)256; }
-        return gemm_conv_shortcut_ok(p);
+        return gemm_plan(p).shortcut_fold;
     }
     // final 3x3 conv straight to the caller's NCHW buffer
     int conv3_nchw(const Tn& x, const ConvW& w, void* out, int out_dtype) {
@@ -538,7 +536,7 @@ struct Exec {
         if (cs_for && !rs) TRY(attach_colstats(p, *cs_for, cs_for->H * cs_for->W));
         if (rs) {
             if (!p.samples) p.samples = batch;
-            rs->nparts = store ? gemm_rowstat_parts(p) : 0;
+            rs->nparts = store ? gemm_plan(p).rowstat_parts : 0;
             if (rs->nparts > 0) {
                 TRY(alloc_raw(rs->t, (size_t)rs->nparts * M * 2 * sizeof(float)));
                 p.rowstat_out = (float*)rs->t.p;
@@ -570,13 +568,14 @@ struct Exec {
         p.A = x.p; p.lda = C; p.mode = GEMM_LINEAR; p.W = w; p.K = C; p.N = N; p.M = M; p.samples = batch;
         p.out = y.p; p.ldc = y.C; p.out_mode = OUT_BF16; p.rows_per_sample = HW; p.ld_rowbias = N;
         p.rowbias = (const float*)(uintptr_t)256;              // (planning only: any aligned non-null value)
-        if (!gemm_per_sample_w_ok(p)) return 0;
+        const GemmPlan pl = gemm_plan(p);
+        if (!pl.per_sample_w) return 0;
         Tn ws, wf, bfv;
         TRY(alloc_raw(ws, gn_workspace_bytes(x.B, HW, C, groups)));
         TRY(alloc_raw(wf, (size_t)x.B * N * C * 2));
         TRY(alloc_raw(bfv, (size_t)x.B * N * sizeof(float)));
         if (rs) {
-            rs->nparts = gemm_rowstat_parts(p);
+            rs->nparts = pl.rowstat_parts;
             if (rs->nparts > 0) TRY(alloc_raw(rs->t, (size_t)rs->nparts * M * 2 * sizeof(float)));
         }
         if (!dry()) {
@@ -609,7 +608,6 @@ struct Exec {
     // rows with the layer's own weights / bias; on return it points at the gamma-folded copies (made on first use per handle,
     // refreshed after any gyre_*_set_weight) and the launch normalises on the fly - the normalised tensor never exists.
     struct LnFold { const float* g; const float* b; const RowStatBuf* have = nullptr; };
-    bool ln_fusable(const GemmParams& p) const { return store && gemm_ln_fusable(p); }
     // `stats`: arena scratch for the per-row statistics (one streaming pass over the rows); freed by the caller after the launch
     int ln_fold_into(GemmParams& p, const LnFold& ln, Tn& stats) {
         if (ln.have && ln.have->nparts > 0) {           // the producer of these rows left their partial sums
@@ -634,7 +632,7 @@ struct Exec {
         GemmParams p;
         p.A = x.p; p.lda = x.C; p.mode = GEMM_LINEAR; p.W = w; p.K = x.C; p.N = N; p.M = x.rows(); p.bias = bias; p.geglu = geglu;
         p.out = y; p.ldc = ldc; p.out_mode = OUT_BF16; p.samples = batch; p.ar_ok = store != nullptr;
-        if (ln_fusable(p)) {
+        if (store && gemm_plan(p).ln_fold) {
             Tn stats;
             TRY(ln_fold_into(p, ln, stats));
             int rc = run_gemm(p);
@@ -709,23 +707,22 @@ struct Exec {
                 p.vt_out = vt.p; p.vt_col0 = 2 * C; p.tokens_per_batch = Nq; p.ldt = ldvt;
                 p.ar_ok = store != nullptr;
                 if (dry()) { p.out = (void*)(uintptr_t)256; p.vt_out = (bf16_t*)(uintptr_t)256; p.A = (const bf16_t*)(uintptr_t)256; }  // (planning: aligned non-null)
-                GemmPlan pl = gemm_plan(p);
-                // (config 30 = the A-resident kernel: its 64-row weight tiles line up with the V columns whenever 2 C % 64 == 0)
-                const int tn = pl.cfg == 4 ? 160 : (pl.cfg == 5 || pl.cfg == 8) ? 80 : pl.cfg == 6 ? 128 : (pl.cfg == 7 || pl.cfg == 30 || pl.cfg == 32) ? 64 : 0;
-                if (tn && pl.splits == 1 && (2 * C) % tn == 0) {
+                const GemmPlan pl = gemm_plan(p);
+                if (pl.vt_align && pl.splits == 1 && (2 * C) % pl.vt_align == 0) {
                     fused = true;
                     Tn stats;
-                    if (ln && ln_fusable(p)) {
+                    if (ln && store && pl.ln_fold) {
                         TRY(ln_fold_into(p, *ln, stats));
                         ln = nullptr;
                     } else {
                         TRY(normalise());
                         p.A = xq.p;
                     }
-                    if (!dry()) {
-                        TRY(prep_ar(p));
-                        TRY(prep_blk(p));
-                        TRY(launch_gemm(st, p));
+                    if (!dry()) {     // (p now holds the folded or the normalised rows: plan it again)
+                        const GemmPlan pf = gemm_plan(p);
+                        TRY(prep_ar(p, pf));
+                        TRY(prep_blk(p, pf));
+                        TRY(launch_gemm(st, p, pf));
                     }
                     free(stats);
                 }
@@ -741,7 +738,7 @@ struct Exec {
             // Round 6: the whole block - to_q with the folded LayerNorm, attention over the cached text keys, to_out + bias + residual
             // and the row statistics for the next LayerNorm - as ONE kernel per 128 rows (kernels_xattn.hip) where the shape fits it
             // (SD1.x's 64x64 level); inference path with a context cache only; tuning bit 13 of gyre_debug_gemm_ablation = off
-            if (ln && !sv && ctx_cache && store && !w.bq && w.k_prescaled && residual.p == xq_in.p && !(gemm_planner_state() & 0x2000L) &&
+            if (ln && !sv && ctx_cache && store && !w.bq && w.k_prescaled && residual.p == xq_in.p && !(gemm_planner_state() & GEMM_DBG_NO_XATTN) &&
                 // (batch-invariant planning: the grid-size rule is evaluated for the canonical batch, so that every split of a request
                 //  takes the same path - a sub-batch then runs the fused kernel on a small grid, slower and bit-identical)
                 xattn_supports(C, w.heads, Nq, Nk, gemm_get_batch_invariant() > 0 ? gemm_get_batch_invariant() * Nq : B * Nq)) {
