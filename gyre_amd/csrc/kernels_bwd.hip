@@ -1015,7 +1015,7 @@ __device__ __forceinline__ void abw_dq_lds_body(const AttnBwdParams& p) {
     // ---- ONE pass (round 6, as k_attn_bwd_dq_dma): dQ^T[d][q] += K^T[d][keys] dS^T[keys][q] against a running reference, divided
     // by the row sum at the end; the separate log-sum-exp pass over K is gone ----
 #ifdef GYRE_STORE_F16
-    constexpr float RECENTRE = 8.f;
+    constexpr float RECENTRE = 0.f;       // fp16 dS operand: p <= 1, as in k_attn_bwd_dq_dma
 #else
     constexpr float RECENTRE = 20.f;
 #endif
@@ -1297,7 +1297,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
 // normalisation is linear in the accumulator - dQ = (1 / l) sum_k 2^(s_k - m) (dP_k - delta) K_k with l = sum_k 2^(s_k - m) for ANY
 // reference m - so the kernel keeps a reference per query, accumulates against it and divides at the end, like the forward kernel's
 // output; the reference is re-centred (accumulators and l rescaled, wave-uniform branch) on the first tile and whenever a score
-// exceeds it by more than 2^RECENTRE (p <= 2^20: harmless in fp32 sums and in the bf16 dS operand; 2^8 in the fp16 build) - in practice once per row.
+// exceeds it by more than 2^RECENTRE (p <= 2^20: harmless in fp32 sums and in the bf16 dS operand; p <= 1 in the fp16 build) - in practice once per row.
 // Lanes l and l + 32 hold the same query (different keys of the tile) and meet in the MFMA contraction, so they share the reference.
 // The row log-sum-exp m + log2(l) goes to p.lse for the dK / dV kernel.  26 -> 20 MFMAs and half the exponentials per 64 keys.
 template <int D>
@@ -1306,7 +1306,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     constexpr int DS = T::DS, NDB = T::NDB, RS = T::RS, NV = T::NV, NS = T::NS, STAGE = T::STAGE;
     constexpr int PPW = (2 * NV + 3) / 4;
 #ifdef GYRE_STORE_F16
-    constexpr float RECENTRE = 8.f;      // dS = p (dP - delta) is an fp16 MFMA operand: p <= 2^8 leaves |dP - delta| < 255 before 65504
+    // dS = p (dP - delta) is an fp16 MFMA operand: with p <= 2^8 it overflowed 65504 once |dP - delta| passed 255, which a scaled
+    // guidance loss (x 500 guidance_scale) reaches.  A reference that follows every new row maximum keeps p <= 1 - the range of
+    // the normalised P the two-pass kernels use - and p >= P, so the fp16 subnormal floor of dS is no worse than theirs either.
+    constexpr float RECENTRE = 0.f;
 #else
     constexpr float RECENTRE = 20.f;
 #endif
