@@ -49,14 +49,17 @@ def report(name, got, ref, tol):
     assert e <= tol, f"{name}: rel_l2 {e:.3e} > {tol}"
 
 
-def check_bound(name, got, ref, bound, k=4.0, tiny=0.0, dims=None):
+def check_bound(name, got, ref, bound, k=4.0, tiny=0.0, dims=None, hdt=None, enforce=True):
     """Element-wise  |got - ref| <= k u bound + u |ref| + tiny  (u = unit roundoff of the 16-bit storage, HDT: 2^-8 bf16, 2^-11
     fp16); bound = the float64 absolute-value form of the same computation, tiny an absolute floor (scalar or tensor).  Prints the
-    worst ratio |got - ref| / tolerance and where it is (dims names the axes), pass or fail; NaN / inf in got fails."""
-    u = 2.0 ** -8 if HDT == torch.bfloat16 else 2.0 ** -11
+    worst ratio |got - ref| / tolerance and where it is (dims names the axes), pass or fail; NaN / inf in got fails.  hdt: judge for
+    that storage type instead of the flavour under test (host self-tests of an error model); enforce = False: return the ratio
+    without asserting (seeded mistakes that are meant to exceed it)."""
+    hdt = HDT if hdt is None else hdt
+    u = 2.0 ** -8 if hdt == torch.bfloat16 else 2.0 ** -11
     g, r, b = got.double().cpu(), ref.double().cpu(), bound.double().cpu()
     tiny = tiny.double().cpu() if torch.is_tensor(tiny) else tiny
-    floor = 2.0 ** -134 if HDT == torch.bfloat16 else 2.0 ** -25      # half the smallest subnormal: the output's own rounding floor
+    floor = 2.0 ** -134 if hdt == torch.bfloat16 else 2.0 ** -25      # half the smallest subnormal: the output's own rounding floor
     tol = k * u * b + u * r.abs() + tiny + floor
     ratio = ((g - r).abs() / tol.clamp_min(1e-300)).nan_to_num(nan=float("inf"))
     flat = int(ratio.flatten().argmax())
@@ -64,7 +67,7 @@ def check_bound(name, got, ref, bound, k=4.0, tiny=0.0, dims=None):
     idx = list(zip(dims, _unravel(flat, ratio.shape))) if dims else _unravel(flat, ratio.shape)
     print(f"[bound] {name}: worst ratio {worst:.3g} (k={k}) at {idx}: got {float(g.flatten()[flat]):.6g} "
           f"ref {float(r.flatten()[flat]):.6g} bound {float(b.flatten()[flat]):.6g}")
-    assert worst <= 1.0, f"{name}: |got - ref| exceeds k u bound + u |ref| + tiny by {worst:.3g}x at {idx}"
+    assert worst <= 1.0 or not enforce, f"{name}: |got - ref| exceeds k u bound + u |ref| + tiny by {worst:.3g}x at {idx}"
     return worst
 
 
