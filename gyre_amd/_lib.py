@@ -117,6 +117,9 @@ _SIGS = {
     "gyre_debug_set_ar_workspace": (_i, [_vp, _sz]),
     "gyre_debug_set_wblk_workspace": (_i, [_vp, _sz]),
     "gyre_debug_attn_redo_count": (C.c_long, []),
+    "gyre_debug_attn_plan": (_i, [_i] * 10 + [C.POINTER(C.c_int32)]),
+    "gyre_debug_attn_bwd_plan": (_i, [_i] * 6 + [C.POINTER(C.c_int32)]),
+    "gyre_debug_attn_tables": (_i, [_i, C.POINTER(C.c_int32), _i]),
     "gyre_debug_xattn_stamps": (_i, [_vp]),
     "gyre_debug_force_attn_variant": (_i, [_i]),
     "gyre_debug_gemm_ablation": (_i, [_i]),

@@ -223,6 +223,33 @@ struct AttnParams {
     int always_check = 0;       // tuning (k_attn3): keep the per-tile overflow check instead of the optimistic first pass
     unsigned* redo_counter = nullptr;   // incremented by every workgroup that repeats its pass (per device; gyre_debug_attn_redo_count)
 };
+// Values of gyre_debug_force_attn_variant (bits 0 .. 7; bits 8 and up: the ablation id of GYRE_ATTN_ABLATIONS builds).
+enum AttnVariant {
+    ATTN_VAR_AUTO = 0,           // the rule of attn_plan()
+    ATTN_VAR_V1 = 1,             // k_attn
+    ATTN_VAR_V2_PLAIN = 2,       // k_attn2, plain online softmax
+    ATTN_VAR_V2_FOLD = 3,        // k_attn2 FOLD where K is prescaled and the head dim has the form
+    ATTN_VAR_V2_Q64 = 4,         // k_attn2 plain with 64 query rows per wave (QI = 4; D <= 32)
+    ATTN_VAR_V3 = 5,             // k_attn3 whatever the key count
+    ATTN_VAR_NO_QLOOP = 6,       // automatic, without the several-query-blocks-per-workgroup form of short key sequences
+    ATTN_VAR_ALWAYS_CHECK = 7,   // automatic, k_attn3 with the per-tile overflow check from the start
+    ATTN_VAR_AUTO_ALIAS = 8,     // a synonym of 0, kept for the tools
+};
+enum AttnFamily { ATTN_FAM_V1 = 0, ATTN_FAM_V2_PLAIN = 1, ATTN_FAM_V2_FOLD = 2, ATTN_FAM_V3 = 3 };
+// What one launch_attention call runs, decided once on the host (no HIP call, no global state).
+struct AttnPlan {
+    int status = 0; std::string error;       // status != 0: the launch is refused with this code and message
+    int family = 0, D = 0, QI = 0, row = -1; // AttnFamily; row of the launch table (kernels_attn.hip)
+    int PD = 0, slots = 0, stage_bytes = 0;  // LDS-DMA ring: lookahead, slot count, bytes per slot (0 for k_attn)
+    int lds_bytes = 0;                       // dynamic LDS of the launch
+    dim3 grid;
+    bool qloop = false; int qiter = 1;       // k_attn2: query blocks per workgroup
+    bool always_check = false;               // k_attn3: AttnParams::always_check of the launch
+    int ablation = 0;                        // GYRE_ATTN_ABLATIONS builds (k_attn3, D = 40)
+    double flops = 0, bytes = 0;             // the profiling scope's model
+};
+AttnPlan attn_plan(const AttnParams& p, int variant);
+constexpr int ATTN_PLAN_INTS = 12, ATTN_BWD_PLAN_INTS = 10;     // gyre_debug_attn_plan / gyre_debug_attn_bwd_plan (include/gyre_hip.h)
 int launch_attention(hipStream_t st, const AttnParams& p);
 
 // ---- fused cross-attention block: to_q (+ folded LayerNorm) -> attention over the cached text keys -> to_out + residual (kernels_xattn.hip) ----
@@ -283,6 +310,7 @@ struct AttnBwdParams {
 size_t attn_bwd_stats_bytes(int B, int H, int Nq);
 bool attn_bwd_needs_transposes(int D);     // false: the LDS-tiled kernels (D <= 160) ignore kt / qt / d_ot
 int launch_attention_bwd(hipStream_t st, AttnBwdParams p);
+int attn_bwd_table(int which, int32_t* out, int cap);      // gyre_debug_attn_tables: 1 = LDS-tile rows, 2 = register-staged rows
 
 // ---- ToMe: bipartite soft matching + merge of self-attention K / V tokens (kernels_tome.hip) ---------------------------
 struct TomeParams {

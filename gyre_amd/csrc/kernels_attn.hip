@@ -21,12 +21,14 @@
 //   * head dims 40/80/160 are zero-padded in LDS only (QK^T contraction to a multiple of 32, PV
 //     output to a multiple of 16); global traffic is the unpadded Q/K/V/O.
 //
-// Three kernels, chosen in launch_attention():
+// Three kernels; attn_plan() below holds the whole rule that picks one (and its grid, ring and LDS size), launch_attention() runs it:
 //   k_attn   (v1)  register-staged K / V^T tiles; any head dim up to 512 (the VAE mid block)
 //   k_attn2  (v2)  LDS-DMA ring; plain online softmax, or FOLD (K prescaled: scale in the to_k weights, running max in
 //                  the MFMA C input) for short key sequences (cross-attention) and D = 160
 //   k_attn3  (v3)  FOLD + software pipeline inside the wave (exp of tile t overlaps QK^T of tile t+1); all UNet
 //                  self-attention with D in {16,32,40,64,80}
+// gyre_debug_force_attn_variant overrides the rule per thread: ATTN_VAR_V1 / _V2_PLAIN / _V2_FOLD / _V2_Q64 / _V3 force a family where it
+// has the head dim, _NO_QLOOP / _ALWAYS_CHECK / _AUTO_ALIAS are the automatic rule with one switch each (AttnVariant, kernels.h).
 #include "kernels.h"
 #include <type_traits>
 
@@ -223,6 +225,33 @@ __global__ __launch_bounds__(256) void k_attn(AttnParams p) {
 typedef __attribute__((address_space(3))) void lds_void_a;
 typedef __attribute__((address_space(1))) const void gbl_void_a;
 
+// The LDS-DMA ring of k_attn2 and k_attn3: the kernels index it and attn_plan() sizes the launch's dynamic LDS from these constants
+// and from nowhere else.  PD = tiles in flight ahead of the one being computed.
+constexpr int attn2_pd(int D) { return D <= 80 ? 2 : 1; }
+// k_attn3, D = 80 (a few spills: its loop drains the DMA queue every step anyway): one tile of lookahead, so that TWO workgroups per
+// CU fit instead of the one a deeper ring allowed (the 32x32 level of SD1.x)
+constexpr int attn3_pd(int D) { return D > 64 ? 1 : 2; }
+template <int D, int PD, bool V3> struct AttnRing {
+    static constexpr int DO = (D + 15) / 16;                    // output d fragments
+    static constexpr int KVEC = D / 8;                          // 16-byte granules per K row
+    static constexpr int VR = DO * 16;                          // V^T rows staged (rows >= D come from the zero page)
+    static constexpr int KBYTES = 64 * D * 2;
+    static constexpr int RAW = KBYTES + VR * 128;
+    static constexpr int STAGE = (RAW + 4095) / 4096 * 4096;    // whole number of 4-wave DMA rounds
+    static constexpr int NW = STAGE / 4096;                     // DMA instructions per wave per tile
+    static constexpr int KG = 64 * KVEC, VG = VR * 8;
+    // PD tiles in flight + the one being computed + one spare, so a refill never targets a stage a slower wave may still be reading;
+    // k_attn3 takes one more (LDSX, see its ring discipline) where two workgroups per CU still fit with it
+#ifdef GYRE_ATTN_R4_RING      // reproducer build (tools/attn_race_repro.sh): the round-4 ring of four slots
+    static constexpr bool SPARE = false;
+#else
+    static constexpr bool SPARE = V3 && 2 * (PD + 3) * STAGE <= 160 * 1024;
+#endif
+    static constexpr int NS = PD + (SPARE ? 3 : 2);
+    static constexpr int LDS_BYTES = NS * STAGE;
+    static_assert(KG % 64 == 0, "K granules fill whole wave instructions");
+};
+
 // FOLD (needs AttnParams::k_prescaled): K carries log2(e)/sqrt(D), so the MFMA output is already the exp2 argument
 // up to the row offset - and that offset (the reference maximum of the row) is subtracted by the MFMA itself through its
 // C input.  p = exp2(S') then costs one v_exp per score and nothing else; rows are re-centred in a wave-uniform branch
@@ -233,19 +262,11 @@ typedef __attribute__((address_space(1))) const void gbl_void_a;
 // chain Q load -> tile DMA -> barrier -> 2 tiles -> store (47 us for the 64x64 cross-attention, 84 MB: 1.8 TB/s).
 template <int D, int QI, int PD, bool FOLD, bool QLOOP = false>
 __global__ __launch_bounds__(256, (D <= 80 ? 2 : 1)) void k_attn2(AttnParams p, const bf16_t* zero, int qiter) {
-    constexpr int NS = PD + 2;               // ring depth: PD tiles in flight + the one being computed + one spare,
-                                             // so a refill never targets a stage a slower wave may still be reading
+    using R = AttnRing<D, PD, false>;
+    constexpr int NS = R::NS, STAGE = R::STAGE, NW = R::NW, KBYTES = R::KBYTES, KVEC = R::KVEC, KG = R::KG, VG = R::VG, DO = R::DO;
     constexpr int DP = (D + 31) / 32 * 32;
     constexpr int KS = DP / 32;
-    constexpr int DO = (D + 15) / 16;
-    constexpr int KVEC = D / 8;              // 16-byte granules per K row
-    constexpr int VR = DO * 16;              // V^T rows staged (rows >= D come from the zero page)
-    constexpr int KBYTES = 64 * D * 2;
-    constexpr int RAW = KBYTES + VR * 128;
-    constexpr int STAGE = (RAW + 4095) / 4096 * 4096;   // whole number of 4-wave DMA rounds
-    constexpr int NW = STAGE / 4096;         // DMA instructions per wave per tile
-    constexpr int KG = 64 * KVEC, VG = VR * 8;
-    static_assert(KG % 64 == 0, "K granules fill whole wave instructions");
+    static_assert(NS * STAGE == R::LDS_BYTES && (D <= 80 ? 2 : 1) * R::LDS_BYTES <= 160 * 1024, "the ring is the launch's dynamic LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -587,8 +608,6 @@ __global__ __launch_bounds__(256, (D <= 80 ? 2 : 1)) void k_attn2(AttnParams p, 
 // The redo flag lives in the dynamic LDS region too (word 0 of slot 0, three barriers once per workgroup): a second __shared__
 // object made hipcc put s_waitcnt vmcnt(0) in front of the first V^T read of EVERY step (LDS-DMA alias scopes), which drained the
 // whole DMA lookahead - the reason the checked kernel got slower between rounds 3 and 4.
-__host__ __device__ constexpr int attn3_stage_bytes(int D) { return (64 * D * 2 + ((D + 15) / 16) * 16 * 128 + 4095) / 4096 * 4096; }
-__host__ __device__ constexpr bool attn3_spare_slot(int D, int PD) { return 2 * (PD + 3) * attn3_stage_bytes(D) <= 160 * 1024; }
 struct AttnRtCheck { bool on; };
 template <class T> __device__ __forceinline__ constexpr bool attn_check_on(T) { return T::value; }
 __device__ __forceinline__ bool attn_check_on(AttnRtCheck c) { return c.on; }
@@ -599,27 +618,17 @@ __global__ __launch_bounds__(256, (QI >= 4 ? 1 : 2)) void k_attn3(AttnParams p, 
     // measured: no faster (the matrix core is not the limiter) and a dependent x32 -> x16 chain on one accumulator
     // gave wrong results for D = 80 under this compiler, so the contraction stays padded to 32)
     constexpr int KS = (D + 31) / 32;
-    constexpr int DO = (D + 15) / 16;
-    constexpr int KVEC = D / 8;
-    constexpr int VR = DO * 16;
-    constexpr int KBYTES = 64 * D * 2;
-    constexpr int RAW = KBYTES + VR * 128;
-    constexpr int STAGE = (RAW + 4095) / 4096 * 4096;
-    constexpr int NW = STAGE / 4096;
-#ifdef GYRE_ATTN_R4_RING      // reproducer build (tools/attn_race_repro.sh): the round-4 ring - the refill targets the slot the previous
-                              // step read and nothing waits for that step's fragment reads - under the round-5 code otherwise
-    constexpr bool LDSX = false;
-#else
-    constexpr bool LDSX = attn3_spare_slot(D, PD);      // two workgroups per CU still fit with one more slot
-#endif
-    constexpr int NS = PD + (LDSX ? 3 : 2);
-    constexpr int KG = 64 * KVEC, VG = VR * 8;
+    using R = AttnRing<D, PD, true>;
+    constexpr int NS = R::NS, STAGE = R::STAGE, NW = R::NW, KBYTES = R::KBYTES, KVEC = R::KVEC, KG = R::KG, VG = R::VG, DO = R::DO;
+    // GYRE_ATTN_R4_RING (reproducer build): never a spare slot - the refill targets the slot the previous step read and nothing waits
+    // for that step's fragment reads - under the round-5 code otherwise
+    constexpr bool LDSX = R::SPARE;
+    static_assert(NS * STAGE == R::LDS_BYTES && (QI >= 4 ? 1 : 2) * R::LDS_BYTES <= 160 * 1024, "the ring is the launch's dynamic LDS");
     constexpr bool ONES = (D % 16 != 0);
     constexpr float TAU = GYRE_ATTN_TAU;       // 60 (bf16 storage); 14 with fp16 storage, whose P operand ends at 65504 (common.h)
     // D = 80 does not fit 256 registers without a few spills.  Scratch stores count in vmcnt and may retire before
     // older loads, so a counted wait is not safe there: drain completely instead (one tile less of DMA lookahead).
     constexpr bool DRAIN = D > 64;
-    static_assert(KG % 64 == 0, "K granules fill whole wave instructions");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1049,160 +1058,155 @@ extern "C" long gyre_debug_attn_redo_count() {
     if (hipMemcpy(&v, c, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return (long)v;
 }
-static thread_local int g_attn_variant = 0;  // tests / tuning: 0 auto, 1 = v1, 2 = v2 plain, 3 = v2 folded, 4 = v2 QI=4 (D <= 32), 5 = v3,
-                                             // 6 = auto without the several-query-blocks-per-workgroup form of short key sequences
+static thread_local int g_attn_variant = ATTN_VAR_AUTO;      // tests / tuning: AttnVariant (kernels.h), read by attn_thread_variant() alone
 extern "C" int gyre_debug_force_attn_variant(int v) { int o = g_attn_variant; g_attn_variant = v; return o; }
+static int attn_thread_variant() { return g_attn_variant; }
 
-template <int D, int QI, bool FOLD = false>
-static int launch_attn2_t(hipStream_t st, const AttnParams& p) {
-    constexpr int DO = (D + 15) / 16;
-    constexpr int RAW = 64 * D * 2 + DO * 16 * 128;
-    constexpr int STAGE = (RAW + 4095) / 4096 * 4096;
-    constexpr int PD = D <= 80 ? 2 : 1;      // tiles in flight ahead of the one being computed
-    const size_t lds = (size_t)(PD + 2) * STAGE;
-    const bf16_t* zero = attn_zero_page();
-    if (!zero) GYRE_FAIL(-5, "attention: cannot allocate the zero page");
-    const int nblk = (p.Nq + 64 * QI - 1) / (64 * QI);
-    GyreProfScope prof_(KC_ATTN, st, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * D,
-                        2.0 * p.B * p.H * D * (2.0 * p.Nq + 2.0 * p.Nk));
-    // short key sequence with many query blocks (cross-attention against the text context): K / V^T staged once per
-    // workgroup, several query blocks per workgroup - as many as still leave ~2 workgroups per CU
-    if constexpr (D == 40 || D == 64 || D == 80 || D == 160) {
-        int qiter = (int)((long)nblk * p.B * p.H / 512);
-        if (qiter > 8) qiter = 8;
-        if (qiter > nblk) qiter = nblk;
-        if ((p.Nk + 63) / 64 <= PD + 2 && qiter >= 2 && ((g_attn_variant & 255) == 0 || (g_attn_variant & 255) == 7 || (g_attn_variant & 255) == 8)) {
-            auto kern = k_attn2<D, QI, PD, FOLD, true>;
-            static std::atomic<unsigned long long> attr_done{0};
-            if (gyre_lds_attr_needed(attr_done))
-                (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kern, dim3((nblk + qiter - 1) / qiter, p.B * p.H), dim3(256), lds, st, p, zero, qiter);
-            GYRE_LAUNCH_CHECK();
-            return 0;
-        }
+// ---- the launch table: the only place that names kernel instantiations ---------------------------------------------------------
+// (not built, measured: k_attn2 with 64 query rows per wave spills from head dim 40 up, which a counted-vmcnt kernel must not, and is
+//  slower than 32 rows at every SD shape; the folded k_attn2 for D = 80 spills 7 registers at 2 waves/SIMD and is no faster; k_attn3
+//  with 48 rows per wave (QI = 3, D = 40): 232 B/lane of spills; with 64 rows at ONE wave per SIMD (QI = 4, 412 registers): 625 vs
+//  619 us at 64x64, 10-40 % slower on the smaller shapes)
+struct AttnRow {
+    int family, D, QI; bool qloop;
+    int PD, slots, stage_bytes, lds_bytes;
+    const void* kern;
+};
+constexpr int attn1_lds_bytes(int D) { return 64 * ((D + 31) / 32 * 32 * 2 + 16) + (D + 15) / 16 * 16 * (64 * 2 + 16); }     // k_attn: [64][KROW] + [DO * 16][VROW]
+#define ATTN_V1(D, QI) {ATTN_FAM_V1, D, QI, false, 0, 0, 0, attn1_lds_bytes(D), (const void*)k_attn<D, QI>}
+#define ATTN_V2_(D, QI, FOLD, QLOOP) {FOLD ? ATTN_FAM_V2_FOLD : ATTN_FAM_V2_PLAIN, D, QI, QLOOP, attn2_pd(D), AttnRing<D, attn2_pd(D), false>::NS, \
+        AttnRing<D, attn2_pd(D), false>::STAGE, AttnRing<D, attn2_pd(D), false>::LDS_BYTES, (const void*)k_attn2<D, QI, attn2_pd(D), FOLD, QLOOP>}
+#define ATTN_V2(D, QI, FOLD) ATTN_V2_(D, QI, FOLD, false)
+#define ATTN_V2Q(D, QI, FOLD) ATTN_V2_(D, QI, FOLD, false), ATTN_V2_(D, QI, FOLD, true)      // + the several-query-blocks form
+#define ATTN_V3(D) {ATTN_FAM_V3, D, 2, false, attn3_pd(D), AttnRing<D, attn3_pd(D), true>::NS, AttnRing<D, attn3_pd(D), true>::STAGE, \
+        AttnRing<D, attn3_pd(D), true>::LDS_BYTES, (const void*)k_attn3<D, attn3_pd(D), 2>}
+static const AttnRow g_attn_rows[] = {
+    ATTN_V3(16), ATTN_V3(32), ATTN_V3(40), ATTN_V3(64), ATTN_V3(80),
+    ATTN_V2(16, 2, true), ATTN_V2(32, 2, true), ATTN_V2Q(40, 2, true), ATTN_V2Q(64, 2, true), ATTN_V2Q(160, 2, true),
+    ATTN_V2(16, 2, false), ATTN_V2(32, 2, false), ATTN_V2Q(40, 2, false), ATTN_V2Q(64, 2, false), ATTN_V2Q(80, 2, false),
+    ATTN_V2(128, 2, false), ATTN_V2Q(160, 2, false), ATTN_V2(16, 4, false), ATTN_V2(32, 4, false),
+    ATTN_V1(8, 2), ATTN_V1(16, 2), ATTN_V1(32, 2), ATTN_V1(40, 2), ATTN_V1(64, 2), ATTN_V1(80, 2), ATTN_V1(128, 2), ATTN_V1(160, 2),
+    ATTN_V1(512, 1),
+};
+#undef ATTN_V1
+#undef ATTN_V2_
+#undef ATTN_V2
+#undef ATTN_V2Q
+#undef ATTN_V3
+constexpr int ATTN_NROWS = sizeof(g_attn_rows) / sizeof(g_attn_rows[0]);
+// QI = 0: the row's own (every family but the plain k_attn2 has one QI per head dim)
+static int attn_find_row(int family, int D, int QI, bool qloop) {
+    for (int i = 0; i < ATTN_NROWS; ++i) {
+        const AttnRow& r = g_attn_rows[i];
+        if (r.family == family && r.D == D && (QI == 0 || r.QI == QI) && r.qloop == qloop) return i;
     }
-    auto kern = k_attn2<D, QI, PD, FOLD>;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (gyre_lds_attr_needed(attr_done))
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(nblk, p.B * p.H), dim3(256), lds, st, p, zero, 1);
-    GYRE_LAUNCH_CHECK();
-    return 0;
+    return -1;
 }
 
-template <int D, int QI = 2>
-static int launch_attn3_t(hipStream_t st, const AttnParams& p) {
-    constexpr int DO = (D + 15) / 16;
-    constexpr int RAW = 64 * D * 2 + DO * 16 * 128;
-    constexpr int STAGE = (RAW + 4095) / 4096 * 4096;
-    // D = 80 (24 KB per stage, a few spills: its loop drains the DMA queue every step anyway): one tile of lookahead and a 3-slot
-    // ring = 72 KB, TWO workgroups per CU instead of the one its 4 x 24 KB ring allowed (the 32x32 level of SD1.x)
-    constexpr int PD = D > 64 ? 1 : 2;
-    static_assert(STAGE == attn3_stage_bytes(D), "ring stage size");
-#ifdef GYRE_ATTN_R4_RING
-    const size_t lds = (size_t)(PD + 2) * STAGE;
-#else
-    const size_t lds = (size_t)(PD + (attn3_spare_slot(D, PD) ? 3 : 2)) * STAGE;
-#endif
-    const bf16_t* zero = attn_zero_page();
-    if (!zero) GYRE_FAIL(-5, "attention: cannot allocate the zero page");
-    auto kern = k_attn3<D, PD, QI>;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (gyre_lds_attr_needed(attr_done))
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    dim3 grid((unsigned)(((p.Nq + 64 * QI - 1) / (64 * QI)) * p.B * p.H));
-    GyreProfScope prof_(KC_ATTN, st, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * D,
-                        2.0 * p.B * p.H * D * (2.0 * p.Nq + 2.0 * p.Nk));
-    AttnParams q = p;
-    // optimistic first pass by default (variant 7 = always the per-tile check; 8 = a synonym of the default, kept for the tools)
-    q.always_check = (g_attn_variant & 255) == 7 ? 1 : 0;
-    q.redo_counter = (unsigned*)((char*)zero + 512);        // the device's counter sits behind its zero / ones page
+AttnPlan attn_plan(const AttnParams& p, int variant) {
+    AttnPlan pl;
+    auto reject = [&](int code, std::string msg) { pl.status = code; pl.error = std::move(msg); return pl; };
+    if (p.D % 8) return reject(-1, "attention: head dim must be a multiple of 8");
+    if (p.ldq % 8 || p.ldk % 8 || p.ldvt % 8 || p.ldo % 4) return reject(-1, "attention: strides must be multiples of 8");
+    if (p.ldvt < (p.Nk + 7) / 8 * 8) return reject(-1, "attention: ldvt must cover Nk rounded up to 8");
+    if (p.Nk < 1 || p.Nq < 1) return reject(-1, "attention: empty sequence");
+    const int raw = variant & 255;
+    const bool auto_qloop = raw == ATTN_VAR_AUTO || raw == ATTN_VAR_ALWAYS_CHECK || raw == ATTN_VAR_AUTO_ALIAS;
+    const int var = (auto_qloop || raw == ATTN_VAR_NO_QLOOP) ? ATTN_VAR_AUTO : raw;
+    // k_attn3 from 256 keys: with only a couple of key tiles (cross-attention, Nk = 77) its longer prologue costs more than the
+    // overlap wins (measured 47.8 vs 41.1 us), so short key sequences stay on k_attn2
+    int row = -1;
+    if (p.k_prescaled && ((var == ATTN_VAR_AUTO && p.Nk >= 256) || var == ATTN_VAR_V3)) row = attn_find_row(ATTN_FAM_V3, p.D, 0, false);
+    if (row < 0 && p.k_prescaled && var != ATTN_VAR_V1 && var != ATTN_VAR_V2_PLAIN && var != ATTN_VAR_V2_Q64)
+        row = attn_find_row(ATTN_FAM_V2_FOLD, p.D, 0, false);
+    if (row < 0 && var != ATTN_VAR_V1) {
+        if (var == ATTN_VAR_V2_Q64) row = attn_find_row(ATTN_FAM_V2_PLAIN, p.D, 4, false);
+        if (row < 0) row = attn_find_row(ATTN_FAM_V2_PLAIN, p.D, 2, false);
+    }
+    if (row < 0) row = attn_find_row(ATTN_FAM_V1, p.D, 0, false);
+    if (row < 0) return reject(-6, "attention: unsupported head dim " + std::to_string(p.D));
+
+    const AttnRow& r = g_attn_rows[row];
+    const int nblk = (p.Nq + 64 * r.QI - 1) / (64 * r.QI), BH = p.B * p.H;
+    pl.grid = r.family == ATTN_FAM_V3 ? dim3((unsigned)(nblk * BH)) : dim3(nblk, BH);
+    if (r.family == ATTN_FAM_V2_PLAIN || r.family == ATTN_FAM_V2_FOLD) {
+        // short key sequence with many query blocks (cross-attention against the text context): K / V^T staged once per workgroup,
+        // several query blocks per workgroup - as many as still leave ~2 workgroups per CU
+        const int qrow = attn_find_row(r.family, r.D, r.QI, true);
+        int qiter = (int)((long)nblk * BH / 512);
+        if (qiter > 8) qiter = 8;
+        if (qiter > nblk) qiter = nblk;
+        if (qrow >= 0 && auto_qloop && (p.Nk + 63) / 64 <= r.slots && qiter >= 2) {
+            row = qrow;
+            pl.qloop = true; pl.qiter = qiter;
+            pl.grid = dim3((nblk + qiter - 1) / qiter, BH);
+        }
+    }
+    pl.row = row;
+    pl.family = r.family; pl.D = r.D; pl.QI = r.QI;
+    pl.PD = r.PD; pl.slots = r.slots; pl.stage_bytes = r.stage_bytes; pl.lds_bytes = r.lds_bytes;
+    pl.always_check = r.family == ATTN_FAM_V3 && raw == ATTN_VAR_ALWAYS_CHECK;
+    pl.ablation = variant >> 8;
+    pl.flops = 4.0 * p.B * p.H * (double)p.Nq * p.Nk * p.D;
+    pl.bytes = 2.0 * p.B * p.H * p.D * (2.0 * p.Nq + 2.0 * p.Nk);
+    return pl;
+}
+
+// hipLaunchKernel reads as many arguments as the kernel declares: k_attn (p), k_attn3 (p, zero), k_attn2 (p, zero, qiter)
+static int attn_launch(hipStream_t st, const AttnPlan& pl, AttnParams p, const bf16_t* zero) {
+    static std::atomic<unsigned long long> attr_done[ATTN_NROWS];
+    const void* kern = g_attn_rows[pl.row].kern;
+    if (gyre_lds_attr_needed(attr_done[pl.row]))
+        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
 #ifdef GYRE_ATTN_ABLATIONS
-    if constexpr (D == 40) {
-        const int abl = g_attn_variant >> 8;              // gyre_debug_force_attn_variant(abl << 8)
-#define GYRE_ATTN_ABL(A_) if (abl == A_) { hipLaunchKernelGGL((k_attn3<D, PD, QI, A_>), grid, dim3(256), lds, st, q, zero); GYRE_LAUNCH_CHECK(); return 0; }
+    if (pl.family == ATTN_FAM_V3 && pl.D == 40) {         // gyre_debug_force_attn_variant(abl << 8)
+#define GYRE_ATTN_ABL(A_) if (pl.ablation == A_) kern = (const void*)k_attn3<40, attn3_pd(40), 2, A_>;
         GYRE_ATTN_ABL(1) GYRE_ATTN_ABL(2) GYRE_ATTN_ABL(4) GYRE_ATTN_ABL(6) GYRE_ATTN_ABL(8) GYRE_ATTN_ABL(16) GYRE_ATTN_ABL(32) GYRE_ATTN_ABL(33)
         GYRE_ATTN_ABL(9) GYRE_ATTN_ABL(24) GYRE_ATTN_ABL(57) GYRE_ATTN_ABL(63) GYRE_ATTN_ABL(22)
 #undef GYRE_ATTN_ABL
     }
 #endif
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q, zero);
-    GYRE_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int D, int QI>
-static int launch_attn_t(hipStream_t st, const AttnParams& p) {
-    constexpr int DP = (D + 31) / 32 * 32;
-    constexpr int DO = (D + 15) / 16;
-    const size_t lds = (size_t)64 * (DP * 2 + 16) + (size_t)DO * 16 * (64 * 2 + 16);
-    auto kern = k_attn<D, QI>;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (gyre_lds_attr_needed(attr_done))
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    dim3 grid((p.Nq + 64 * QI - 1) / (64 * QI), p.B * p.H);
-    GyreProfScope prof_(KC_ATTN, st, 4.0 * p.B * p.H * (double)p.Nq * p.Nk * D,
-                        2.0 * p.B * p.H * D * (2.0 * p.Nq + 2.0 * p.Nk));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
+    int qiter = pl.qiter;
+    void* args[] = {&p, &zero, &qiter};
+    GyreProfScope prof_(KC_ATTN, st, pl.flops, pl.bytes);
+    (void)hipLaunchKernel(kern, pl.grid, dim3(256), args, (size_t)pl.lds_bytes, st);
     GYRE_LAUNCH_CHECK();
     return 0;
 }
 
 int launch_attention(hipStream_t st, const AttnParams& p) {
-    if (p.D % 8) GYRE_FAIL(-1, "attention: head dim must be a multiple of 8");
-    if (p.ldq % 8 || p.ldk % 8 || p.ldvt % 8 || p.ldo % 4) GYRE_FAIL(-1, "attention: strides must be multiples of 8");
-    if (p.ldvt < (p.Nk + 7) / 8 * 8) GYRE_FAIL(-1, "attention: ldvt must cover Nk rounded up to 8");
-    if (p.Nk < 1 || p.Nq < 1) GYRE_FAIL(-1, "attention: empty sequence");
-    const int var = ((g_attn_variant & 255) == 6 || (g_attn_variant & 255) == 7 || (g_attn_variant & 255) == 8) ? 0 : (g_attn_variant & 255);
-    // software-pipelined folded kernel; with only a couple of key tiles (cross-attention, Nk = 77) its longer prologue
-    // costs more than the overlap wins (measured 47.8 vs 41.1 us), so short key sequences stay on the v2 form
-    // (48 query rows per wave, QI = 3, was tried for D = 40: 232 B/lane of spills at 2 waves/SIMD - not built)
-    // (64 rows per wave at ONE wave per SIMD, QI = 4 with 412 registers: 625 vs 619 us at 64x64, 10-40 % slower on
-    //  the smaller shapes - not built)
-    if (p.k_prescaled && ((var == 0 && p.Nk >= 256) || var == 5)) {
-        switch (p.D) {
-            case 16: return launch_attn3_t<16>(st, p);
-            case 32: return launch_attn3_t<32>(st, p);
-            case 40: return launch_attn3_t<40>(st, p);
-            case 64: return launch_attn3_t<64>(st, p);
-            case 80: return launch_attn3_t<80>(st, p);
-            default: break;
-        }
+    const AttnPlan pl = attn_plan(p, attn_thread_variant());
+    if (pl.status) GYRE_FAIL(pl.status, pl.error);
+    if (pl.family == ATTN_FAM_V1) return attn_launch(st, pl, p, nullptr);
+    const bf16_t* zero = attn_zero_page();
+    if (!zero) GYRE_FAIL(-5, "attention: cannot allocate the zero page");
+    AttnParams q = p;
+    if (pl.family == ATTN_FAM_V3) {
+        q.always_check = pl.always_check ? 1 : 0;
+        q.redo_counter = (unsigned*)((char*)zero + 512);        // the device's counter sits behind its zero / ones page
     }
-    if (p.k_prescaled && var != 1 && var != 2 && var != 4) {
-        switch (p.D) {
-            case 16: return launch_attn2_t<16, 2, true>(st, p);
-            case 32: return launch_attn2_t<32, 2, true>(st, p);
-            case 40: return launch_attn2_t<40, 2, true>(st, p);
-            case 64: return launch_attn2_t<64, 2, true>(st, p);
-            case 160: return launch_attn2_t<160, 2, true>(st, p);
-            default: break;   // D = 80: the folded form spills 7 registers at 2 waves/SIMD and is no faster (measured)
-        }
+    return attn_launch(st, pl, q, zero);
+}
+
+// ---- what a launch would do, for the tests (no device is touched) ---------------------------------------------------------------
+extern "C" int gyre_debug_attn_plan(int B, int H, int Nq, int Nk, int D, int k_prescaled, int ldq, int ldk, int ldvt, int ldo, int32_t* out) {
+    AttnParams p{};
+    p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D; p.k_prescaled = k_prescaled;
+    p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo;
+    const AttnPlan pl = attn_plan(p, attn_thread_variant());
+    if (pl.status) GYRE_FAIL(pl.status, pl.error);
+    const int32_t v[ATTN_PLAN_INTS] = {pl.family, pl.D, pl.QI, pl.PD, pl.slots, pl.lds_bytes, (int32_t)pl.grid.x, (int32_t)pl.grid.y,
+                                            (int32_t)pl.grid.z, pl.qiter, pl.always_check, pl.qloop};
+    for (int i = 0; i < ATTN_PLAN_INTS; ++i) out[i] = v[i];
+    return 0;
+}
+// which = 0: the rows of the launch table above as (family, D, QI, qloop); 1 / 2: launch_attention_bwd's LDS-tile / register-staged
+// rows as (upper head-dim bound).  Returns the number of rows.
+extern "C" int gyre_debug_attn_tables(int which, int32_t* out, int cap) {
+    if (which) return attn_bwd_table(which, out, cap);
+    for (int i = 0; i < ATTN_NROWS && 4 * i + 3 < cap; ++i) {
+        const AttnRow& r = g_attn_rows[i];
+        out[4 * i] = r.family; out[4 * i + 1] = r.D; out[4 * i + 2] = r.QI; out[4 * i + 3] = r.qloop;
     }
-    if (var != 1) {
-        const bool q4 = var == 4;  // 64 query rows per wave: measured slower than 32 at every SD shape (register pressure)
-        switch (p.D) {
-            case 16: return q4 ? launch_attn2_t<16, 4>(st, p) : launch_attn2_t<16, 2>(st, p);
-            case 32: return q4 ? launch_attn2_t<32, 4>(st, p) : launch_attn2_t<32, 2>(st, p);
-            // (64 query rows per wave spill from head dim 40 up, which a counted-vmcnt kernel must not: not built)
-            case 40: return launch_attn2_t<40, 2>(st, p);
-            case 64: return launch_attn2_t<64, 2>(st, p);
-            case 80: return launch_attn2_t<80, 2>(st, p);
-            case 128: return launch_attn2_t<128, 2>(st, p);
-            case 160: return launch_attn2_t<160, 2>(st, p);
-            default: break;
-        }
-    }
-    switch (p.D) {
-        case 8: return launch_attn_t<8, 2>(st, p);
-        case 16: return launch_attn_t<16, 2>(st, p);
-        case 32: return launch_attn_t<32, 2>(st, p);
-        case 40: return launch_attn_t<40, 2>(st, p);
-        case 64: return launch_attn_t<64, 2>(st, p);
-        case 80: return launch_attn_t<80, 2>(st, p);
-        case 128: return launch_attn_t<128, 2>(st, p);
-        case 160: return launch_attn_t<160, 2>(st, p);
-        case 512: return launch_attn_t<512, 1>(st, p);
-        default: GYRE_FAIL(-6, "attention: unsupported head dim " + std::to_string(p.D));
-    }
+    return ATTN_NROWS;
 }

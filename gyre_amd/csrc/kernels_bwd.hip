@@ -1449,12 +1449,72 @@ size_t attn_bwd_stats_bytes(int B, int H, int Nq) {
     const size_t npad = (size_t)(Nq + 63) / 64 * 64;     // 64-row tiles of the LDS-DMA kernels
     return 2 * (((size_t)B * H * npad * 4 + 255) & ~(size_t)255);
 }
+// ---- which kernels a launch_attention_bwd call runs: one row per kernel set, head dims up to `bound` --------------------------------
+// NDB = 32-wide head-dim blocks a workgroup holds (the register-staged kernels walk ceil(D / 32) / NDB d-chunks), DS: see the kernels.
+struct AttnBwdRow { int bound, ndb; const void* dq; const void* dkv; };
+#define ABW_ROW(BOUND, DQ, DKV, NDB, ...) {BOUND, NDB, (const void*)DQ<NDB, __VA_ARGS__>, (const void*)DKV<NDB, __VA_ARGS__>}
+// LDS-tile kernels (D <= 160).  32-row tiles: 64-row tiles (RT = 2) were measured slower (2.71 vs 2.14 ms at N = 4096, D = 40: fewer
+// resident workgroups outweigh the halved barrier count).  80: five k-steps (the 32 x 32 level)
+static const AttnBwdRow g_abw_lds_rows[] = {
+    ABW_ROW(48, k_attn_bwd_dq_lds, k_attn_bwd_dkv_lds, 2, 3, 1), ABW_ROW(64, k_attn_bwd_dq_lds, k_attn_bwd_dkv_lds, 2, 4, 1),
+    ABW_ROW(80, k_attn_bwd_dq_lds, k_attn_bwd_dkv_lds, 3, 5, 1), ABW_ROW(96, k_attn_bwd_dq_lds, k_attn_bwd_dkv_lds, 3, 6, 1),
+    ABW_ROW(160, k_attn_bwd_dq_lds, k_attn_bwd_dkv_lds, 5, 10, 1),
+};
+// register-staged kernels.  launch_attention_bwd sends them D > 160 only, so the last row is the one that runs; the others are the
+// kernels every head dim had before the LDS-tile ones and stay built.
+static const AttnBwdRow g_abw_reg_rows[] = {
+    ABW_ROW(48, k_attn_bwd_dq, k_attn_bwd_dkv, 2, 3), ABW_ROW(64, k_attn_bwd_dq, k_attn_bwd_dkv, 2, 4), ABW_ROW(96, k_attn_bwd_dq, k_attn_bwd_dkv, 3, 6),
+    ABW_ROW(160, k_attn_bwd_dq, k_attn_bwd_dkv, 5, 10), ABW_ROW(1 << 30, k_attn_bwd_dq, k_attn_bwd_dkv, 4, 0),
+};
+#undef ABW_ROW
+constexpr int ABW_NLDS = sizeof(g_abw_lds_rows) / sizeof(AttnBwdRow), ABW_NREG = sizeof(g_abw_reg_rows) / sizeof(AttnBwdRow);
+enum { ATTN_BWD_DMA = 0, ATTN_BWD_LDS = 1, ATTN_BWD_REG = 2 };
+struct AttnBwdPlan { int family, row, bound, dchunks; size_t lds_bytes; dim3 gq, gk; };
+static bool abw_no_dma() {
+    static const bool no_dma = getenv("GYRE_ABW_NO_DMA") != nullptr;      // tuning / A-B: the LDS-tile kernels for D = 40 too
+    return no_dma;
+}
+static AttnBwdPlan attn_bwd_plan(int B, int H, int Nq, int Nk, int D, bool no_dma) {
+    AttnBwdPlan pl{};
+    pl.dchunks = 1;
+    if (D == 40 && !no_dma) {
+        pl.family = ATTN_BWD_DMA; pl.row = 0; pl.bound = 40;
+        pl.lds_bytes = (size_t)Abw2<40>::NS * Abw2<40>::STAGE;
+    } else {
+        const bool lds = !attn_bwd_needs_transposes(D);
+        const AttnBwdRow* rows = lds ? g_abw_lds_rows : g_abw_reg_rows;
+        while (D > rows[pl.row].bound) ++pl.row;         // (the last bound of either table covers every D that reaches it)
+        pl.family = lds ? ATTN_BWD_LDS : ATTN_BWD_REG; pl.bound = rows[pl.row].bound;
+        if (lds) pl.lds_bytes = 2 * attn_bwd_stage_bytes(D, 1);
+        else pl.dchunks = ((D + 31) / 32 + rows[pl.row].ndb - 1) / rows[pl.row].ndb;
+    }
+    pl.gq = dim3((unsigned)((Nq + 127) / 128 * pl.dchunks), H, B);
+    pl.gk = dim3((unsigned)((Nk + 127) / 128 * pl.dchunks), H, B);
+    return pl;
+}
+int attn_bwd_table(int which, int32_t* out, int cap) {
+    const AttnBwdRow* rows = which == 1 ? g_abw_lds_rows : g_abw_reg_rows;
+    const int n = which == 1 ? ABW_NLDS : ABW_NREG;
+    for (int i = 0; i < n && i < cap; ++i) out[i] = rows[i].bound;
+    return n;
+}
+// what launch_attention_bwd would run (no device is touched): family, the row's bound, dchunks, LDS bytes, dQ grid, dK / dV grid
+extern "C" int gyre_debug_attn_bwd_plan(int B, int H, int Nq, int Nk, int D, int with_dk, int32_t* out) {
+    if (D % 8) GYRE_FAIL(-1, "attention_bwd: head dim and row strides must be multiples of 8 elements");
+    if (B < 1 || H < 1 || Nq < 1 || Nk < 1) GYRE_FAIL(-1, "attention_bwd: empty problem");
+    const AttnBwdPlan pl = attn_bwd_plan(B, H, Nq, Nk, D, abw_no_dma());
+    const dim3 gk = with_dk ? pl.gk : dim3(0, 0, 0);
+    const int32_t v[ATTN_BWD_PLAN_INTS] = {pl.family, pl.bound, pl.dchunks, (int32_t)pl.lds_bytes, (int32_t)pl.gq.x, (int32_t)pl.gq.y, (int32_t)pl.gq.z,
+                                           (int32_t)gk.x, (int32_t)gk.y, (int32_t)gk.z};
+    for (int i = 0; i < ATTN_BWD_PLAN_INTS; ++i) out[i] = v[i];
+    return 0;
+}
+
 int launch_attention_bwd(hipStream_t st, AttnBwdParams p) {
     if (p.D % 8 || p.ldq % 8 || p.ldk % 8 || p.ldv % 8 || p.lddo % 8 || p.ldo % 8 || p.lddq % 4 || p.ldkt % 4 || p.ldqt % 4)
         GYRE_FAIL(-1, "attention_bwd: head dim and row strides must be multiples of 8 elements");
     if (p.B < 1 || p.H < 1 || p.Nq < 1 || p.Nk < 1) GYRE_FAIL(-1, "attention_bwd: empty problem");
-    const bool lds_path = !attn_bwd_needs_transposes(p.D);
-    if (!lds_path && (!p.kt || p.ldkt < (p.Nk + 31) / 32 * 32 || (p.dk && (!p.qt || !p.d_ot || p.ldqt < (p.Nq + 31) / 32 * 32))))
+    if (attn_bwd_needs_transposes(p.D) && (!p.kt || p.ldkt < (p.Nk + 31) / 32 * 32 || (p.dk && (!p.qt || !p.d_ot || p.ldqt < (p.Nq + 31) / 32 * 32))))
         GYRE_FAIL(-1, "attention_bwd: transposed operands need token strides padded to a multiple of 32");
     p.NqPad = (p.Nq + 63) / 64 * 64;
     const size_t half = ((size_t)p.B * p.H * p.NqPad * 4 + 255) & ~(size_t)255;
@@ -1470,10 +1530,10 @@ int launch_attention_bwd(hipStream_t st, AttnBwdParams p) {
     const size_t nd = (size_t)p.B * p.Nq * p.H;
     hipLaunchKernelGGL(k_attn_bwd_delta, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, p);
     GYRE_LAUNCH_CHECK();
-    static const bool no_dma = getenv("GYRE_ABW_NO_DMA") != nullptr;      // tuning / A-B: the register-staged kernels for D = 40 too
-    if (p.D == 40 && !no_dma) {
-        const size_t lds = (size_t)Abw2<40>::NS * Abw2<40>::STAGE;
-        const dim3 gq((unsigned)((p.Nq + 127) / 128), p.H, p.B), gk((unsigned)((p.Nk + 127) / 128), p.H, p.B);
+    const AttnBwdPlan pl = attn_bwd_plan(p.B, p.H, p.Nq, p.Nk, p.D, abw_no_dma());
+    if (pl.family == ATTN_BWD_DMA) {
+        const size_t lds = pl.lds_bytes;
+        const dim3 gq = pl.gq, gk = pl.gk;
         hipLaunchKernelGGL((k_attn_bwd_dq_dma<40>), gq, dim3(256), lds, st, p);
         GYRE_LAUNCH_CHECK();
         if (!p.dk) return 0;
@@ -1498,60 +1558,17 @@ int launch_attention_bwd(hipStream_t st, AttnBwdParams p) {
         GYRE_LAUNCH_CHECK();
         return 0;
     }
-    if (lds_path) {
-        const int sel = p.D <= 48 ? 0 : (p.D <= 64 ? 1 : (p.D <= 80 ? 4 : (p.D <= 96 ? 2 : 3)));      // 4: D = 80 with five k-steps (the 32 x 32 level)
-        // 32-row LDS tiles: 64-row tiles (RT = 2) were measured slower (2.71 vs 2.14 ms at N = 4096, D = 40: fewer resident
-        // workgroups outweigh the halved barrier count)
-        const size_t lds = 2 * attn_bwd_stage_bytes(p.D, 1);
-        const dim3 gq((unsigned)((p.Nq + 127) / 128), p.H, p.B), gk((unsigned)((p.Nk + 127) / 128), p.H, p.B);
-#define GYRE_ABW_GO(KERN, GRID)                                                                                   \
-        do {                                                                                                          \
-            auto kern = KERN;                                                                                         \
-            static std::atomic<unsigned long long> attr_done{0};                                                      \
-            if (gyre_lds_attr_needed(attr_done))                                                                      \
-                (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   \
-            hipLaunchKernelGGL(kern, GRID, dim3(256), lds, st, p);                                                    \
-            GYRE_LAUNCH_CHECK();                                                                                      \
-        } while (0)
-        switch (sel) {
-            case 0: GYRE_ABW_GO((k_attn_bwd_dq_lds<2, 3, 1>), gq); break;
-            case 1: GYRE_ABW_GO((k_attn_bwd_dq_lds<2, 4, 1>), gq); break;
-            case 2: GYRE_ABW_GO((k_attn_bwd_dq_lds<3, 6, 1>), gq); break;
-            case 4: GYRE_ABW_GO((k_attn_bwd_dq_lds<3, 5, 1>), gq); break;
-            default: GYRE_ABW_GO((k_attn_bwd_dq_lds<5, 10, 1>), gq); break;
-        }
-        if (!p.dk) return 0;
-        switch (sel) {
-            case 0: GYRE_ABW_GO((k_attn_bwd_dkv_lds<2, 3, 1>), gk); break;
-            case 1: GYRE_ABW_GO((k_attn_bwd_dkv_lds<2, 4, 1>), gk); break;
-            case 2: GYRE_ABW_GO((k_attn_bwd_dkv_lds<3, 6, 1>), gk); break;
-            case 4: GYRE_ABW_GO((k_attn_bwd_dkv_lds<3, 5, 1>), gk); break;
-            default: GYRE_ABW_GO((k_attn_bwd_dkv_lds<5, 10, 1>), gk); break;
-        }
-#undef GYRE_ABW_GO
-        return 0;
+    // hipLaunchKernel reads as many arguments as the kernel declares: the LDS-tile kernels (p), the register-staged ones (p, dchunks)
+    static std::atomic<unsigned long long> attr_done[ABW_NLDS][2];
+    const AttnBwdRow& r = (pl.family == ATTN_BWD_LDS ? g_abw_lds_rows : g_abw_reg_rows)[pl.row];
+    int dchunks = pl.dchunks;
+    void* args[] = {&p, &dchunks};
+    const void* kerns[2] = {r.dq, r.dkv};
+    for (int i = 0; i < (p.dk ? 2 : 1); ++i) {
+        if (pl.family == ATTN_BWD_LDS && gyre_lds_attr_needed(attr_done[pl.row][i]))
+            (void)hipFuncSetAttribute(kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipLaunchKernel(kerns[i], i ? pl.gk : pl.gq, dim3(256), args, pl.lds_bytes, st);
+        GYRE_LAUNCH_CHECK();
     }
-    const int ndb_total = (p.D + 31) / 32;
-    const int sel = p.D <= 48 ? 0 : (p.D <= 64 ? 1 : (p.D <= 96 ? 2 : (p.D <= 160 ? 3 : 4)));
-    const int ndb = sel <= 1 ? 2 : (sel == 2 ? 3 : (sel == 3 ? 5 : 4));
-    const int dchunks = (ndb_total + ndb - 1) / ndb;
-    const dim3 gq((unsigned)((p.Nq + 127) / 128 * dchunks), p.H, p.B), gk((unsigned)((p.Nk + 127) / 128 * dchunks), p.H, p.B);
-    switch (sel) {
-        case 0: hipLaunchKernelGGL((k_attn_bwd_dq<2, 3>), gq, dim3(256), 0, st, p, dchunks); break;
-        case 1: hipLaunchKernelGGL((k_attn_bwd_dq<2, 4>), gq, dim3(256), 0, st, p, dchunks); break;
-        case 2: hipLaunchKernelGGL((k_attn_bwd_dq<3, 6>), gq, dim3(256), 0, st, p, dchunks); break;
-        case 3: hipLaunchKernelGGL((k_attn_bwd_dq<5, 10>), gq, dim3(256), 0, st, p, dchunks); break;
-        default: hipLaunchKernelGGL((k_attn_bwd_dq<4, 0>), gq, dim3(256), 0, st, p, dchunks); break;
-    }
-    GYRE_LAUNCH_CHECK();
-    if (!p.dk) return 0;
-    switch (sel) {
-        case 0: hipLaunchKernelGGL((k_attn_bwd_dkv<2, 3>), gk, dim3(256), 0, st, p, dchunks); break;
-        case 1: hipLaunchKernelGGL((k_attn_bwd_dkv<2, 4>), gk, dim3(256), 0, st, p, dchunks); break;
-        case 2: hipLaunchKernelGGL((k_attn_bwd_dkv<3, 6>), gk, dim3(256), 0, st, p, dchunks); break;
-        case 3: hipLaunchKernelGGL((k_attn_bwd_dkv<5, 10>), gk, dim3(256), 0, st, p, dchunks); break;
-        default: hipLaunchKernelGGL((k_attn_bwd_dkv<4, 0>), gk, dim3(256), 0, st, p, dchunks); break;
-    }
-    GYRE_LAUNCH_CHECK();
     return 0;
 }

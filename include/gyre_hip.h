@@ -289,6 +289,17 @@ int gyre_debug_force_attn_variant(int v);
  * this process (always counted since round 6: the increment sits on the redo path only; one blocking 4-byte read-back per call;
  * -1: no device / allocation failure).  bench.py reports the count of its timed region as `attn_redo_count`. */
 long gyre_debug_attn_redo_count(void);
+/* What gyre_op_attention_ex / gyre_op_attention_bwd would launch for these sizes under the calling thread's forced variant, without
+ * touching a device (tests/test_attn_plan_host.py).  Return value: the status the launch would give (message in gyre_last_error()).
+ * gyre_debug_attn_plan: out[12] = kernel family (0 k_attn, 1 k_attn2 plain, 2 k_attn2 folded, 3 k_attn3), D, query fragments per wave
+ * (QI), ring lookahead (PD), ring slots, dynamic LDS bytes, grid x / y / z, query blocks per workgroup (qiter), always_check, QLOOP.
+ * gyre_debug_attn_bwd_plan: out[10] = family (0 LDS-DMA D = 40, 1 LDS-tile, 2 register-staged), the head-dim bound of the kernel
+ * set's row, d-chunks, dynamic LDS bytes, dQ grid x / y / z, dK / dV grid x / y / z (zeros without with_dk).
+ * gyre_debug_attn_tables: the kernel sets a launch can reach - which = 0: (family, D, QI, QLOOP) per forward row; 1 / 2: the bound of
+ * every LDS-tile / register-staged backward row; at most cap ints are written, the number of rows is returned. */
+int gyre_debug_attn_plan(int B, int H, int Nq, int Nk, int D, int k_prescaled, int ldq, int ldk, int ldvt, int ldo, int32_t* out);
+int gyre_debug_attn_bwd_plan(int B, int H, int Nq, int Nk, int D, int with_dk, int32_t* out);
+int gyre_debug_attn_tables(int which, int32_t* out, int cap);
 /* Tuning only: per-workgroup cycle stamps of the fused cross-attention kernel's phase boundaries (8 x uint64 per workgroup of the
  * last launch) into a caller-allocated device buffer; NULL = off (tools/r06_xattn_phases.py). */
 int gyre_debug_xattn_stamps(void* dev_buf);

@@ -20,6 +20,8 @@ import pytest
 import torch
 
 import attn_fwd_ref as R
+from attn_cases import (BRANCH_CASES, BRANCHES, MOVING_ATTN3_DIMS, MOVING_FOLDED_DIMS, MOVING_SHAPE, QLOOP_DIMS, UNSUPPORTED_DIMS,
+                        batch_heads, qloop_shapes, qloop_variants)
 from gyre_amd import _lib
 from gpu_util import DEV, HDT, check_bound, randn, release_kept, repack_linear, st, vp
 
@@ -28,17 +30,6 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 0x7E5A
 DIMS = ("sample", "query", "channel")
 TAU = R.TAU[HDT]
-# (Nq, Nk): Nq in {1, 63, 65, 129, 300} and a multi-block 600; Nk in {1, 7, 8, 63, 64, 65, 77, 129, 257, 1000}; 300 x 300 gives
-# family 5 a self-attention (Q and K out of one buffer)
-SHAPES = [(1, 1), (129, 1), (63, 7), (65, 8), (129, 63), (300, 64), (65, 65), (129, 77), (300, 129), (63, 257), (300, 300),
-          (600, 257), (300, 1000)]
-LONG = [(1, 257), (63, 257), (65, 1000), (129, 256), (300, 300), (600, 257), (300, 1000)]       # k_attn3 by default: Nk >= 256
-SHORT = [s for s in SHAPES if s[1] < 256] + [(600, 255)]                                          # k_attn3 forced below that
-
-
-def batch_heads(D):
-    return (3, 1) if D == 512 else (2, 2)
-
 
 def run_fwd(q, k, v, heads, presc, variant, layout="dense", vpad="zero"):
     """gyre_op_attention_ex under gyre_debug_force_attn_variant(variant).  layout: dense (ld = C); qk2c - Q and K at columns 0 and
@@ -101,26 +92,12 @@ def check_case(tag, ins, heads, presc, variant, layout="dense", vpad="zero", cac
     return w, got
 
 
-# branch -> (variant, prescaled, head dims, shapes, V^T pad)
-BRANCHES = {
-    "k_attn": (1, 0, [8, 16, 32, 40, 64, 80, 128, 160, 512], SHAPES, "zero"),
-    "auto_plain": (0, 0, [8, 16, 32, 40, 64, 80, 128, 160, 512], SHAPES, "nan"),          # k_attn2 plain (k_attn for 8, 512), NaN pads
-    "attn2_plain": (2, 0, [16, 32, 40, 64, 80, 128, 160], SHAPES, "zero"),
-    "attn2_plain_q64": (4, 0, [16, 32], SHAPES, "zero"),
-    "attn2_folded": (3, 1, [16, 32, 40, 64, 160], SHAPES, "zero"),
-    "prescaled_no_folded_form": (3, 1, [80, 128], SHAPES, "zero"),                        # falls to plain with unit scale
-    "attn3_optimistic": (0, 1, [16, 32, 40, 64, 80], LONG, "zero"),
-    "attn3_checked": (7, 1, [16, 32, 40, 64, 80], LONG, "zero"),
-    "attn3_short_keys": (5, 1, [16, 32, 40, 64, 80], SHORT, "zero"),
-}
-BRANCH_CASES = [(b, D) for b, spec in BRANCHES.items() for D in spec[2]]
-
-
+# the branches, their head dims and shapes, and the kernel family each reaches: tests/attn_cases.py
 @pytest.mark.parametrize("branch,D", BRANCH_CASES, ids=[f"{b}-D{D}" for b, D in BRANCH_CASES])
 def test_branch_elementwise(branch, D):
     """Families 1, 2 and 5 on every shape the branch takes, `negative` on the key counts with pad columns, uniform softmax, and a
     single key bit for bit."""
-    variant, presc, _, shapes, vpad = BRANCHES[branch]
+    variant, presc, _, shapes, vpad = BRANCHES[branch][:5]
     B, heads = batch_heads(D)
     worst = {}
 
@@ -162,9 +139,9 @@ def _moving(B, heads, Nq, Nk, D):
     return fams
 
 
-@pytest.mark.parametrize("D", [16, 32, 40, 64, 160])
+@pytest.mark.parametrize("D", MOVING_FOLDED_DIMS)
 def test_moving_maximum_folded_attn2(D):
-    B, heads, Nq, Nk = 2, 2, 300, 1000
+    B, heads, Nq, Nk = MOVING_SHAPE
     for name, (ins, _) in _moving(B, heads, Nq, Nk, D).items():
         cache = {}
         _, got = check_case(f"attn2_folded D{D} {name}", ins, heads, 1, 3, cache=cache)
@@ -178,13 +155,13 @@ def _peaked_row(tag, got, ins, cache):
     check_bound(f"{tag} the peaked row {row}", got[:, row:row + 1], ref, bound, k=R.K_FWD, tiny=R.fwd_tiny(ins[2], HDT), dims=DIMS)
 
 
-@pytest.mark.parametrize("D", [16, 32, 40, 64, 80])
+@pytest.mark.parametrize("D", MOVING_ATTN3_DIMS)
 def test_moving_maximum_attn3_default_equals_checked_and_counts_its_redos(D):
     """Default (optimistic first pass where built: OPTIMISTIC = D <= 40 in k_attn3) and variant 7 (per-tile check from the start)
     both inside the bound, bit-identical on all of family 3, the peaked row checked on its own; and the redo counter moves exactly
     when a row's first-tile-centred sum reaches 2^TAU - proof that the branch under test ran."""
     L = _lib.lib()
-    B, heads, Nq, Nk = 2, 2, 300, 1000
+    B, heads, Nq, Nk = MOVING_SHAPE
     for name, (ins, above) in _moving(B, heads, Nq, Nk, D).items():
         q, k, v = ins[:3]
         x = float(R.first_tile_excess(q, k, heads, 1).max())
@@ -214,32 +191,17 @@ def test_moving_maximum_attn3_default_equals_checked_and_counts_its_redos(D):
 # ---------------------------------------------------------------------------------------------------------------------------
 # several query blocks per workgroup (k_attn2<..., QLOOP>)
 # ---------------------------------------------------------------------------------------------------------------------------
-def _qloop_shapes(D):
-    """(B, heads, Nq, Nk, qiter expected).  ring = the largest key count whose tiles each have a ring slot."""
-    ring = 192 if D == 160 else 256
-    shapes = [(13, 16, 600, 77, 2),          # nblk = 5: qiter 2, the last workgroup walks one block, that block a tail
-              (13, 16, 640, 1, 2), (13, 16, 640, 80, 2),
-              (13, 16, 640, ring, 2), (13, 16, 640, ring + 1, 0)]     # the last key count inside the branch, the first outside
-    if D <= 64:
-        shapes.append((32, 32, 200, 77, 2))  # nblk = 2 < nblk B H / 512 = 4: qiter clipped to nblk, a tail block
-    if D == 40:
-        shapes.append((16, 8, 4096, 77, 8))  # the 64x64 level's cross-attention at batch 16: qiter clipped to 8
-    return shapes
-
-
 @pytest.mark.parametrize("presc", [0, 1], ids=["plain", "prescaled"])
-@pytest.mark.parametrize("D", [40, 64, 80, 160])
+@pytest.mark.parametrize("D", QLOOP_DIMS)
 def test_qloop_and_its_one_block_form(D, presc):
     """Automatic dispatch (variant 0: QLOOP where expects_qloop says so) and variant 6 (the same without QLOOP) on the same inputs,
     both inside the bound; the first key count outside the ring reaches the one-block form under either (see below for the prescaled
     exception).  prescaled: the folded form for D = 40, 64, 160, the plain form with unit scale for D = 80.  (No
     bit-equality between the two is asserted: the source does not state it.)  Non-prescaled automatic dispatch: NaN V^T pads."""
     vpad = "zero" if presc else "nan"
-    for B, heads, Nq, Nk, qiter in _qloop_shapes(D):
+    for B, heads, Nq, Nk, qiter in qloop_shapes(D):
         assert R.expects_qloop(B, heads, Nq, Nk, D) == qiter, (B, heads, Nq, Nk, D)
-        # the first key count outside the ring, prescaled, D <= 80: launch_attention sends Nk >= 256 to k_attn3 under variants 0 and
-        # 6 alike, so variant 3 is what reaches the one-block k_attn2 there (folded; plain with unit scale for D = 80)
-        variants = (3,) if presc and qiter == 0 and Nk >= 256 else (0, 6)
+        variants = qloop_variants(presc, qiter, Nk)       # (the first key count outside the ring: see there)
         fams = {"randn": (R.family_randn(B, heads, Nq, Nk, D, presc, HDT), ("dense",)),
                 "probes": (R.family_probes(B, heads, Nq, Nk, D, presc, HDT), ("dense", "wide"))}
         for fam, (ins, layouts) in fams.items():
@@ -250,7 +212,7 @@ def test_qloop_and_its_one_block_form(D, presc):
                                presc, variant, layout, vpad, cache=cache)
 
 
-@pytest.mark.parametrize("D", [48, 24])
+@pytest.mark.parametrize("D", UNSUPPORTED_DIMS)
 def test_unsupported_head_dim_returns_minus_six_and_writes_nothing(D):
     B, heads, Nq, Nk = 2, 2, 65, 77
     q, k, v = R.family_randn(B, heads, Nq, Nk, D, 0, HDT)

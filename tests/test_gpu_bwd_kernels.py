@@ -11,21 +11,21 @@ k = 4: a correct kernel rounds each 16-bit operand of its second products once (
 else is fp32.  The cotangents are chosen so that the terms kernels get wrong dominate: structured GroupNorm / LayerNorm cotangents
 whose true gradient nearly cancels, and score ramps whose row maximum keeps moving under the one-pass dQ kernels.
 
-The attention cases walk every dispatch branch of launch_attention_bwd: D = 40 (LDS-DMA kernels), D <= 160 (LDS-tile kernels,
-sel 0 ... 4, including D = 128 with a partial last k-step) and D > 160 (register-streaming kernels with d-chunks, D = 192 partial).
+The attention cases walk every dispatch branch of launch_attention_bwd; the head dims and the kernel set each reaches are in
+tests/attn_cases.py (BWD_REACHES), which tests/test_attn_plan_host.py holds against the library's own rule.
 """
 import math
 
 import pytest
 import torch
 
+from attn_cases import BWD_D_ALL as D_ALL, BWD_EQUAL_V_DIMS, BWD_SCALING_DIMS, BWD_SUM_DIMS, bwd_elementwise_shapes
 from gyre_amd import _lib
 from gpu_util import DEV, HDT, check_bound, randn, release_kept, st, vp
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -8 if HDT == torch.bfloat16 else 2.0 ** -11
-D_ALL = [8, 32, 40, 48, 64, 80, 96, 128, 160, 192, 512]
 TOK = ("sample", "token", "channel")
 
 
@@ -151,16 +151,7 @@ def attn_case(B, heads, Nq, Nk, D, presc, cross=False, **kw):
     return (q, k, v, o, d_o), got, ref, bnd
 
 
-def _shapes():
-    out = []
-    for D in D_ALL:
-        for (B, Nq, Nk) in ((2, 1, 1), (2, 33, 31), (1, 300, 257)) + (((1, 1030, 1030),) if D <= 160 else ()):
-            for presc in (0, 1):
-                out.append((B, Nq, Nk, D, presc))
-    return out
-
-
-@pytest.mark.parametrize("B,Nq,Nk,D,presc", _shapes())
+@pytest.mark.parametrize("B,Nq,Nk,D,presc", bwd_elementwise_shapes())
 def test_attention_bwd_elementwise(B, Nq, Nk, D, presc):
     """(1, 1): one key per row, P = 1, dQ = dK = 0 exactly in the reference; (33, 31): ragged single tiles; (300, 257): enough
     32-row tiles to wrap the prefetch rings, ragged last tile; 1030 tokens: a UNet-sized self-attention."""
@@ -224,7 +215,7 @@ _SCALES = [-4, 6] if HDT == torch.bfloat16 else [6]
 
 
 @pytest.mark.parametrize("kexp", _SCALES)
-@pytest.mark.parametrize("D", [40, 80, 160])
+@pytest.mark.parametrize("D", BWD_SCALING_DIMS)
 def test_attention_bwd_power_of_two_cotangent_scaling_is_exact(D, kexp):
     """f(2^k dO) = 2^k f(dO) bit for bit: every step is linear in dO (delta, dP, dS, the fp32 sums) and a power of two commutes
     with every rounding - unless a value leaves the format's range.  The ramp puts p = 2^(s - m) of the one-pass dQ kernels at
@@ -247,7 +238,7 @@ def test_attention_bwd_power_of_two_cotangent_scaling_is_exact(D, kexp):
             assert diff == 0, f"{name}: {diff} elements of f(2^{kexp} dO) differ from 2^{kexp} f(dO)"
 
 
-@pytest.mark.parametrize("D", [8, 40, 80, 128, 192, 512])
+@pytest.mark.parametrize("D", BWD_SUM_DIMS)
 def test_attention_bwd_sum_identities(D):
     """Per (sample, head):  sum_j dV_j = sum_q dO_q  and  sum_j dK_j = beta sum_q Q_q dO_q.(O_q - o_q)  (zero but for the rounding
     of the o handed in), each within the summed element bounds."""
@@ -264,7 +255,7 @@ def test_attention_bwd_sum_identities(D):
         check_bound(f"attn_bwd D{D} {name}", gs, want, tol / (4 * U), k=4.0, dims=("sample", "head", "d"))
 
 
-@pytest.mark.parametrize("D", [8, 40, 80, 160, 192])
+@pytest.mark.parametrize("D", BWD_EQUAL_V_DIMS)
 def test_attention_bwd_equal_value_rows_give_zero_dq_dk(D):
     """All V rows equal: O = v for every query, dP_qj = dO_q.v = delta_q, so dS = 0 and dQ = dK = 0 up to the rounding of dP and
     delta - within the bound."""
