@@ -65,6 +65,11 @@ class VAECfg(C.Structure):
                 ("layers_per_block", C.c_int32), ("norm_num_groups", C.c_int32)]
 
 
+class T2ICfg(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("cin", C.c_int32), ("channels", C.c_int32 * 4), ("n_levels", C.c_int32),
+                ("nums_rb", C.c_int32), ("ksize", C.c_int32), ("sk", C.c_int32), ("use_conv", C.c_int32)]
+
+
 _vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
 _SIGS = {
     "gyre_abi_version": (C.c_int, []),
@@ -108,6 +113,14 @@ _SIGS = {
     "gyre_vae_decode": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
     "gyre_vae_decode_vjp_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "gyre_vae_decode_vjp": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _i, _vp, _i]),
+    "gyre_t2i_create": (_i, [C.POINTER(T2ICfg), _i, C.POINTER(_vp)]),
+    "gyre_t2i_destroy": (None, [_vp]),
+    "gyre_t2i_num_params": (_i, [_vp]),
+    "gyre_t2i_param_key": (C.c_char_p, [_vp, _i]),
+    "gyre_t2i_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
+    "gyre_t2i_finalize": (_i, [_vp, _vp]),
+    "gyre_t2i_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "gyre_t2i_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(_vp), _i, _i]),
     "gyre_prof_set_mask": (_i, [C.c_uint64]),
     "gyre_prof_num_classes": (_i, []),
     "gyre_prof_class_name": (C.c_char_p, [_i]),
@@ -159,6 +172,9 @@ _SIGS = {
     "gyre_op_cross_attention_block": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "gyre_op_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "gyre_op_copy_probe": (_i, [_vp, _vp, _vp, _sz]),
+    "gyre_op_pixel_unshuffle8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gyre_op_avgpool2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "gyre_op_relu": (_i, [_vp, _vp, _sz]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

@@ -98,3 +98,32 @@ def sdxl_vae() -> VAEConfig:
 
 def tiny_vae() -> VAEConfig:
     return VAEConfig(block_out_channels=(32, 64, 64, 64), sample_size=64)
+
+
+class T2IConfig(dict):
+    """Configuration of a T2I adapter: a mapping that also reads as attributes - the reference asks both ``"cin" in
+    model.config`` and ``model.config.cin`` (unified_pipeline.py:869)."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+# the reference's per-type defaults (t2i_adapter/models.py:82-89, 187-191)
+T2I_DEFAULTS = {"main": dict(cin=192, channels=(320, 640, 1280, 1280), nums_rb=2, ksize=1, sk=True, use_conv=False),
+                "light": dict(cin=192, channels=(320, 640, 1280, 1280), nums_rb=4)}
+
+
+def t2i_config(type: str = "main", **kw) -> T2IConfig:
+    if type not in T2I_DEFAULTS:
+        raise NotImplementedError(f"T2I adapter type {type!r} (style adapters and the co-adapter fuser are outside the native path)")
+    cfg = T2IConfig(type=type, **{**T2I_DEFAULTS[type], **kw})
+    cfg["channels"] = tuple(cfg["channels"])
+    return cfg
+
+
+def tiny_t2i(kind: str = "main", **kw) -> T2IConfig:
+    """The reference's default adapter of the given kind at the widths of tiny_unet."""
+    return t2i_config(kind, **{"channels": (32, 64, 128, 128), **kw})

@@ -93,6 +93,15 @@ int launch_repack_linear(hipStream_t st, const void* w, int dtype, int O, int I,
 int launch_cast_f32(hipStream_t st, const void* w, int dtype, size_t n, int geglu_interleave, float* out, float scale = 1.f);
 int launch_copy_probe(hipStream_t st, const void* src, void* dst, size_t bytes);
 
+// ---- T2I-adapter element-wise ops (kernels_t2i.hip) ----------------------------
+// x NCHW [B][c][H][W] of a runtime dtype (H, W multiples of 8) -> y NHWC storage [B][H/8][W/8][64 c], channel c*64 + dy*8 + dx
+int launch_pixel_unshuffle8(hipStream_t st, const void* x, int dtype, int B, int c, int H, int W, bf16_t* y);
+// NHWC [B][H][W][C] -> [B][H/2][W/2][C] (C % 8 == 0; an odd last row / column is dropped): fp32 sum of the window, one rounding
+int launch_avgpool2(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, bf16_t* y);
+int launch_relu(hipStream_t st, bf16_t* x, size_t n);                      // in place, n % 8 == 0
+// y NCHW [B][C][HW] of a runtime dtype = the first C channels of x NHWC [B][HW][Cpad]
+int launch_nhwc_to_nchw(hipStream_t st, const bf16_t* x, int B, int C, int HW, int Cpad, void* y, int dtype);
+
 // ---- MFMA GEMM / implicit-GEMM conv (kernels_gemm.hip) -------------------------
 enum { GEMM_LINEAR = 0, GEMM_CONV3 = 1 };
 enum { OUT_BF16 = 0, OUT_NCHW = 1, OUT_BF16_T = 2 };

@@ -25,8 +25,11 @@ into PNG artifacts.  What this class has to honour is therefore exactly what the
   * ``set_options`` with the reference's option names (unified_pipeline.py:1538-1629)
   * no-op memory knobs (attention / VAE slicing, xformers): 288 GB of HBM3E, the whole batch stays resident.
 
-Features outside the native hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py):
-depth / hint images (ControlNet, T2I), textual-inversion token embeddings.  CLIP guidance
+Hint images handled by a T2I adapter (gyre_amd/t2i.py GyreHipT2IAdapter through the engine's ``hintset_manager``) run natively:
+the adapter once per request, its states added inside the UNet on every step (gyre_amd/hints.py).  Features outside the native
+hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py): depth maps / depth UNets, ControlNet
+hint handlers, style adapters and co-adapters, masked hints, hints together with hires fix / grafted inpaint / CLIP guidance /
+shard_devices, textual-inversion token embeddings.  CLIP guidance
 is implemented (gyre_amd/clipguided.py over the native input-gradient sweeps).  The safety checker stays the host module the
 manager loaded; it is RUN exactly as the reference runs it (``_safety_check``), never skipped silently.
 """
@@ -89,7 +92,7 @@ class GyreUnifiedPipeline:
         self.scheduler, self.inpaint_unet = scheduler, inpaint_unet
         self.safety_checker, self.feature_extractor = safety_checker, feature_extractor
         self.clip_model, self.clip_tokenizer = clip_model, clip_tokenizer
-        self.hintset_manager = hintset_manager
+        self.hintset_manager, self.depth_unet = hintset_manager, depth_unet
         self.progress_bar: Optional[Callable] = None
         self._grafted_inpaint: Any = False
         self._hires_fix, self._hires_threshold_fraction = True, 0.0333
@@ -308,6 +311,34 @@ class GyreUnifiedPipeline:
         return dict(clip_guidance_scale=scale, clip_config=cfg,
                     clip_text_embeddings=feats.repeat_interleave(num_images_per_prompt, dim=0))
 
+    def _hints(self, hint_images, mask_image) -> list:
+        """The reference's hint loop (unified_pipeline.py:1994-2047) for what is native: every hint image needs exactly one model
+        from the hintset manager and that model must be a GyreHipT2IAdapter.  Depth hints routed to a depth UNet and ControlNet
+        handlers stay NotImplementedError; a hint type nobody handles is the reference's EnvironmentError."""
+        from .hints import T2IHint
+        from .t2i import GyreHipT2IAdapter
+        hints = []
+        for hint_image in hint_images or ():
+            hint_type = hint_image.hint_type
+            weight = 1.0 if hint_image.weight is None else hint_image.weight
+            priority = hint_image.priority
+            if hint_type == "depth" and getattr(self, "depth_unet", None) is not None:
+                raise NotImplementedError("depth hints routed to a depth UNet are outside the native hot path")
+            handler_models = self.hintset_manager.for_type(hint_type, None) if self.hintset_manager else None
+            if not handler_models:
+                raise EnvironmentError(f"Pipeline doesn't know how to handle hint image of type {hint_type}")
+            models = dict(handler_models)
+            for extra in ("clip_model", "feature_extractor", "fuser"):
+                models.pop(extra, None)
+            if len(models) != 1:
+                raise ValueError(f"Unknown set of hint models: {models.keys()}")
+            _, model = models.popitem()
+            if not isinstance(model, GyreHipT2IAdapter):
+                raise NotImplementedError(f"hint model {type(model).__name__} (ControlNet and foreign adapters are outside the native hot path)")
+            hints.append(T2IHint(model, hint_image.image, mask=None, weight=weight, soft_injection=priority != "balanced",
+                                 cfg_only=priority == "hint"))
+        return hints
+
     # ---- the generation call (keywords of reference UnifiedPipeline.__call__, unified_pipeline.py:1722-1790) ---------------
     @torch.no_grad()
     def __call__(self, prompt, height: int = 512, width: int = 512, image=None, mask_image=None, outmask_image=None,
@@ -324,8 +355,11 @@ class GyreUnifiedPipeline:
                  run_safety_checker: bool = True, lora=None, token_embeddings=None,
                  hires_fix=None, hires_oos_fraction=None, tiling=False, debug_latent_tags=None, debug_latent_prefix="",
                  cfg_execution: str = "parallel"):
-        if depth_map is not None or hint_images:
-            raise NotImplementedError("depth / hint conditioning (ControlNet, T2I adapters) is outside the native hot path")
+        if depth_map is not None:
+            raise NotImplementedError("depth-map conditioning (depth UNet) is outside the native hot path")
+        t2i_hints = self._hints(hint_images, mask_image)
+        if t2i_hints and len(self._shard_devices) > 1:
+            raise NotImplementedError("hint images together with shard_devices (the adapter states live on one device slot)")
         if token_embeddings:
             raise NotImplementedError("textual-inversion token embeddings are outside the native hot path")
         if tiling not in (False, None, True, "x", "y", "xy"):
@@ -415,6 +449,8 @@ class GyreUnifiedPipeline:
                        sigma_max=sigma_max, scheduler_noise_type=scheduler_noise_type or "normal", **clip_kw)
         if sdxl:
             request.update(added_cond=added, uncond_added_cond=uadded)
+        if t2i_hints:
+            request.update(t2i_hints=[h.to(dev) for h in t2i_hints])
         if len(self._shard_devices) > 1 and B > 1 and not clip_kw and not lora and not self._tome and not tiling:
             # one request over several device slots (engine option "shard_devices"); progress / cancellation are polled once
             # per request here: the replicas run their loops concurrently and a per-step callback has no single owner.

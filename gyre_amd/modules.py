@@ -470,6 +470,19 @@ class GyreHipUNet(_NativeModule):
                 for r in keep + akeep:
                     if r.ndim != 4 or r.shape[0] != B:
                         raise ValueError(f"residual / adapter tensors must be [B,C,h,w] with B={B}, got {tuple(r.shape)}")
+                if akeep:
+                    # one state per down level, added before the level's downsampler at the cross-attention (and the last) levels,
+                    # behind it otherwise (include/gyre_hip.h gyre_unet_forward_ctrl): the native add trusts these shapes
+                    boc, ah, aw = self.config.block_out_channels, H, W
+                    if len(akeep) != len(boc):
+                        raise ValueError(f"one adapter state per down level expected ({len(boc)}), got {len(akeep)}")
+                    for i, r in enumerate(akeep):
+                        last = i == len(boc) - 1
+                        nh, nw = (ah, aw) if last else ((ah + 1) // 2, (aw + 1) // 2)
+                        want = (B, boc[i], ah, aw) if (self.config.attn_levels[i] or last) else (B, boc[i], nh, nw)
+                        if tuple(r.shape) != want:
+                            raise ValueError(f"adapter state {i} must be {want} for {H} x {W} latents, got {tuple(r.shape)}")
+                        ah, aw = nh, nw
                 midk = mid.to(dev, rdt).contiguous() if mid is not None else None
                 arr = (C.c_void_p * max(len(keep), 1))(*[r.data_ptr() for r in keep])
                 aarr = (C.c_void_p * max(len(akeep), 1))(*[r.data_ptr() for r in akeep])

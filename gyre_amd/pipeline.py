@@ -262,16 +262,20 @@ class GyrePipeline:
             leaf.blend_orig, leaf.blend_mask = orig, leaf.latent_mask
 
     def _bind_leaf(self, leaf, *, text_embeddings, uncond_embeddings, guidance_scale, cfg_execution, B, added_cond,
-                   uncond_added_cond, cfg_embeddings, clip_mode=None):
-        """UNet stack of one leaf: embeddings -> extra channels -> CFG (unified_pipeline.py:2235-2337, 2408-2430)."""
-        def bind(emb, added=None):
-            u = S.UNetWithEmbeddings(leaf.unet, emb, added)
+                   uncond_added_cond, cfg_embeddings, clip_mode=None, t2i_states=None):
+        """UNet stack of one leaf: embeddings (+ T2I-adapter states) -> extra channels -> CFG (unified_pipeline.py:2235-2337,
+        2408-2430).  t2i_states: combine_t2i_states' {"g", "u", "f"} at batch B / B / 2B (reference UNetWithT2I, unet/core.py:96-218:
+        "g" to the conditional side, "u" to the unconditional one, "f" to the CFG-parallel call)."""
+        st = t2i_states or {}
+
+        def bind(emb, added=None, states=None):
+            u = S.UNetWithEmbeddings(leaf.unet, emb, added) if states is None else S.UNetWithEmbeddings(leaf.unet, emb, added, states)
             return S.UnetWithExtraChannels(u, leaf.extra) if leaf.extra is not None else u
 
         if guidance_scale > 1.0:
             if cfg_execution == "sequential":
-                leaf.eps_unet = S.CFGUNet_Sequential(bind(text_embeddings, added_cond), bind(uncond_embeddings, uncond_added_cond),
-                                                     guidance_scale, B)
+                leaf.eps_unet = S.CFGUNet_Sequential(bind(text_embeddings, added_cond, st.get("g")),
+                                                     bind(uncond_embeddings, uncond_added_cond, st.get("u")), guidance_scale, B)
             else:
                 both = None
                 if added_cond is not None:
@@ -280,9 +284,9 @@ class GyrePipeline:
                 # tensor identity, and the leaves of a hires / graft tree alternate on the same UNet every step
                 if cfg_embeddings.get("both") is None:
                     cfg_embeddings["both"] = torch.cat([uncond_embeddings, text_embeddings])
-                leaf.eps_unet = S.CFGUNet_Parallel(bind(cfg_embeddings["both"], both), guidance_scale, B)
+                leaf.eps_unet = S.CFGUNet_Parallel(bind(cfg_embeddings["both"], both, st.get("f")), guidance_scale, B)
         else:
-            leaf.eps_unet = bind(text_embeddings, added_cond)
+            leaf.eps_unet = bind(text_embeddings, added_cond, st.get("g"))
         leaf.clip_mode = clip_mode
         if clip_mode is not None:       # ClipGuidedMode.wrap_guidance_unet over the conditional / unconditional stems
             cfg = guidance_scale > 1.0
@@ -328,9 +332,18 @@ class GyrePipeline:
                  clip_gradient_length: Optional[int] = None, clip_gradient_threshold: Optional[float] = None,
                  clip_gradient_maxloss: Optional[float] = None, vae_cutouts: Optional[int] = None,
                  approx_cutouts: Optional[int] = None, no_cutouts=None, clip_input_ids: Optional[Tensor] = None,
-                 clip_text_embeddings: Optional[Tensor] = None, clip_config: Optional[CG.ClipGuidanceConfig] = None):
+                 clip_text_embeddings: Optional[Tensor] = None, clip_config: Optional[CG.ClipGuidanceConfig] = None,
+                 t2i_hints: Optional[Sequence] = None):
         """clip_*: CLIP guidance (reference keywords of UnifiedPipeline.__call__, unified_pipeline.py:1756-1764).  The text
-        side comes as ``clip_input_ids`` (encoded by clip_model.get_text_features) or ``clip_text_embeddings`` [B, D]."""
+        side comes as ``clip_input_ids`` (encoded by clip_model.get_text_features) or ``clip_text_embeddings`` [B, D].
+        t2i_hints: gyre_amd.hints.T2IHint objects (hint image bound to its adapter).  Their states are computed once per request
+        and added inside the UNet's down path on every step.  Together with hires fix, a grafted inpaint pair or CLIP guidance
+        they are refused (NotImplementedError) before any device work."""
+        if t2i_hints:
+            if clip_guidance_scale and self.clip_model is not None and self.feature_extractor is not None:
+                raise NotImplementedError("T2I hints together with CLIP guidance (no input gradients through adapter states)")
+            if mask_image is not None and self.inpaint_unet is not None and self.inpaint_unet is not self.unet and self.grafted_inpaint:
+                raise NotImplementedError("T2I hints together with grafted inpaint")
         if height % self.vae_scale_factor or width % self.vae_scale_factor:
             raise ValueError(f"`height` and `width` have to be divisible by {self.vae_scale_factor} "
                              f"but are {height} and {width}.")
@@ -441,6 +454,8 @@ class GyrePipeline:
         if hires_fix and not (width < natural_px or height < natural_px):
             threshold = math.floor(natural_px * (1 + self.hires_threshold_fraction))
             use_hires = not (width <= threshold and height <= threshold)
+        if use_hires and t2i_hints:
+            raise NotImplementedError("T2I hints together with hires fix (the natural-size leaf needs its own resized hint states)")
         if use_hires and not is_k:
             raise ValueError("Can't use Diffuser schedulers with Hires fix. "
                              "Either use a K-Diffusion scheduler or disable Hires fix.")
@@ -458,6 +473,15 @@ class GyrePipeline:
 
         for leaf in leaves:                                     # build_mode: every constructor first
             self._construct_leaf(leaf, generators, B)
+        t2i_states = None
+        if t2i_hints:                          # once per request; the states do not depend on the step (unet/core.py:125-206)
+            from .hints import combine_t2i_states
+            t2i_states = combine_t2i_states(t2i_hints)
+            grow = lambda s: (s.expand(B, -1, -1, -1) if s.shape[0] == 1 and B > 1 else s).to(dev).contiguous()
+            t2i_states = {k: [grow(s) for s in t2i_states[k]] for k in ("u", "g")}
+            if any(s.shape[0] != B for s in t2i_states["g"]):
+                raise ValueError(f"hint image batch must be 1 or the number of seeds ({B})")
+            t2i_states["f"] = [torch.cat([u, g], dim=0) for u, g in zip(t2i_states["u"], t2i_states["g"])]
         shared = {}
         for leaf in leaves:
             clip_mode = None
@@ -471,7 +495,7 @@ class GyrePipeline:
                                               config=clip_config, generators=generators, latent_scale=self.latent_scale)
             self._bind_leaf(leaf, text_embeddings=text_embeddings, uncond_embeddings=uncond_embeddings,
                             guidance_scale=guidance_scale, cfg_execution=cfg_execution, B=B, added_cond=added_cond,
-                            uncond_added_cond=uncond_added_cond, cfg_embeddings=shared, clip_mode=clip_mode)
+                            uncond_added_cond=uncond_added_cond, cfg_embeddings=shared, clip_mode=clip_mode, t2i_states=t2i_states)
         sched.set_eps_unets([l.eps_unet for l in leaves])
         sched.set_timesteps(num_inference_steps, strength=strength if image is not None else None,
                             config=S.SchedulerConfig(eta=eta, karras_rho=karras_rho, churn=churn, churn_tmin=churn_tmin,

@@ -160,10 +160,15 @@ class CFGUNet_Sequential:
 class UNetWithEmbeddings:
     """Binds encoder_hidden_states and takes `.sample` (reference unet/core.py:242-274)."""
 
-    def __init__(self, unet, text_embeddings: Tensor, added_cond_kwargs: Optional[dict] = None):
-        self.unet, self.text_embeddings, self.added = unet, text_embeddings, added_cond_kwargs
+    def __init__(self, unet, text_embeddings: Tensor, added_cond_kwargs: Optional[dict] = None, adapter_states=None):
+        """adapter_states: T2I-adapter states of the request, one NCHW tensor per down level at the batch of this wrapper's
+        calls (reference UNetWithT2I.__call__, unet/core.py:213-218)."""
+        self.unet, self.text_embeddings, self.added, self.adapter_states = unet, text_embeddings, added_cond_kwargs, adapter_states
 
     def __call__(self, latents: Tensor, t) -> Tensor:
+        if self.adapter_states is not None:
+            kw = {} if self.added is None else {"added_cond_kwargs": self.added}
+            return self.unet(latents, t, encoder_hidden_states=self.text_embeddings, adapter_states=self.adapter_states, **kw).sample
         if self.added is not None:   # SDXL "text_time" conditioning (pooled text embedding + size / crop ids)
             return self.unet(latents, t, encoder_hidden_states=self.text_embeddings, added_cond_kwargs=self.added).sample
         return self.unet(latents, t, encoder_hidden_states=self.text_embeddings).sample

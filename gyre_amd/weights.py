@@ -197,3 +197,40 @@ def synthetic_tensor(key: str, shape: Tuple[int, ...], seed: int = 0) -> torch.T
 
 def synthetic_state_dict(shapes: Shapes, seed: int = 0) -> Dict[str, torch.Tensor]:
     return OrderedDict((k, synthetic_tensor(k, shp, seed)) for k, shp in shapes.items())
+
+
+def t2i_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's T2I adapters (gyre/pipeline/t2i_adapter/adapter.py ``Adapter`` for
+    ``type == "main"``, ``Adapter_light`` for ``"light"``); cfg: a mapping as gyre_amd.config.tiny_t2i returns."""
+    s: Shapes = OrderedDict()
+    ch, nums_rb, cin = tuple(cfg["channels"]), cfg["nums_rb"], cfg["cin"]
+
+    def conv(p, o, i, k):
+        s[p + ".weight"] = (o, i, k, k)
+        s[p + ".bias"] = (o,)
+
+    if cfg.get("type", "main") == "light":
+        for i, c in enumerate(ch):
+            inter = c // 4
+            conv(f"body.{i}.in_conv", inter, ch[i - 1] if i else cin, 1)
+            for j in range(nums_rb):
+                conv(f"body.{i}.body.{j}.block1", inter, inter, 3)
+                conv(f"body.{i}.body.{j}.block2", inter, inter, 3)
+            conv(f"body.{i}.out_conv", c, inter, 1)
+        return s
+    k, sk, use_conv = cfg["ksize"], cfg["sk"], cfg["use_conv"]
+    for i, c in enumerate(ch):
+        for j in range(nums_rb):
+            p = f"body.{i * nums_rb + j}"
+            down = i != 0 and j == 0
+            in_c = ch[i - 1] if down else c
+            if in_c != c or not sk:
+                conv(p + ".in_conv", c, in_c, k)
+            conv(p + ".block1", c, c, 3)
+            conv(p + ".block2", c, c, k)
+            if not sk:
+                conv(p + ".skep", c, in_c, k)
+            if down and use_conv:
+                conv(p + ".down_opt.op", in_c, in_c, 3)
+    conv("conv_in", ch[0], cin, 3)
+    return s

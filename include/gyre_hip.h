@@ -90,8 +90,21 @@ typedef struct {
     int32_t norm_num_groups;         /* 32 */
 } gyre_vae_cfg;
 
+/* T2I adapter (reference gyre/pipeline/t2i_adapter/adapter.py: Adapter = "main", Adapter_light = "light") */
+typedef struct {
+    int32_t kind;                    /* 0 main, 1 light */
+    int32_t cin;                     /* 64 x image channels (PixelUnshuffle(8)): 64 or 192 */
+    int32_t channels[4];             /* 320,640,1280,1280 */
+    int32_t n_levels;                /* 4 */
+    int32_t nums_rb;                 /* residual blocks per level: 2 (main), 4 (light) */
+    int32_t ksize;                   /* main: kernel size of in_conv / block2 / skep, 1 or 3 */
+    int32_t sk;                      /* main: 1 = identity skip (no skep conv, in_conv only where the width changes) */
+    int32_t use_conv;                /* main: 1 = stride-2 conv downsampling (down_opt.op), 0 = 2x2 average pool */
+} gyre_t2i_cfg;
+
 typedef struct gyre_unet gyre_unet;
 typedef struct gyre_vae gyre_vae;
+typedef struct gyre_t2i gyre_t2i;
 
 /* ---- library ---------------------------------------------------------- */
 int gyre_abi_version(void);
@@ -249,6 +262,21 @@ int gyre_vae_encode(gyre_vae* h, void* stream, const void* image_nchw, int in_dt
 /* image[B,3,8h,8w] = decoder(post_quant_conv(z[B,z,h,w])) */
 int gyre_vae_decode(gyre_vae* h, void* stream, const void* z_nchw, int in_dtype, int B, int h_lat, int w_lat,
                     void* workspace, size_t workspace_bytes, void* image_out_nchw, int out_dtype);
+
+/* ---- T2I adapter ------------------------------------------------------------ */
+/* Weight keys are the state-dict keys of the reference's Adapter / Adapter_light.  Same weight store, workspace and dry-run sizing
+ * rules as the UNet and the VAE. */
+int gyre_t2i_create(const gyre_t2i_cfg* cfg, int device, gyre_t2i** out);
+void gyre_t2i_destroy(gyre_t2i* h);
+int gyre_t2i_num_params(const gyre_t2i* h);
+const char* gyre_t2i_param_key(const gyre_t2i* h, int i);
+int gyre_t2i_set_weight(gyre_t2i* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_t2i_finalize(gyre_t2i* h, void* stream);
+size_t gyre_t2i_workspace_bytes(gyre_t2i* h, int B, int H, int W);
+/* features_out_nchw[i] [B, channels[i], H/8 >> i, W/8 >> i] = level i of the adapter over image[B, cin/64, H, W] (H, W multiples
+ * of 8; n = n_levels).  The stride-2 conv downsampling (use_conv) rounds an odd size up, the average pool down, as torch does. */
+int gyre_t2i_forward(gyre_t2i* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                     void* workspace, size_t workspace_bytes, void* const* features_out_nchw, int n, int out_dtype);
 
 /* ---- per-launch timing with HIP events on the launch stream (bench.py roofline leg) ----
  * mask: bit k enables kernel class k (names from gyre_prof_class_name; they equal the prefix of the
@@ -473,6 +501,12 @@ int gyre_op_cross_attention_block(void* stream, const void* x, int M, int tokens
                                   const float* beta, float eps, const void* wq, const void* k_prescaled, const void* vt, int Nk,
                                   int ldvt, const void* wo, const float* bo, void* ws, size_t ws_bytes, void* out, float* row_stats);
 int gyre_op_nchw_to_nhwc(void* stream, const void* x, int dtype, int B, int C, int HW, int Cpad, void* y_bf16);
+/* The element-wise kernels of the T2I adapter (kernels_t2i.hip).  pixel_unshuffle8: x NCHW [B][c][H][W] of a runtime dtype -> y NHWC
+ * storage [B][H/8][W/8][64 c] in torch.nn.PixelUnshuffle(8) channel order.  avgpool2: NHWC storage [B][H][W][C] -> [B][H/2][W/2][C]
+ * (C % 8 == 0; fp32 sum, one rounding).  relu: in place on n storage elements (n % 8 == 0). */
+int gyre_op_pixel_unshuffle8(void* stream, const void* x, int dtype, int B, int c, int H, int W, void* y);
+int gyre_op_avgpool2(void* stream, const void* x, int B, int H, int W, int C, void* y);
+int gyre_op_relu(void* stream, void* x, size_t n);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
