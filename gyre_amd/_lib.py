@@ -136,6 +136,8 @@ _SIGS = {
     "gyre_debug_xattn_stamps": (_i, [_vp]),
     "gyre_debug_force_attn_variant": (_i, [_i]),
     "gyre_debug_gemm_ablation": (_i, [_i]),
+    "gyre_debug_ln_linear_folds": (_i, [_i, _i, _i, _i]),
+    "gyre_debug_gn_uses_small": (_i, [_i, _i, _i, _i]),
     "gyre_set_batch_invariant": (_i, [_i]),
     "gyre_get_batch_invariant": (_i, []),
     "gyre_op_groupnorm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _sz, _vp]),
@@ -144,6 +146,7 @@ _SIGS = {
     "gyre_op_conv3x3_colstats": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gyre_op_linear_colstats": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gyre_op_groupnorm_colstats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "gyre_op_gn_fold": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp, _vp]),
     "gyre_op_layernorm": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _vp]),
     "gyre_op_linear": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "gyre_op_linear_t": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _vp]),

@@ -426,6 +426,29 @@ int gyre_op_groupnorm_colstats(void* st, const void* x, const void* x2, int C1, 
     if (!gn_accepts_colstats(p)) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "groupnorm: this shape does not take producer statistics");
     return launch_groupnorm_apply((hipStream_t)st, p);
 }
+// The weight side of Linear(GroupNorm(x)) as gn_fold_linear (model_impl.h) runs it, without the GEMM: the statistics pass unless
+// the producer's column statistics are given (cs_x), then per sample Wf_out [B][N][C] = W diag(rstd gamma) and
+// bf_out [B][N] = bias + W (beta - mean rstd gamma).  One source only (the fold has no concat form).
+int gyre_op_gn_fold(void* st, const void* x, int B, int HW, int C, int groups, const float* gamma, const float* beta, float eps,
+                    const void* W, const float* bias, int N, const float* cs_x, int cs_x_chunks, int unit, void* ws, size_t wsb,
+                    void* Wf_out, float* bf_out) {
+    if (!x || !gamma || !beta || !W || !ws || !Wf_out || !bf_out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (B <= 0 || HW <= 0 || C <= 0 || groups <= 0 || N <= 0) GYRE_FAIL(GYRE_ERR_INVALID, "gn_fold: sizes must be positive");
+    if (wsb < gn_workspace_bytes(B, HW, C, groups)) GYRE_FAIL(GYRE_ERR_WORKSPACE, "gn_fold workspace too small");
+    GnParams p;
+    p.x = (const bf16_t*)x; p.x2 = (const bf16_t*)x; p.C1 = C;
+    p.B = B; p.HW = HW; p.C = C; p.G = groups; p.gamma = gamma; p.beta = beta; p.eps = eps; p.silu = 0;
+    p.nchunks = gn_pick_chunks(B, HW, C);
+    p.partial = (float*)ws;
+    p.scale_shift = (float*)((char*)ws + align_up((size_t)B * p.nchunks * groups * 2 * sizeof(float), 256));
+    if (cs_x) {
+        if (unit <= 0 || cs_x_chunks <= 0 || C % groups || (C / groups) % unit) GYRE_FAIL(GYRE_ERR_INVALID, "gn_fold: bad producer statistics");
+        p.cs_x = cs_x; p.cs_x_chunks = cs_x_chunks; p.cs_unit = unit;
+    } else {
+        TRY(launch_groupnorm_stats((hipStream_t)st, p));
+    }
+    return launch_gn_fold((hipStream_t)st, p, (const bf16_t*)W, bias, N, (bf16_t*)Wf_out, bf_out);
+}
 int gyre_op_layernorm(void* st, const void* x, int M, int C, const float* g, const float* b, float eps, void* y) {
     if (!x || !g || !b || !y) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     return launch_layernorm((hipStream_t)st, (const bf16_t*)x, M, C, g, b, eps, (bf16_t*)y);
@@ -607,20 +630,37 @@ int gyre_op_linear_rowstats(void* st, const void* x, int M, int K, const void* w
     p.rowstat_out = stats_out;
     return launch_gemm((hipStream_t)st, p);
 }
+// The problem gyre_op_ln_linear hands to the planner: shared by the operator and by its shape query, so the two cannot drift.
+static void ln_linear_problem(GemmParams& p, int M, int K, int N, int geglu, int qkv_tokens, int ldt) {
+    p.lda = K; p.mode = GEMM_LINEAR; p.K = K; p.M = M; p.out_mode = OUT_BF16;
+    if (qkv_tokens > 0) {
+        p.N = 3 * K; p.ldc = 2 * K; p.samples = M / qkv_tokens;
+        p.vt_col0 = 2 * K; p.tokens_per_batch = qkv_tokens; p.ldt = ldt;
+    } else {
+        p.N = geglu ? 2 * N : N; p.ldc = N; p.geglu = geglu;
+    }
+}
+// Shape queries (no device).  Would gyre_op_ln_linear keep the folded form for this plain / GEGLU linear (N as there)?
+int gyre_debug_ln_linear_folds(int M, int K, int N, int geglu) {
+    if (M <= 0 || K <= 0 || N <= 0) return 0;
+    GemmParams p;
+    ln_linear_problem(p, M, K, N, geglu, 0, 0);
+    return gemm_plan(p).ln_fold ? 1 : 0;
+}
+// Does gyre_op_groupnorm run the one-launch two-pass kernel (k_gn_small) for this shape?  (C1 = C for one source)
+int gyre_debug_gn_uses_small(int HW, int C, int C1, int groups) {
+    if (HW <= 0 || C <= 0 || groups <= 0 || C % groups) return 0;
+    return gn_use_small(HW, C, C1, groups) ? 1 : 0;
+}
 int gyre_op_ln_linear(void* st, const void* x, int M, int K, const float* gamma, const float* beta, float eps, const void* w,
                       int N, const float* bias, int geglu, int qkv_tokens, void* vt_out, int ldt, const float* row_parts,
                       int n_parts, void* ws, size_t ws_bytes, void* y) {
     if (!x || !w || !y || !gamma || !beta || !ws) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     GemmParams p;
-    p.A = (const bf16_t*)x; p.lda = K; p.mode = GEMM_LINEAR; p.W = (const bf16_t*)w; p.K = K; p.M = M; p.bias = bias;
-    p.out = y; p.out_mode = OUT_BF16;
-    if (qkv_tokens > 0) {
-        if (!vt_out || M % qkv_tokens || N != 3 * K || geglu) GYRE_FAIL(GYRE_ERR_INVALID, "bad fused Q|K|V arguments");
-        p.N = 3 * K; p.ldc = 2 * K; p.samples = M / qkv_tokens;
-        p.vt_out = (bf16_t*)vt_out; p.vt_col0 = 2 * K; p.tokens_per_batch = qkv_tokens; p.ldt = ldt;
-    } else {
-        p.N = geglu ? 2 * N : N; p.ldc = N; p.geglu = geglu;
-    }
+    if (qkv_tokens > 0 && (!vt_out || M % qkv_tokens || N != 3 * K || geglu)) GYRE_FAIL(GYRE_ERR_INVALID, "bad fused Q|K|V arguments");
+    ln_linear_problem(p, M, K, N, geglu, qkv_tokens, ldt);
+    p.A = (const bf16_t*)x; p.W = (const bf16_t*)w; p.bias = bias; p.out = y;
+    if (qkv_tokens > 0) p.vt_out = (bf16_t*)vt_out;
     if (ws_bytes < gyre_op_ln_linear_workspace(p.N, K, M)) GYRE_FAIL(GYRE_ERR_WORKSPACE, "ln_linear: workspace too small");
     if (!gemm_plan(p).ln_fold) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "ln_linear: the planner's kernel for this shape cannot fold the LayerNorm");
     bf16_t* wf = (bf16_t*)ws;

@@ -353,6 +353,10 @@ int gyre_debug_xattn_stamps(void* dev_buf);
  * These switches are PER CALLING THREAD (thread-local, like gyre_set_batch_invariant): they never change what another thread's
  * handle computes. */
 int gyre_debug_gemm_ablation(int bits);
+/* Shape query, no device: 1 when gyre_op_ln_linear keeps the folded form for this plain / GEGLU linear (N as there), else 0. */
+int gyre_debug_ln_linear_folds(int M, int K, int N, int geglu);
+/* Shape query, no device: 1 when gyre_op_groupnorm runs the one-launch two-pass kernel for this shape (C1 = C for one source). */
+int gyre_debug_gn_uses_small(int HW, int C, int C1, int groups);
 
 /* ---- batch-invariant mode ------------------------------------------------
  * The reference asserts that an image does not depend on what shares its batch (tests/batch_independance.py:15-27)
@@ -395,6 +399,13 @@ int gyre_op_linear_colstats(void* stream, const void* x, int M, int K, const voi
 int gyre_op_groupnorm_colstats(void* stream, const void* x, const void* x2, int C1, int B, int HW, int C, int groups,
                                const float* gamma, const float* beta, float eps, int silu, const float* cs_x, int cs_x_chunks,
                                const float* cs_x2, int cs_x2_chunks, int unit, void* workspace, size_t workspace_bytes, void* y);
+/* The affine-only GroupNorm folded into the Linear that consumes it, up to but not including the GEMM: per sample
+ * Wf_out [B][N][C] = W diag(rstd gamma) (16-bit, rounded once) and bf_out [B][N] f32 = bias + W (beta - mean rstd gamma).
+ * cs_x != NULL: statistics from the producer's partials ([B][cs_x_chunks][C / unit][2], unit divides C / groups), else the
+ * kernel's own statistics pass.  bias may be NULL.  workspace: gyre_op_groupnorm_workspace(B, HW, C, groups) bytes. */
+int gyre_op_gn_fold(void* stream, const void* x, int B, int HW, int C, int groups, const float* gamma, const float* beta, float eps,
+                    const void* W, const float* bias, int N, const float* cs_x, int cs_x_chunks, int unit,
+                    void* workspace, size_t workspace_bytes, void* Wf_out, float* bf_out);
 int gyre_op_layernorm(void* stream, const void* x, int M, int C, const float* gamma, const float* beta,
                       float eps, void* y);
 /* y[M,N] = x[M,K] @ w[N,K]^T (+bias) (+residual); geglu!=0: w holds [2N,K], y = val*gelu(gate) */
