@@ -70,6 +70,15 @@ class T2ICfg(C.Structure):
                 ("nums_rb", C.c_int32), ("ksize", C.c_int32), ("sk", C.c_int32), ("use_conv", C.c_int32)]
 
 
+class GemmTestArgs(C.Structure):
+    """gyre_gemm_test_args (include/gyre_hip.h): one GEMM / conv launch field by field, for tests and tuning."""
+    _fields_ = [(n, C.c_int32) for n in ("conv", "M", "K", "N", "geglu", "B", "Hi", "Wi", "Cin", "stride", "pad", "ups", "Hup", "Wup",
+                                         "wrap", "C1", "lda", "lda2", "ldc", "ldr", "rows_per_sample", "ld_rowbias", "samples",
+                                         "out_mode", "out_dtype", "tokens", "ldt", "colstat_unit")] + \
+               [(n, C.c_void_p) for n in ("A", "A2", "W", "bias", "rowbias", "residual", "out", "ws")] + [("ws_bytes", C.c_size_t)] + \
+               [("sc_A", C.c_void_p), ("sc_A2", C.c_void_p)] + [(n, C.c_int32) for n in ("sc_K", "sc_C1", "sc_lda", "sc_lda2")]
+
+
 _vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
 _SIGS = {
     "gyre_abi_version": (C.c_int, []),
@@ -138,6 +147,9 @@ _SIGS = {
     "gyre_debug_gemm_ablation": (_i, [_i]),
     "gyre_debug_ln_linear_folds": (_i, [_i, _i, _i, _i]),
     "gyre_debug_gn_uses_small": (_i, [_i, _i, _i, _i]),
+    "gyre_op_gemm_test": (_i, [_vp, C.POINTER(GemmTestArgs)]),
+    "gyre_debug_gemm_plan": (_i, [C.POINTER(GemmTestArgs), C.POINTER(C.c_int32)]),
+    "gyre_debug_gemm_tiles": (_i, [C.POINTER(C.c_int32), _i]),
     "gyre_set_batch_invariant": (_i, [_i]),
     "gyre_get_batch_invariant": (_i, []),
     "gyre_op_groupnorm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _sz, _vp]),

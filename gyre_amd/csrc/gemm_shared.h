@@ -39,6 +39,11 @@ struct GemmTile {
     bool w_block;        // reads the blocked weight copy (W_blk)
 };
 const GemmTile* gemm_tile(int cfg);     // nullptr: no such config
+// Convolutions whose K steps are whole 64-channel chunks of one source walk K chunk-outer / tap-inner (UNIFORM_TAP of k_gemm and
+// k_gemm8): the one predicate, read by both launchers and by the plan query.  p normalised as launch_gemm sees it.
+static inline bool gemm_conv_uniform_tap(const GemmParams& p) { return p.Cin % BK == 0 && p.C1 % BK == 0; }
+// ring depth and uniform-tap flag of an 8-wave launch (kernels_gemm.hip; p normalised as launch_gemm sees it)
+void gemm8_loop_form(const GemmParams& p, int bm, int bn, int splits, int* nst, bool* uni);
 
 // kernels_gemm4s.hip: tile configs 20 - 24
 bool gemm4s_supports(const GemmParams& p, int cfg);

@@ -219,6 +219,10 @@ struct GemmPlan {
 GemmPlan gemm_plan(const GemmParams& p);
 int launch_gemm(hipStream_t st, const GemmParams& p);                          // plans `p`, then runs that plan
 int launch_gemm(hipStream_t st, const GemmParams& p, const GemmPlan& plan);    // plan: gemm_plan(p)
+// Plan queries (no device).  *nst = the LDS ring depth the launch of `plan` would use when its kernel is an 8-wave one (else 0),
+// *uni = 1 when a convolution's K loop takes the uniform-tap form (chunk outer, tap inner), both from the rule the launch reads.
+void gemm_plan_loop_form(const GemmParams& p, const GemmPlan& plan, int* nst, int* uni);
+int gemm_tile_table(int* out, int cap);      // (id, bm, bn, kind) of every tile config, at most cap ints; returns the number of configs
 
 
 // ---- flash-style attention (kernels_attn.hip) ------------------------------------

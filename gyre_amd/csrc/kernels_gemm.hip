@@ -1220,7 +1220,7 @@ static int launch_cfg(hipStream_t st, const GemmParams& p) {
     if (p.mode == GEMM_LINEAR) {
         if (trans) GYRE_GEMM_GO(GEMM_LINEAR, true, true); else GYRE_GEMM_GO(GEMM_LINEAR, true, false);
     } else {
-        const bool uni = (p.Cin % BK == 0) && (p.C1 % BK == 0);
+        const bool uni = gemm_conv_uniform_tap(p);
         if (trans) GYRE_FAIL(-6, "conv with transposed output is not supported");
         if (uni) GYRE_GEMM_GO(GEMM_CONV3, true, false); else GYRE_GEMM_GO(GEMM_CONV3, false, false);
     }
@@ -1248,13 +1248,15 @@ const bf16_t* gemm_zero_page_for_current_device() {
     return (const bf16_t*)p;
 }
 
-template <int BM, int BN, int WM, int WN>
-static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int splits) {
+// The K-loop form an 8-wave launch (k_gemm8) of tile bm x bn takes for `p` in `splits` K slices: the one rule, read by launch_cfg8
+// and by the plan query (gyre_debug_gemm_plan).
+//  *nst: ring depth of the linear-mode K loop: as deep as the LDS of ONE workgroup per CU allows when the grid has no second
+//   workgroup for a CU anyway (or the tile is too big for two), else two stages each for two co-resident workgroups
+//   (tuning bit 24: the two-stage loop everywhere; bit 25: the deep ring also where two 2-stage workgroups would fit)
+//  *uni: convolutions whose K steps are whole 64-channel chunks of one source walk K chunk-outer / tap-inner (UNIFORM_TAP)
+void gemm8_loop_form(const GemmParams& p, int BM, int BN, int splits, int* nst_out, bool* uni_out) {
     const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
     const int grid = tiles_m * tiles_n * splits;
-    // ring depth of the linear-mode K loop (k_gemm8): as deep as the LDS of ONE workgroup per CU allows when the grid has no second
-    // workgroup for a CU anyway (or the tile is too big for two), else two stages each for two co-resident workgroups
-    // (tuning bit 24: the two-stage loop everywhere; bit 25: the deep ring also where two 2-stage workgroups would fit)
     const size_t stage = (size_t)(BM + (BN + 63) / 64 * 64) * 128;
     int nst = 2;
     const bool conv_ring = ((BM == 128 && BN == 160) || (BM == 256 && BN == 128)) && p.mode == GEMM_CONV3 && p.Cin % BK == 0 && p.C1 % BK == 0 && p.K % BK == 0 && !(p.debug & GEMM_DBG_TWO_STAGE_CONV);
@@ -1266,6 +1268,17 @@ static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int s
         if (nst > steps) nst = steps < 2 ? 2 : steps;
         if (nst < 2) nst = 2;
     }
+    *nst_out = nst;
+    *uni_out = p.mode == GEMM_LINEAR || gemm_conv_uniform_tap(p);
+}
+
+template <int BM, int BN, int WM, int WN>
+static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int splits) {
+    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    const int grid = tiles_m * tiles_n * splits;
+    const size_t stage = (size_t)(BM + (BN + 63) / 64 * 64) * 128;
+    int nst = 2; bool uni = true;
+    gemm8_loop_form(p, BM, BN, splits, &nst, &uni);
     size_t lds = (size_t)nst * stage;
     if (p.mode == GEMM_LINEAR && p.ln_colsum && p.geglu && gemm_geglu_lnf_lds_bytes(BM, BN, WM, WN) <= 160 * 1024)
         lds = std::max(lds, gemm_geglu_lnf_lds_bytes(BM, BN, WM, WN));
@@ -1286,7 +1299,6 @@ static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int s
     } while (0)
     if (p.colstat_out && splits == 1) {
         if constexpr (BN == 320 || BN == 160) {
-            const bool uni = (p.Cin % BK == 0) && (p.C1 % BK == 0);
 #define GYRE_GEMM8_CS(MODE_, UNI_)                                                                                  \
     do {                                                                                                            \
         auto kern = k_gemm8<BM, BN, WM, WN, MODE_, UNI_, false, false, true>;                                       \
@@ -1317,7 +1329,6 @@ static int launch_cfg8(hipStream_t st, const GemmParams& p, int kcls_base, int s
     } else if (p.mode == GEMM_LINEAR) {
         GYRE_GEMM8_GO(GEMM_LINEAR, true);
     } else {
-        const bool uni = (p.Cin % BK == 0) && (p.C1 % BK == 0);
         if (uni) GYRE_GEMM8_GO(GEMM_CONV3, true); else GYRE_GEMM8_GO(GEMM_CONV3, false);
     }
 #undef GYRE_GEMM8_GO
@@ -1582,6 +1593,27 @@ GemmPlan gemm_plan(const GemmParams& p0) {
         if (rows && p.rows_per_sample % rows == 0) pl.colstat_rows = rows;
     }
     return pl;
+}
+
+void gemm_plan_loop_form(const GemmParams& p0, const GemmPlan& plan, int* nst, int* uni) {
+    const GemmParams p = gemm_normalised(p0);
+    const GemmTile* t = gemm_tile(plan.cfg);
+    *nst = 0; *uni = 0;
+    if (!t) return;
+    // (the pipelined, A-resident and small-problem kernels have no tap forms: their K steps are always whole chunks)
+    if (t->kind == GEMM_K_4W) *uni = p.mode == GEMM_CONV3 && gemm_conv_uniform_tap(p) ? 1 : 0;
+    if (t->kind != GEMM_K_8W) return;
+    bool u = true;
+    gemm8_loop_form(p, t->bm, t->bn, plan.splits, nst, &u);
+    *uni = p.mode == GEMM_CONV3 && u ? 1 : 0;
+}
+int gemm_tile_table(int* out, int cap) {
+    int n = 0;
+    for (const GemmTile& t : g_tiles) {
+        if (4 * n + 4 <= cap) { out[4 * n] = t.id; out[4 * n + 1] = t.bm; out[4 * n + 2] = t.bn; out[4 * n + 3] = (int)t.kind; }
+        ++n;
+    }
+    return n;
 }
 
 // W[N][K] -> 1-KiB blocks of 8 rows x 64 k (GemmParams::W_blk); one thread per 16 bytes

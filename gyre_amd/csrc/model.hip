@@ -652,6 +652,118 @@ int gyre_debug_gn_uses_small(int HW, int C, int C1, int groups) {
     if (HW <= 0 || C <= 0 || groups <= 0 || C % groups) return 0;
     return gn_use_small(HW, C, C1, groups) ? 1 : 0;
 }
+// The problem gyre_op_gemm_test launches and gyre_debug_gemm_plan asks the planner about: built here for both, so the two cannot
+// drift.  Returns the status of the argument check (every integer is looked at before anything is derived from it).
+static int gemm_test_problem(GemmParams& p, const gyre_gemm_test_args* a, bool need_device_pointers) {
+    if (!a) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: null argument struct");
+    if (need_device_pointers && (!a->A || !a->W || !a->out)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: null argument");
+    const int lim = 1 << 24;
+    if ((a->conv != 0 && a->conv != 1) || a->N <= 0 || a->N > lim || (a->geglu != 0 && a->geglu != 1))
+        GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: conv and geglu are 0 or 1, N must be positive");
+    if (a->out_mode < OUT_BF16 || a->out_mode > OUT_BF16_T || a->out_dtype < 0 || a->out_dtype > 2)
+        GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: bad out_mode / out_dtype");
+    if (a->lda < 0 || a->lda2 < 0 || a->ldc < 0 || a->ldr < 0 || a->C1 < 0 || a->ld_rowbias < 0 || a->rows_per_sample < 0 || a->samples < 0 ||
+        a->tokens < 0 || a->ldt < 0 || a->colstat_unit < 0 || a->lda > lim || a->lda2 > lim || a->ldc > lim || a->ldr > lim || a->ld_rowbias > lim)
+        GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: negative or oversized stride / count");
+    const int n_out = a->N, n_w = a->geglu ? 2 * a->N : a->N;
+    int M, K, width;             // rows, reduction length, logical width of the A operand's rows (linear: K, conv: Cin)
+    if (a->conv) {
+        if (a->B <= 0 || a->Hi <= 0 || a->Wi <= 0 || a->Cin <= 0 || a->B > 4096 || a->Hi > 4096 || a->Wi > 4096 || a->Cin > 65536 || a->Cin % 8)
+            GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: conv sizes must be positive, Cin a multiple of 8");
+        if ((a->stride != 1 && a->stride != 2) || (a->pad != 0 && a->pad != 1) || (a->ups != 0 && a->ups != 1) || a->wrap < 0 || a->wrap > 3)
+            GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: stride 1 or 2, pad 0 or 1, ups 0 or 1, wrap 0 .. 3");
+        if (a->geglu || a->out_mode == OUT_BF16_T) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: GEGLU and transposed output are linear forms");
+        if (a->wrap && a->pad != 1) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: circular padding replaces the symmetric pad of 1");
+        if (!a->ups && (a->Hup || a->Wup)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: Hup / Wup need ups");
+        if (a->ups && ((a->Hup != 0 && a->Hup != 2 * a->Hi && a->Hup != 2 * a->Hi - 1) || (a->Wup != 0 && a->Wup != 2 * a->Wi && a->Wup != 2 * a->Wi - 1)))
+            GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: the upsample target must be 2x or 2x-1 of the input");
+        const int Hin = a->ups ? (a->Hup ? a->Hup : 2 * a->Hi) : a->Hi, Win = a->ups ? (a->Wup ? a->Wup : 2 * a->Wi) : a->Wi;
+        if (Hin + (a->pad ? 2 : 1) < 3 || Win + (a->pad ? 2 : 1) < 3) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: image smaller than the window");
+        const int Ho = (Hin + (a->pad ? 2 : 1) - 3) / a->stride + 1, Wo = (Win + (a->pad ? 2 : 1) - 3) / a->stride + 1;
+        if ((long)a->B * Ho * Wo > lim) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: too many output pixels");
+        M = a->B * Ho * Wo; K = 9 * a->Cin; width = a->Cin;
+        p.mode = GEMM_CONV3; p.Hi = a->Hi; p.Wi = a->Wi; p.Cin = a->Cin; p.Ho = Ho; p.Wo = Wo; p.stride = a->stride; p.pad = a->pad;
+        p.ups = a->ups; p.Hup = a->ups ? a->Hup : 0; p.Wup = a->ups ? a->Wup : 0; p.wrap = a->wrap;
+        p.samples = a->B; p.rows_per_sample = Ho * Wo;
+        if (a->samples && a->samples != a->B) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: samples of a convolution is B");
+        if (a->rows_per_sample && a->rows_per_sample != Ho * Wo) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: rows_per_sample of a convolution is Ho * Wo");
+    } else {
+        if (a->M <= 0 || a->K <= 0 || a->M > lim || a->K > lim || a->K % 8) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: M and K must be positive, K a multiple of 8");
+        if (a->out_mode == OUT_NCHW) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: NCHW output is a convolution form");
+        M = a->M; K = a->K; width = a->K;
+        p.mode = GEMM_LINEAR; p.rows_per_sample = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
+        if (M % p.rows_per_sample) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: rows_per_sample must divide M");
+        p.samples = a->samples;
+        if (a->samples && M % a->samples) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: samples must divide M");
+    }
+    if (a->sc_K < 0 || a->sc_K > 65536 || a->sc_C1 < 0 || a->sc_lda < 0 || a->sc_lda2 < 0 || a->sc_lda > lim || a->sc_lda2 > lim)
+        GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: negative or oversized shortcut field");
+    if (a->sc_K) {         // (launch_gemm checks the form itself: whole 64-channel steps, stride 1, pad 1, no upsample / wrap)
+        if (!a->conv || a->sc_K % 8) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: the folded shortcut belongs to a convolution, sc_K a multiple of 8");
+        if (need_device_pointers && !a->sc_A) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: null shortcut source");
+        p.sc_A = (const bf16_t*)a->sc_A; p.sc_K = a->sc_K; p.sc_C1 = a->sc_K; p.sc_lda = a->sc_lda ? a->sc_lda : a->sc_K;
+        if (a->sc_A2) {
+            if (a->sc_C1 <= 0 || a->sc_C1 >= a->sc_K || a->sc_C1 % 8) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: sc_C1 must be a multiple of 8 inside sc_K");
+            p.sc_A2 = (const bf16_t*)a->sc_A2; p.sc_C1 = a->sc_C1; p.sc_lda = a->sc_lda ? a->sc_lda : a->sc_C1;
+            p.sc_lda2 = a->sc_lda2 ? a->sc_lda2 : a->sc_K - a->sc_C1;
+            if (p.sc_lda2 < a->sc_K - a->sc_C1 || p.sc_lda2 % 8 || ((size_t)a->sc_A2 & 15)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: bad second shortcut source");
+        }
+        if (p.sc_lda < p.sc_C1 || p.sc_lda % 8 || ((size_t)a->sc_A & 15)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: bad shortcut source stride / alignment");
+        K += a->sc_K;
+    }
+    p.M = M; p.K = K; p.N = n_w; p.geglu = a->geglu;
+    p.A = (const bf16_t*)a->A; p.W = (const bf16_t*)a->W; p.lda = a->lda ? a->lda : width;
+    if (a->A2) {
+        if (a->C1 <= 0 || a->C1 >= width || a->C1 % 8) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: C1 must be a multiple of 8 inside the A rows");
+        p.A2 = (const bf16_t*)a->A2; p.C1 = a->C1; p.lda2 = a->lda2 ? a->lda2 : width - a->C1;
+        if (p.lda < a->C1 || p.lda2 < width - a->C1) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: lda / lda2 below the width of their source");
+        if (p.lda2 % 8 || ((size_t)a->A2 & 15)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: the second source needs 16-byte rows");
+    } else if (p.lda < width) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: lda below the width of the A rows");
+    if (p.lda % 8 || ((size_t)a->A & 15) || ((size_t)a->W & 15)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: A and W need 16-byte rows");
+    p.bias = a->bias; p.residual = (const bf16_t*)a->residual; p.out = a->out; p.out_mode = a->out_mode; p.out_dtype = a->out_dtype;
+    p.ldc = a->ldc ? a->ldc : n_out; p.ldr = a->ldr ? a->ldr : n_out;
+    if (a->out_mode == OUT_BF16 && (p.ldc < n_out || (a->residual && p.ldr < n_out))) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: ldc / ldr below N");
+    if (a->out_mode != OUT_BF16 && (a->residual || a->geglu || a->rowbias)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: residual / GEGLU / row bias need 16-bit row-major output");
+    // (the direct epilogue stores 4 columns = 8 bytes at a time and reads bias vectors of 16 bytes)
+    if (((size_t)a->out & 7) || ((size_t)a->residual & 7) || ((size_t)a->bias & 15))
+        GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: out / residual need 8-byte, bias 16-byte alignment");
+    if (a->rowbias) {
+        if (a->geglu) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: no row bias with GEGLU");
+        p.rowbias = a->rowbias; p.ld_rowbias = a->ld_rowbias ? a->ld_rowbias : n_out;
+        if (p.ld_rowbias < n_out || p.ld_rowbias % 4 || ((size_t)a->rowbias & 15)) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: ld_rowbias below N or rows not 16-byte aligned");
+    }
+    if (a->out_mode == OUT_BF16_T) {
+        if (a->tokens <= 0 || M % a->tokens || a->ldt < a->tokens) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_test: tokens must divide M, ldt >= tokens");
+        p.tokens_per_batch = a->tokens; p.ldt = a->ldt;
+    }
+    p.colstat_unit = a->colstat_unit;      // (asks the planner only: no statistics pointer is ever set here)
+    if (a->ws && a->ws_bytes) { p.splitk_ws = (float*)a->ws; p.splitk_ws_bytes = a->ws_bytes; }
+    return 0;
+}
+int gyre_op_gemm_test(void* st, const gyre_gemm_test_args* a) {
+    GemmParams p;
+    TRY(gemm_test_problem(p, a, true));
+    p.colstat_unit = 0;
+    // the plan the query reports is the plan that runs: no silent fall-back to an unsplit configuration for want of slab space
+    const GemmPlan pl = gemm_plan(p);
+    if (pl.splits > 1 && (!p.splitk_ws || p.splitk_ws_bytes < pl.ws_bytes))
+        GYRE_FAIL(GYRE_ERR_WORKSPACE, "gemm_test: the plan runs in K slices and needs ws_bytes of slab space in ws (gyre_debug_gemm_plan)");
+    return launch_gemm((hipStream_t)st, p, pl);
+}
+int gyre_debug_gemm_plan(const gyre_gemm_test_args* a, int32_t* out) {
+    if (!out) GYRE_FAIL(GYRE_ERR_INVALID, "gemm_plan: null output");
+    GemmParams p;
+    TRY(gemm_test_problem(p, a, false));
+    const GemmPlan pl = gemm_plan(p);
+    int nst = 0, uni = 0;
+    gemm_plan_loop_form(p, pl, &nst, &uni);
+    out[0] = pl.cfg; out[1] = pl.splits; out[2] = (int32_t)(pl.ws_bytes & 0xffffffffu); out[3] = (int32_t)(pl.ws_bytes >> 32);
+    out[4] = pl.w_block ? 1 : 0; out[5] = pl.colstat_rows; out[6] = pl.rowstat_parts; out[7] = pl.ln_fold ? 1 : 0;
+    out[8] = pl.per_sample_w ? 1 : 0; out[9] = pl.shortcut_fold ? 1 : 0; out[10] = nst; out[11] = uni;
+    return 0;
+}
+/* (id, bm, bn, kernel family) of every GEMM tile configuration (at most cap ints are written); returns the number of configurations */
+int gyre_debug_gemm_tiles(int32_t* out, int cap) { return gemm_tile_table(out, out ? cap : 0); }
 int gyre_op_ln_linear(void* st, const void* x, int M, int K, const float* gamma, const float* beta, float eps, const void* w,
                       int N, const float* bias, int geglu, int qkv_tokens, void* vt_out, int ldt, const float* row_parts,
                       int n_parts, void* ws, size_t ws_bytes, void* y) {

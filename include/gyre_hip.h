@@ -357,6 +357,47 @@ int gyre_debug_gemm_ablation(int bits);
 int gyre_debug_ln_linear_folds(int M, int K, int N, int geglu);
 /* Shape query, no device: 1 when gyre_op_groupnorm runs the one-launch two-pass kernel for this shape (C1 = C for one source). */
 int gyre_debug_gn_uses_small(int HW, int C, int C1, int groups);
+/* Tests / tuning only: one GEMM / implicit-GEMM 3x3 convolution launch described field by field, for the inputs the model runtime
+ * produces and no gyre_op_* entry can express (tests/test_gpu_gemm_exact.py).  Zero-initialise, then fill in:
+ *   conv = 0: out[M][ldc] = (A[M][lda] | A2[M][lda2]) W[N][K]^T, the sources split at column C1 of K (A2 = NULL: one source, C1 ignored);
+ *             geglu = 1: W holds 2 N_out rows interleaved in 16-row value / gate groups (gyre_op_repack_linear_weight), N = N_out.
+ *   conv = 1: 3x3 convolution of the NHWC image A[B][Hi][Wi][lda] (| A2 [..][lda2], split at channel C1 of Cin), W [N][3][3][Cin]:
+ *             stride 1 / 2; pad = 1 (all sides) or 0 (one zero row / column below and right: the (0,1,0,1) pad of a downsampler);
+ *             ups = 1: nearest 2x upsample first, of logical size Hup x Wup (0 = 2 Hi x 2 Wi; 2 Hi - 1 / 2 Wi - 1 crops the last row /
+ *             column); wrap bit 0 / 1: circular instead of zero padding along x / y.  M, K are derived (B Ho Wo, 9 Cin).
+ *   epilogue: + bias[N] (GEGLU: [2 N_out] interleaved) + rowbias[row / rows_per_sample][ld_rowbias] + residual[M][ldr], one rounding.
+ *   out_mode = 0: 16-bit rows [M][ldc]; 1: NCHW of out_dtype (GYRE_F32 / BF16 / F16; convolutions); 2: transposed,
+ *             out[(b N + col) ldt + tok] with tokens rows per b (linear).  ws / ws_bytes: split-K slab space (may be NULL).
+ * lda / lda2 / ldc / ldr = 0 mean the logical widths.  The tile config is the planner's, or the one forced through
+ * gyre_debug_force_gemm_cfg.  A plan in K slices needs its slab space in ws (gyre_debug_gemm_plan says how much): too little is
+ * GYRE_ERR_WORKSPACE, never a silent run of another configuration.  Bad sizes, strides below the logical width, a missing pointer: GYRE_ERR_INVALID and no launch; a
+ * form the chosen kernel does not have: GYRE_ERR_UNSUPPORTED and no launch. */
+typedef struct gyre_gemm_test_args {
+    int32_t conv, M, K, N, geglu;
+    int32_t B, Hi, Wi, Cin, stride, pad, ups, Hup, Wup, wrap;
+    int32_t C1, lda, lda2, ldc, ldr;
+    int32_t rows_per_sample, ld_rowbias, samples;
+    int32_t out_mode, out_dtype, tokens, ldt;
+    int32_t colstat_unit;      /* gyre_debug_gemm_plan only: the channel unit its column-statistics answer is for (0: none) */
+    const void* A; const void* A2; const void* W;
+    const float* bias; const float* rowbias; const void* residual;
+    void* out; void* ws; size_t ws_bytes;
+    /* the 1x1 shortcut folded into a stride-1 / pad-1 convolution as extra K steps: sc_K more channels of a second image pair
+     * sc_A[B][Hi][Wi][sc_lda] (| sc_A2 [..][sc_lda2], split at sc_C1; NULL: one source) behind the conv's; W then holds
+     * [N][9 Cin + sc_K] rows (the conv's followed by the shortcut's) and bias the sum of the two.  sc_K = 0: none. */
+    const void* sc_A; const void* sc_A2; int32_t sc_K, sc_C1, sc_lda, sc_lda2;
+} gyre_gemm_test_args;
+int gyre_op_gemm_test(void* stream, const gyre_gemm_test_args* a);
+/* Shape query, no device: what gyre_op_gemm_test would launch for `a` under the calling thread's planner state (forced config, tuning
+ * switches, scratch buffers).  Pointers are looked at for NULL and for their 16-byte alignment only.  Returns the status the
+ * argument check gives; out[12] = tile config, K slices, split-K slab bytes (low / high 32 bits), blocked weights, column-statistics
+ * rows (for colstat_unit), row-statistics parts, folded LayerNorm, per-sample weights, folded shortcut, and for the 8-wave
+ * tile configs the LDS ring depth (else 0), for convolutions on the 4- and 8-wave configs whether the K loop takes the uniform-tap
+ * form (else 0; the other kernels have no tap forms).  out[9] needs the sc_* fields of the folded shortcut. */
+int gyre_debug_gemm_plan(const gyre_gemm_test_args* a, int32_t* out);
+/* The tile-config table: out[4 i ..] = id, rows, columns, kernel family (0 register-staged 4-wave, 1 LDS-DMA 8-wave, 2 pipelined,
+ * 3 A-resident, 4 small-problem) of the i-th configuration; at most cap ints are written.  Returns the number of configurations. */
+int gyre_debug_gemm_tiles(int32_t* out, int cap);
 
 /* ---- batch-invariant mode ------------------------------------------------
  * The reference asserts that an image does not depend on what shares its batch (tests/batch_independance.py:15-27)

@@ -51,15 +51,17 @@ def report(name, got, ref, tol):
 
 def check_bound(name, got, ref, bound, k=4.0, tiny=0.0, dims=None, hdt=None, enforce=True):
     """Element-wise  |got - ref| <= k u bound + u |ref| + tiny  (u = unit roundoff of the 16-bit storage, HDT: 2^-8 bf16, 2^-11
-    fp16); bound = the float64 absolute-value form of the same computation, tiny an absolute floor (scalar or tensor).  Prints the
+    fp16; 2^-24 for hdt = torch.float32, an output that is stored unrounded); bound = the float64 absolute-value form of the same
+    computation, tiny an absolute floor (scalar or tensor).  Prints the
     worst ratio |got - ref| / tolerance and where it is (dims names the axes), pass or fail; NaN / inf in got fails.  hdt: judge for
     that storage type instead of the flavour under test (host self-tests of an error model); enforce = False: return the ratio
     without asserting (seeded mistakes that are meant to exceed it)."""
     hdt = HDT if hdt is None else hdt
-    u = 2.0 ** -8 if hdt == torch.bfloat16 else 2.0 ** -11
+    u = 2.0 ** -8 if hdt == torch.bfloat16 else 2.0 ** -24 if hdt == torch.float32 else 2.0 ** -11
     g, r, b = got.double().cpu(), ref.double().cpu(), bound.double().cpu()
     tiny = tiny.double().cpu() if torch.is_tensor(tiny) else tiny
-    floor = 2.0 ** -134 if hdt == torch.bfloat16 else 2.0 ** -25      # half the smallest subnormal: the output's own rounding floor
+    # half the smallest subnormal: the output's own rounding floor
+    floor = 2.0 ** -134 if hdt == torch.bfloat16 else 2.0 ** -150 if hdt == torch.float32 else 2.0 ** -25
     tol = k * u * b + u * r.abs() + tiny + floor
     ratio = ((g - r).abs() / tol.clamp_min(1e-300)).nan_to_num(nan=float("inf"))
     flat = int(ratio.flatten().argmax())
