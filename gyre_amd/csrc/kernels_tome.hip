@@ -211,6 +211,7 @@ int launch_tome_merge(hipStream_t st, const TomeParams& p) {
     const int half = p.N / 2, r = tome_effective_r(p.N, p.r);
     if (p.B <= 0 || p.N < 2 || p.C <= 0 || p.C % 8 || p.C > 1536 || p.ldk % 8 || p.ldv % 8 || r <= 0)
         GYRE_FAIL(-1, "tome: needs N >= 2, C a multiple of 8 (<= 1536), 16-byte aligned rows and r > 0");
+    if (half % 4) GYRE_FAIL(-1, "tome: N / 2 must be a multiple of 4");       // (before the first launch: a refusal runs nothing)
     if (half > 16384) GYRE_FAIL(-6, "tome: more than 32768 tokens per sample are not supported (sort runs in one workgroup's LDS)");
     if (!p.ws || p.ws_bytes < tome_workspace_bytes(p.B, p.N, p.C)) GYRE_FAIL(-4, "tome: workspace too small");
     if (p.ldvt < p.N - r) GYRE_FAIL(-1, "tome: ldvt smaller than the merged token count");
@@ -233,7 +234,6 @@ int launch_tome_merge(hipStream_t st, const TomeParams& p) {
     g.A = a; g.lda = p.C; g.mode = GEMM_LINEAR; g.W = b; g.K = p.C; g.N = half; g.M = half;
     g.out = scores; g.ldc = lds; g.out_mode = OUT_BF16;
     g.batch = p.B; g.bsA = (size_t)half * p.C; g.bsW = (size_t)half * p.C; g.bsC = (size_t)half * lds;
-    if (half % 4) GYRE_FAIL(-1, "tome: N / 2 must be a multiple of 4");
     int rc = launch_gemm(st, g);
     if (rc) return rc;
     GyreProfScope prof_(KC_OTHER, st, 0, (double)p.B * half * half * 2.0 + (double)p.B * p.N * p.C * 6.0);

@@ -203,6 +203,42 @@ int gyre_op_tome_merge(void* st, const void* k, int ldk, const void* v, int ldv,
     p.order_out = order_out; p.node_idx_out = node_idx_out;
     return launch_tome_merge((hipStream_t)st, p);
 }
+int gyre_op_tome_merge_ex(void* st, const void* k, int ldk, const void* v, int ldv, int B, int N, int C, int r, void* ws, size_t wsb,
+                          void* k_out, void* vt_out, int ldvt, int32_t* order_out, int32_t* node_idx_out, int32_t* dstlist_out,
+                          void* vrows_out) {
+    if (!k || !v || !ws || !k_out || !vt_out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    TomeParams p;
+    p.k = (const bf16_t*)k; p.ldk = ldk; p.v = (const bf16_t*)v; p.ldv = ldv; p.B = B; p.N = N; p.C = C; p.r = r;
+    p.k_out = (bf16_t*)k_out; p.vt_out = (bf16_t*)vt_out; p.ldvt = ldvt; p.ws = ws; p.ws_bytes = wsb;
+    p.order_out = order_out; p.node_idx_out = node_idx_out; p.dstlist_out = dstlist_out; p.vrows_out = (bf16_t*)vrows_out;
+    return launch_tome_merge((hipStream_t)st, p);
+}
+int gyre_op_tome_unmerge(void* st, const void* dy, int B, int N, int C, int r, const int32_t* order, const int32_t* dstlist,
+                         int32_t* inv_scratch, void* dx, int ldx) {
+    if (!dy || !order || !dstlist || !inv_scratch || !dx) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (B < 1 || N < 2 || C < 8 || ldx < C) GYRE_FAIL(GYRE_ERR_INVALID, "tome_unmerge: needs B >= 1, N >= 2, C >= 8 and ldx >= C");
+    return launch_tome_unmerge((hipStream_t)st, (const bf16_t*)dy, B, N, C, r, order, dstlist, inv_scratch, (bf16_t*)dx, ldx);
+}
+// The time-embedding chain (kernels_elem.hip), fp32 rows.  Odd dim has no defined result in k_timestep_embedding (diffusers
+// zero-pads the last column there): refused here.
+int gyre_op_timestep_embedding(void* st, const int64_t* t, int B, int dim, int flip, float shift, float* out) {
+    if (!t || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (B < 1 || dim < 2 || dim % 2) GYRE_FAIL(GYRE_ERR_INVALID, "timestep_embedding: needs B >= 1 and an even dim");
+    return launch_timestep_embedding((hipStream_t)st, t, B, dim, flip, shift, out);
+}
+int gyre_op_rowvec_linear(void* st, float* x, int B, int K, const void* w, const float* bias, int N, int act_in_silu, float* out,
+                          int ldo) {
+    if (!x || !w || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (B < 1 || K < 8 || K % 8 || N < 1 || ldo < N) GYRE_FAIL(GYRE_ERR_INVALID, "rowvec_linear: needs B, N >= 1, K a multiple of 8 and ldo >= N");
+    return launch_rowvec_linear((hipStream_t)st, x, B, K, (const bf16_t*)w, bias, N, act_in_silu, out, ldo);
+}
+int gyre_op_timestep_linear(void* st, const int64_t* t, int B, int dim, int flip, float shift, float* emb_scratch, const void* w,
+                            const float* bias, int N, float* out, int ldo) {
+    if (!t || !w || !out || ((B > 4 || dim % 8) && !emb_scratch)) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (B < 1 || dim < 8 || dim % 8 || N < 1 || ldo < N)
+        GYRE_FAIL(GYRE_ERR_INVALID, "timestep_linear: needs B, N >= 1, dim a multiple of 8 (the Linear's K) and ldo >= N");
+    return launch_timestep_linear((hipStream_t)st, t, B, dim, flip, shift, emb_scratch, (const bf16_t*)w, bias, N, out, ldo);
+}
 
 int gyre_unet_set_context(gyre_unet* h, void* st, const void* ctx, int cdt, int B, int S) {
     if (!h || !ctx) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");

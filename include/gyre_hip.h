@@ -543,6 +543,26 @@ size_t gyre_op_tome_workspace(int B, int N, int C);
 int gyre_op_tome_merge(void* stream, const void* k, int ldk, const void* v, int ldv, int B, int N, int C, int r,
                        void* workspace, size_t workspace_bytes, void* k_out, void* vt_out, int ldvt,
                        int32_t* order_out, int32_t* node_idx_out);
+/* gyre_op_tome_merge plus two optional outputs: dstlist_out [B,N/2] (int32, dev; entry k < r = the b token the k-th ranked a
+ * token was merged into) and vrows_out [B,N-r,C] (the merged values row-major, what the backward pass reads). */
+int gyre_op_tome_merge_ex(void* stream, const void* k, int ldk, const void* v, int ldv, int B, int N, int C, int r,
+                          void* workspace, size_t workspace_bytes, void* k_out, void* vt_out, int ldvt,
+                          int32_t* order_out, int32_t* node_idx_out, int32_t* dstlist_out, void* vrows_out);
+/* Adjoint of the merge for one merged tensor: dy[B,N-r,C] -> dx[B,N,ldx]; every original token receives the gradient of the row
+ * it went into, divided by that row's token count.  order / dstlist as gyre_op_tome_merge_ex returned them, r = the EFFECTIVE r
+ * (1 <= r <= N / 2, not clipped here), inv_scratch [B,N/2] int32. */
+int gyre_op_tome_unmerge(void* stream, const void* dy, int B, int N, int C, int r, const int32_t* order, const int32_t* dstlist,
+                         int32_t* inv_scratch, void* dx, int ldx);
+/* The time-embedding chain, fp32 rows.  timestep_embedding: out[B,dim] = the diffusers sinusoidal embedding of t[B] (int64, dev),
+ * [cos | sin] when flip, exponent -ln(10000) i / (dim / 2 - shift); dim even.  rowvec_linear: out[B,N] (row stride ldo) =
+ * f(x[B,K]) w[N,K]^T + bias, w in 16-bit storage row-major, f = SiLU when act_in_silu (for B > 4 it is applied to x IN PLACE,
+ * for B <= 4 x is left as it is); K % 8 == 0.  timestep_linear: rowvec_linear of the embedding (K = dim, dim % 8 == 0), one
+ * launch for B <= 4; emb_scratch [B,dim] f32 is needed above that. */
+int gyre_op_timestep_embedding(void* stream, const int64_t* t, int B, int dim, int flip, float shift, float* out);
+int gyre_op_rowvec_linear(void* stream, float* x, int B, int K, const void* w, const float* bias, int N, int act_in_silu,
+                          float* out, int ldo);
+int gyre_op_timestep_linear(void* stream, const int64_t* t, int B, int dim, int flip, float shift, float* emb_scratch,
+                            const void* w, const float* bias, int N, float* out, int ldo);
 /* The cross-attention block of a transformer block as ONE launch (round 6, kernels_xattn.hip; the model runs it for the attn2 module of
  * diffusers' BasicTransformerBlock at SD1.x's 64x64 level): out = softmax(LayerNorm(x) Wq^T . K^T) V Wo^T + bo + x and, if row_stats
  * is not NULL, per row the (sum, sum of squares) of the rounded outputs.  x [M][C] = the rows BEFORE the LayerNorm (M = B * tokens),
