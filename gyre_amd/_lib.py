@@ -79,6 +79,12 @@ class GemmTestArgs(C.Structure):
                [("sc_A", C.c_void_p), ("sc_A2", C.c_void_p)] + [(n, C.c_int32) for n in ("sc_K", "sc_C1", "sc_lda", "sc_lda2")]
 
 
+class LoraPair(C.Structure):
+    """gyre_lora_pair (include/gyre_hip.h): one up / down factor pair of a LoRA, device pointers."""
+    _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("dtype", C.c_int), ("rank", C.c_int), ("scale", C.c_float)]
+
+
+LORA_MAX_PAIRS = 8
 _vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
 _SIGS = {
     "gyre_abi_version": (C.c_int, []),
@@ -90,6 +96,7 @@ _SIGS = {
     "gyre_unet_num_params": (_i, [_vp]),
     "gyre_unet_param_key": (C.c_char_p, [_vp, _i]),
     "gyre_unet_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
+    "gyre_unet_set_weight_lora": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _i, C.POINTER(LoraPair), _vp]),
     "gyre_unet_finalize": (_i, [_vp, _vp]),
     "gyre_unet_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "gyre_unet_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
@@ -170,8 +177,10 @@ _SIGS = {
     "gyre_op_conv3x3_shortcut": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "gyre_op_conv3x3_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i]),
     "gyre_op_repack_conv_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gyre_op_repack_conv_weight_scaled": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "gyre_op_repack_linear_weight": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "gyre_op_repack_bias": (_i, [_vp, _vp, _i, _i, _vp]),
+    "gyre_op_repack_lora": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(LoraPair), _vp]),
     "gyre_op_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_qkv": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i]),
     "gyre_op_attention_ex": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),

@@ -92,6 +92,20 @@ int launch_repack_conv(hipStream_t st, const void* w, int dtype, int O, int I, i
 int launch_repack_linear(hipStream_t st, const void* w, int dtype, int O, int I, int geglu_interleave, bf16_t* out);
 int launch_cast_f32(hipStream_t st, const void* w, int dtype, size_t n, int geglu_interleave, float* out, float scale = 1.f);
 int launch_copy_probe(hipStream_t st, const void* src, void* dst, size_t bytes);
+// fused LoRA delta-merge repack (kernels_lora.hip): launch_repack_conv / _linear of  base + sum_j s[j] up[j] down[j]  (factors in
+// PyTorch layout, up [O][rank], down [rank][I][KH][KW], each pair in its own dtype), summed in fp32 in front of the one rounding;
+// n = 0 gives the plain repack's bits.  Operation order: header of kernels_lora.hip.
+#define GYRE_LORA_MAX_PAIRS 8
+struct LoraArgs {
+    const void* up[GYRE_LORA_MAX_PAIRS];
+    const void* down[GYRE_LORA_MAX_PAIRS];
+    int dtype[GYRE_LORA_MAX_PAIRS];
+    int rank[GYRE_LORA_MAX_PAIRS];
+    float s[GYRE_LORA_MAX_PAIRS];
+    int n = 0;
+};
+int launch_repack_lora(hipStream_t st, const void* base, int base_dtype, int O, int I, int KH, int KW, int Ipad, int geglu_interleave,
+                       float scale_p, const LoraArgs& la, bf16_t* out);
 
 // ---- T2I-adapter element-wise ops (kernels_t2i.hip) ----------------------------
 // x NCHW [B][c][H][W] of a runtime dtype (H, W multiples of 8) -> y NHWC storage [B][H/8][W/8][64 c], channel c*64 + dy*8 + dx

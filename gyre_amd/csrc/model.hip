@@ -58,7 +58,7 @@ static const char* kclass_name(int k) {
         "k_gemm4s<192, 320, 2, 2, 1", "k_gemm4s<192, 320, 2, 2, 0", "k_gemm4s<256, 256, 2, 2, 1", "k_gemm4s<256, 256, 2, 2, 0",
         "k_gemm4s<128, 320, 2, 2, 1", "k_gemm4s<128, 320, 2, 2, 0", "k_gemm4s<128, 256, 2, 2, 1", "k_gemm4s<128, 256, 2, 2, 0", "k_gemm4s<256, 320, 4, 2, 1", "k_gemm4s<256, 320, 4, 2, 0",
         "k_attn", "k_gn_partial+k_gn_finalize", "k_gn_apply", "k_layernorm", "other", "k_attn_bwd", "k_gn_bwd+k_ln_bwd",
-        "k_splitk_reduce", "k_gemm_ar", "k_gemm_sm", "k_xattn"};
+        "k_splitk_reduce", "k_gemm_ar", "k_gemm_sm", "k_xattn", "k_repack_lora"};
     return (k >= 0 && k < KC_COUNT) ? n[k] : "?";
 }
 
@@ -89,6 +89,15 @@ int gyre_unet_set_weight(gyre_unet* h, const char* key, const void* p, int dtype
     h->finalized = false;
     h->invalidate_contexts();
     return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
+}
+int gyre_unet_set_weight_lora(gyre_unet* h, const char* key, const void* base, int base_dtype, const int64_t* shape, int ndim,
+                              int n_pairs, const gyre_lora_pair* pairs, void* st) {
+    if (!h || !key || !base || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    bool was_set = false;
+    TRY(h->store.set_weight_lora(key, base, base_dtype, shape, ndim, n_pairs, pairs, (hipStream_t)st, &was_set));
+    if (!was_set) h->finalized = false;          // a key set before leaves a finalized handle finalized: no re-upload of the rest
+    h->invalidate_contexts();                    // the cached K / V projections of the text contexts were made with the old weights
+    return 0;
 }
 int gyre_unet_finalize(gyre_unet* h, void* st) {
     if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
@@ -615,9 +624,26 @@ int gyre_op_repack_conv_weight(void* st, const float* w, int Cout, int Cin, int 
     if (!w || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     return launch_repack_conv((hipStream_t)st, w, 0, Cout, Cin, KH, KW, Cin_pad, (bf16_t*)out);
 }
+int gyre_op_repack_conv_weight_scaled(void* st, const void* w, int dtype, int Cout, int Cin, int KH, int KW, int Cin_pad, float scale,
+                                      void* out) {
+    if (!w || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (dtype < 0 || dtype > 2 || Cout < 1 || Cin < 1 || KH < 1 || KW < 1 || Cin_pad < Cin) GYRE_FAIL(GYRE_ERR_INVALID, "repack_conv_weight_scaled: bad dtype or sizes");
+    return launch_repack_conv((hipStream_t)st, w, dtype, Cout, Cin, KH, KW, Cin_pad, (bf16_t*)out, scale);
+}
 int gyre_op_repack_linear_weight(void* st, const float* w, int O, int I, int geglu, void* out) {
     if (!w || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     return launch_repack_linear((hipStream_t)st, w, 0, O, I, geglu, (bf16_t*)out);
+}
+int gyre_op_repack_lora(void* st, const void* base, int base_dtype, int O, int I, int KH, int KW, int I_pad, int geglu, float scale_p,
+                        int n_pairs, const gyre_lora_pair* pairs, void* out) {
+    if (!base || !out || (n_pairs > 0 && !pairs)) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (n_pairs < 0 || n_pairs > GYRE_LORA_MAX_PAIRS) GYRE_FAIL(GYRE_ERR_INVALID, "repack_lora: 0 to 8 LoRA pairs per call");
+    LoraArgs la;
+    la.n = n_pairs;
+    for (int j = 0; j < n_pairs; ++j) {
+        la.up[j] = pairs[j].up; la.down[j] = pairs[j].down; la.dtype[j] = pairs[j].dtype; la.rank[j] = pairs[j].rank; la.s[j] = pairs[j].scale;
+    }
+    return launch_repack_lora((hipStream_t)st, base, base_dtype, O, I, KH, KW, I_pad, geglu, scale_p, la, (bf16_t*)out);
 }
 int gyre_op_repack_bias(void* st, const float* b, int n, int geglu, float* out) {
     if (!b || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");

@@ -257,6 +257,50 @@ struct Store {
         ++weights_version;
         return 0;
     }
+    // set_weight of  base + sum_j scale_j up_j down_j  (per-request LoRA, reference gyre/pipeline/lora.py:96-160) for one matrix /
+    // conv key: the low-rank sum joins the repack pass in fp32 (launch_repack_lora), nothing is multiplied out or copied by the
+    // caller.  Same key / shape rules as set_weight; n_pairs == 0 writes set_weight's bits (how a LoRA is taken off again).  The
+    // derived copies (wt / ln / ar / blk / sc caches) share the one version counter and are refreshed by the next forward.
+    // *was_set: whether the key had been set before (a first set leaves the handle un-finalized, a later one does not).
+    int set_weight_lora(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, int n_pairs,
+                        const gyre_lora_pair* pairs, hipStream_t st, bool* was_set) {
+        auto it = by_key.find(key);
+        if (it == by_key.end()) GYRE_FAIL(GYRE_ERR_KEY, std::string("unknown weight key: ") + key);
+        Param& p = *it->second;
+        if (p.kind == PK_VEC || p.kind == PK_VEC_GEGLU) GYRE_FAIL(GYRE_ERR_INVALID, std::string("a LoRA applies to matrices and convolutions, not to the vector ") + key);
+        if (dtype < 0 || dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
+        bool ok = (int)p.shape.size() == ndim;
+        for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
+        if (!ok) {
+            std::string m = std::string("shape mismatch for ") + key + ": expected [";
+            for (auto d : p.shape) m += std::to_string(d) + ",";
+            m += "] got [";
+            for (int i = 0; i < ndim; ++i) m += std::to_string(shape[i]) + ",";
+            GYRE_FAIL(GYRE_ERR_KEY, m + "]");
+        }
+        if (n_pairs < 0 || n_pairs > GYRE_LORA_MAX_PAIRS || (n_pairs > 0 && !pairs)) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: 0 to 8 LoRA pairs per call");
+        LoraArgs la;
+        la.n = n_pairs;
+        for (int j = 0; j < n_pairs; ++j) {
+            if (!pairs[j].up || !pairs[j].down) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: null factor");
+            if (pairs[j].dtype < 0 || pairs[j].dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: bad factor dtype");
+            if (pairs[j].rank < 1) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: rank must be >= 1");
+            la.up[j] = pairs[j].up; la.down[j] = pairs[j].down; la.dtype[j] = pairs[j].dtype; la.rank[j] = pairs[j].rank; la.s[j] = pairs[j].scale;
+        }
+        const int O = (int)p.shape[0], I = (int)p.shape[1];
+        if (p.kind == PK_CONV3) {
+            TRY(launch_repack_lora(st, src, dtype, O, I, 3, 3, p.i_pad, 0, 1.f, la, (bf16_t*)p.dev));
+        } else if (p.kind == PK_MAT_GEGLU) {
+            if (p.i_pad != I) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "geglu weight with padded K");
+            TRY(launch_repack_lora(st, src, dtype, O, I, 1, 1, I, 1, 1.f, la, (bf16_t*)p.dev));
+        } else {
+            TRY(launch_repack_lora(st, src, dtype, O, I, 1, 1, p.i_pad, 0, p.scale, la, (bf16_t*)p.dev));
+        }
+        if (was_set) *was_set = p.set;
+        p.set = true;
+        ++weights_version;
+        return 0;
+    }
     int finalize() {
         for (auto& p : params)
             if (!p->set) GYRE_FAIL(GYRE_ERR_INCOMPLETE, "weight not set: " + p->key);

@@ -102,6 +102,7 @@ class GyreUnifiedPipeline:
         self._shard_devices: list = []       # engine option "shard_devices": fan one request over these device slots
         self._shard_bit_exact = False
         self._executor = None
+        self._lora_uploads: list = []        # LoraFactors of the last four LoRA tensors mappings seen (_lora_factors)
         self.clip_default_config = CG.ClipGuidanceConfig()
 
     # ---- what PipelineWrapper / DiffusionPipelineWrapper touch -----------------------------------------------------------
@@ -311,6 +312,27 @@ class GyreUnifiedPipeline:
         return dict(clip_guidance_scale=scale, clip_config=cfg,
                     clip_text_embeddings=feats.repeat_interleave(num_images_per_prompt, dim=0))
 
+    def _lora_factors(self, tensors):
+        """The uploaded factors of one LoRA tensors mapping (lora.upload_factors), remembered per mapping OBJECT: the reference's
+        manager keeps a loaded LoRA's dict alive and hands the same object to every request that names it, so its factors go to
+        the device once.  Identity-keyed, per UNet object whose shapes the upload was checked against (the entry keeps the mapping
+        referenced, its address cannot be recycled), the four most
+        recently used sets are kept."""
+        dev = self.unet.device
+        cache = self._lora_uploads                          # [(tensors mapping, unet the shapes were checked against, LoraFactors)]
+        for i, (src, net, f) in enumerate(cache):
+            if src is tensors and net is self.unet and f.device == dev:
+                cache.append(cache.pop(i))
+                return f
+        if LR.detect_lora_type(tensors) == "cloneofsimo":
+            raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")
+        if dev.type != "cuda":
+            self.unet._sync(dev)                            # raises: the native UNet has no CPU path
+        f = LR.upload_factors(self.unet, tensors, dev)
+        cache.append((tensors, self.unet, f))
+        del cache[:-4]
+        return f
+
     def _hints(self, hint_images, mask_image) -> list:
         """The reference's hint loop (unified_pipeline.py:1994-2047) for what is native: every hint image needs exactly one model
         from the hintset manager and that model must be a GyreHipT2IAdapter.  Depth hints routed to a depth UNet and ControlNet
@@ -416,13 +438,20 @@ class GyreUnifiedPipeline:
             if u is None:
                 continue
             LR.remove_lora_from_model(u)                    # the reference strips leftovers on every call (:2190-2200)
+            LR.detach_loras(u)                              # ... and what the previous request attached on the device path
             if hasattr(u, "set_tome"):                      # the reference patches ToMe into self.unet only (:1580-1584)
                 u.set_tome(self._tome if u is self.unet else 0)
         if lora:
+            specs = []
             for i, spec in enumerate(lora if isinstance(lora, (list, tuple)) else [lora]):
                 tensors, weights = (spec if isinstance(spec, (list, tuple)) else (spec, {}))
                 scale = (weights or {}).get("unet", 1.0) if isinstance(weights, dict) else 1.0
-                LR.apply_lora(self.unet, tensors, f"request-{i}", scale)
+                specs.append((tensors, f"request-{i}", scale))
+            if hasattr(self.unet, "_sync"):                 # native UNet: merged on the device, each touched weight repacked once
+                LR.attach_loras(self.unet, [(self._lora_factors(t), lid, sc) for t, lid, sc in specs])
+            else:
+                for t, lid, sc in specs:
+                    LR.apply_lora(self.unet, t, lid, sc)
         steps_seen = []
 
         def cb(info):

@@ -22,6 +22,15 @@ inside the repack kernel.  Writing the sum back into a bf16 / fp16 master parame
 master's grid: a delta element below half an ulp of W (|delta| < 0.2-0.4 % of |W|, typical for LoRA) would vanish,
 which the reference's activation-space hook never does.  The master parameter also receives the (rounded) merged value,
 for ``state_dict()`` consumers only.
+
+Device path (``attach_lora`` / ``set_attached_scale`` / ``detach_loras``): the same map without the host.  The factors are kept
+as they come (never multiplied out), live on the module's device in their own dtype, and for each TOUCHED weight one
+``gyre_unet_set_weight_lora`` call hands the untouched master parameter and the factor pairs to the fused repack kernel
+(csrc/kernels_lora.hip): base + sum_j s_j up_j down_j in fp32, rounded once.  Untouched weights are not uploaded again, and
+detaching re-issues the touched keys with zero pairs, which restores the base bits.  On this path the master parameters are
+NEVER written: ``state_dict()`` keeps showing the base weights while a LoRA is attached - which is what the reference's hooks do
+(they leave ``module.weight`` alone).  The two paths do not stack: attaching onto a host-merged module, or merging into a module
+with attached LoRAs, is a ValueError.
 """
 from __future__ import annotations
 
@@ -68,11 +77,10 @@ def lora_delta(up: Tensor, down: Tensor, alpha: Optional[Tensor] = None) -> Tens
     raise ValueError(f"Can't apply LoRA of rank-{down.ndim} tensors")
 
 
-def _targets(unet: torch.nn.Module, lora: Mapping[str, Tensor]) -> Dict[str, Tensor]:
-    """weight-parameter name -> unscaled delta"""
+def _pairs(unet: torch.nn.Module, lora: Mapping[str, Tensor]):
+    """The key rules of both paths: yields (weight-parameter name, up, down, alpha or None) per targeted weight."""
     params = dict(unet.named_parameters())
     kind = detect_lora_type(lora)
-    out: Dict[str, Tensor] = {}
     if kind == "cloneofsimo":
         raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")
     if kind == "kohya-ss":
@@ -87,9 +95,9 @@ def _targets(unet: torch.nn.Module, lora: Mapping[str, Tensor]) -> Dict[str, Ten
             mod = key[len("lora_unet_"):].split(".")[0]
             if mod not in flat:
                 raise RuntimeError(f"Couldn't find model for {key} when applying LoRA")
-            out[flat[mod]] = lora_delta(lora[key.replace(".lora_down.", ".lora_up.")], lora[key],
-                                        lora.get(key.replace(".lora_down.weight", ".alpha")))
-        return out
+            yield flat[mod], lora[key.replace(".lora_down.", ".lora_up.")], lora[key], \
+                lora.get(key.replace(".lora_down.weight", ".alpha"))
+        return
     for key in lora.keys():                                                   # diffusers attention-processor format
         if not key.endswith(".down.weight"):
             continue
@@ -98,7 +106,14 @@ def _targets(unet: torch.nn.Module, lora: Mapping[str, Tensor]) -> Dict[str, Ten
         name = fixed + ".weight"
         if name not in params:
             raise RuntimeError(f"Couldn't find model for {key} when applying LoRA")
-        out[name] = lora_delta(lora[key.replace(".down.weight", ".up.weight")], lora[key])
+        yield name, lora[key.replace(".down.weight", ".up.weight")], lora[key], None
+
+
+def _targets(unet: torch.nn.Module, lora: Mapping[str, Tensor]) -> Dict[str, Tensor]:
+    """weight-parameter name -> unscaled delta"""
+    out: Dict[str, Tensor] = {}
+    for name, up, down, alpha in _pairs(unet, lora):
+        out[name] = lora_delta(up, down, alpha)
     return out
 
 
@@ -143,6 +158,8 @@ def _rebuild(unet) -> None:
 def apply_lora(unet, lora: Mapping[str, Tensor], lora_id, scale: float = 1.0) -> int:
     """Merge one LoRA (a dict of tensors, e.g. safetensors.torch.load_file) under ``lora_id``.  Returns the number of
     weights touched."""
+    if (getattr(unet, "_lora_attached", None) or {"loras": {}})["loras"]:
+        raise ValueError("this module has attached (device-path) LoRAs: the two LoRA paths do not stack - detach_loras() first")
     deltas = _targets(unet, lora)
     st = _state(unet)
     params = dict(unet.named_parameters())
@@ -167,3 +184,168 @@ def remove_lora_from_model(unet) -> None:
     if st["loras"]:
         st["loras"].clear()
         _rebuild(unet)
+
+
+# ---- device path: factors stay factors, merged inside the repack kernel -------------------------------------------------
+class LoraFactors:
+    """One LoRA's factors on a device, as attach_lora keeps them: ``pairs[name] = (up, down, alpha / r)`` with up [O, r] and
+    down [r, I(, KH, KW)] contiguous in their own dtype.  ``source`` keeps the tensors mapping they were made from referenced
+    (an identity-keyed cache of uploads must not see its key's address recycled)."""
+
+    def __init__(self, pairs, device, source=None):
+        self.pairs, self.device, self.source = pairs, device, source
+
+    def to(self, device):
+        """These factors on ``device``: this object where they already are, a NEW one otherwise (an upload may be shared between
+        modules and devices - it is never changed in place)."""
+        if device == self.device:
+            return self
+        return LoraFactors({k: (u.to(device), d.to(device), s) for k, (u, d, s) in self.pairs.items()}, device, self.source)
+
+
+_FACTOR_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def upload_factors(unet, lora: Mapping[str, Tensor], device=None) -> LoraFactors:
+    """Parse ``lora`` (the key rules of apply_lora) and put its factors on ``device`` (default: the module's), each in its own
+    dtype; nothing is multiplied out.  Shapes are checked against the weights they target (ValueError)."""
+    device = torch.device(device) if device is not None else unet.device
+    params = dict(unet.named_parameters())
+    pairs = {}
+    for name, up, down, alpha in _pairs(unet, lora):
+        w = params[name]
+        if down.ndim not in (2, 4) or up.ndim != down.ndim:
+            raise ValueError(f"Can't apply LoRA of rank-{down.ndim} tensors")
+        if down.ndim == 4 and tuple(up.shape[2:]) != (1, 1):
+            raise ValueError("conv LoRA: the up projection must be 1x1")
+        r = down.shape[0]
+        if r < 1 or up.shape[1] != r:
+            raise ValueError(f"LoRA for {name}: up has rank {up.shape[1]}, down rank {r}")
+        if w.ndim != down.ndim or up.shape[0] != w.shape[0] or tuple(down.shape[1:]) != tuple(w.shape[1:]):
+            raise ValueError(f"LoRA for {name}: up {tuple(up.shape)} x down {tuple(down.shape)} does not give the weight's "
+                             f"shape {tuple(w.shape)}")
+        iscale = float(alpha) / r if alpha is not None else 1.0
+        fix = lambda t: (t if t.dtype in _FACTOR_DTYPES else t.to(torch.float32)).detach().to(device).contiguous()
+        pairs[name] = (fix(up), fix(down), iscale)
+    return LoraFactors(pairs, device, lora)
+
+
+def _attached(unet):
+    at = getattr(unet, "_lora_attached", None)
+    if at is None:
+        at = {"loras": {}}                       # id -> (LoraFactors, user scale), in attach order
+        unet._lora_attached = at
+    return at
+
+
+def _issue(unet, names) -> None:
+    """gyre_unet_set_weight_lora for each of ``names`` on the module's live handle: the untouched master parameter plus every
+    attached pair that hits the key (none: the base bits).  A module whose native copy is stale anyway (``_dirty``: after
+    ``.to(...)``) is left to ``_sync``, which re-applies the attached set behind its full upload."""
+    import ctypes as C
+    from . import _lib
+    names = list(names)
+    if not names:
+        return
+    if getattr(unet, "_handle", None) is not None and not unet._dirty:
+        at = _attached(unet)
+        params = dict(unet.named_parameters())
+        dev = unet._handle_device
+        L = unet._L()
+        for lid, (f, scale) in list(at["loras"].items()):       # this module's entry follows it to the handle's device
+            if f.device != dev:
+                at["loras"][lid] = (f.to(dev), scale)
+        # everything is checked before the first call, so a refusal leaves the native copy as it was: the kernel trusts these shapes
+        plan = {}
+        for name in names:                       # (scale 0 contributes nothing, as in the host merge)
+            w = params[name]
+            plan[name] = [(f.pairs[name], scale) for f, scale in at["loras"].values() if name in f.pairs and scale != 0]
+            if len(plan[name]) > _lib.LORA_MAX_PAIRS:
+                raise ValueError(f"{len(plan[name])} LoRAs hit {name}: at most {_lib.LORA_MAX_PAIRS} per weight")
+            for (up, down, _), _ in plan[name]:
+                if up.ndim != w.ndim or down.ndim != w.ndim or up.shape[0] != w.shape[0] or up.shape[1] != down.shape[0] \
+                        or tuple(down.shape[1:]) != tuple(w.shape[1:]) or not (up.is_contiguous() and down.is_contiguous()):
+                    raise ValueError(f"LoRA factors up {tuple(up.shape)} x down {tuple(down.shape)} do not fit {name} "
+                                     f"{tuple(w.shape)} (factors uploaded for another model?)")
+        try:
+            with torch.cuda.device(dev):
+                st = _lib.stream_ptr(dev)
+                for name, hits in plan.items():
+                    base = params[name].detach()
+                    base = (base if base.device == dev else base.to(dev)).contiguous()
+                    arr = (_lib.LoraPair * max(len(hits), 1))()
+                    for j, ((up, down, iscale), scale) in enumerate(hits):
+                        arr[j].up, arr[j].down = up.data_ptr(), down.data_ptr()
+                        arr[j].dtype, arr[j].rank, arr[j].scale = _lib.dtype_code(up), down.shape[0], scale * iscale
+                    shape = (C.c_int64 * base.ndim)(*base.shape)
+                    _lib.check(L.gyre_unet_set_weight_lora(C.c_void_p(unet._handle), name.encode(), C.c_void_p(base.data_ptr()),
+                                                           _lib.dtype_code(base), shape, base.ndim, len(hits), arr, C.c_void_p(st)), L)
+        except Exception:
+            # some keys may carry the new pairs and others not: the native copy no longer matches any registry state, so the next
+            # use uploads everything again and re-applies whatever the caller leaves attached
+            unet._invalidate()
+            raise
+    # what the context cache, the SDXL embedding memo and the device-slot replicas compare; NOT _dirty: nothing else is re-uploaded
+    unet._ctx_slots = []
+    unet._weights_version = getattr(unet, "_weights_version", 0) + 1
+
+
+def _reapply_attached(unet) -> None:
+    """modules._NativeModule._sync, behind a full (dirty) upload: put the attached LoRAs onto the new native copy."""
+    at = getattr(unet, "_lora_attached", None)
+    if at and at["loras"]:
+        _issue(unet, sorted({n for f, _ in at["loras"].values() for n in f.pairs}))
+
+
+def attach_lora(unet, tensors, lora_id, scale: float = 1.0) -> int:
+    """Attach one LoRA (a dict of tensors, or the LoraFactors upload_factors made of one) under ``lora_id`` on the device path:
+    only the weights it touches are repacked, from the master parameter and the factors (module docstring).  Returns the number
+    of weights touched.  The module must be on a GPU (GyreError otherwise, as for a forward)."""
+    return attach_loras(unet, [(tensors, lora_id, scale)])[0]
+
+
+def attach_loras(unet, specs) -> list:
+    """Several LoRAs at once, ``specs = [(tensors or LoraFactors, lora_id, scale), ...]``: all are registered first and every
+    touched weight is repacked ONCE, with all the pairs that hit it.  Returns the number of weights each one touches."""
+    if (getattr(unet, "_lora_state", None) or {"loras": {}})["loras"]:
+        raise ValueError("this module has host-merged LoRAs (apply_lora): the two LoRA paths do not stack - "
+                         "remove_lora_from_model() first")
+    for tensors, _, _ in specs:                                # format errors come first
+        if not isinstance(tensors, LoraFactors) and detect_lora_type(tensors) == "cloneofsimo":
+            raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")
+    dev = unet.device
+    unet._sync(dev)                                            # handle exists and holds the current weights (+ what is attached)
+    new = [(t.to(dev) if isinstance(t, LoraFactors) else upload_factors(unet, t, dev), lid, float(scale)) for t, lid, scale in specs]
+    at = _attached(unet)
+    before = dict(at["loras"])
+    names = set()
+    for factors, lid, scale in new:
+        old = at["loras"].pop(lid, None)
+        at["loras"][lid] = (factors, scale)
+        names |= set(factors.pairs) | (set(old[0].pairs) if old else set())
+    try:
+        _issue(unet, sorted(names))
+    except Exception:                                          # (_issue has left the native copy untouched, or marked it stale)
+        at["loras"].clear()
+        at["loras"].update(before)
+        raise
+    return [len(f.pairs) for f, _, _ in new]
+
+
+def set_attached_scale(unet, lora_id, scale: float = 1.0) -> None:
+    at = _attached(unet)
+    if lora_id not in at["loras"]:
+        raise KeyError(lora_id)
+    factors = at["loras"][lora_id][0]
+    at["loras"][lora_id] = (factors, float(scale))
+    _issue(unet, sorted(factors.pairs))
+
+
+def detach_loras(unet) -> None:
+    """Take every attached LoRA off: the touched keys are re-issued with zero pairs, which writes the base bits."""
+    at = getattr(unet, "_lora_attached", None)
+    if not at or not at["loras"]:
+        return
+    names = sorted({n for f, _ in at["loras"].values() for n in f.pairs})
+    at["loras"].clear()
+    _issue(unet, names)

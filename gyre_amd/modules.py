@@ -75,6 +75,9 @@ class _NativeModule(nn.Module):
         if st is not None:
             st["base"].clear()
             st["loras"].clear()
+        at = getattr(self, "_lora_attached", None)      # device-path LoRAs (lora.attach_lora) hang off the old weights too
+        if at is not None:
+            at["loras"].clear()
         self._invalidate()
 
     def _invalidate(self):
@@ -119,7 +122,8 @@ class _NativeModule(nn.Module):
         except Exception:
             pass
 
-    _NATIVE_STATE = ("_handle", "_handle_device", "_handle_storage", "_ws", "_ws_vjp", "_ctx_slots", "_vjp_pending")
+    # (_lora_attached: device tensors and pointers handed to THIS module's handle - a copy starts without attached LoRAs)
+    _NATIVE_STATE = ("_handle", "_handle_device", "_handle_storage", "_ws", "_ws_vjp", "_ctx_slots", "_vjp_pending", "_lora_attached")
 
     def __deepcopy__(self, memo):
         """A copy gets its OWN native handle (created at first use): the reference clones modules with ``deepcopy`` - per
@@ -191,6 +195,9 @@ class _NativeModule(nn.Module):
                 _lib.check(getattr(L, f"gyre_{self._kind}_finalize")(C.c_void_p(self._handle), C.c_void_p(st)))
                 torch.cuda.current_stream(device).synchronize()  # load time only: temporaries may now be freed
                 self._dirty = False
+                if getattr(self, "_lora_attached", None):         # attached LoRAs follow the module onto its new native copy
+                    from . import lora as _lora
+                    _lora._reapply_attached(self)
         return self._handle
 
     def _upload_source(self, key: str, p: torch.Tensor) -> torch.Tensor:

@@ -128,6 +128,22 @@ const char* gyre_unet_param_key(const gyre_unet* h, int i);
  * the source may be released once the stream has passed this point. */
 int gyre_unet_set_weight(gyre_unet* h, const char* diffusers_key, const void* dev_ptr, int dtype,
                          const int64_t* shape, int ndim, void* stream);
+/* Per-request LoRA without leaving the device.  The reference hooks  up(down(input)) * alpha / r * scale  onto every targeted
+ * layer for one request and strips the hooks at the next (gyre/pipeline/lora.py:96-160); here the same linear map joins the
+ * repack of the ONE weight it touches:
+ *   packed(key) = round( k * ( base + sum_j scale_j * up_j down_j ) ),  summed in fp32, one rounding (k: the factor the library
+ *   folds into some weights itself, e.g. the softmax scale in to_k)
+ * base: the unpatched weight in PyTorch layout, as for gyre_unet_set_weight (same key and shape rules, GYRE_ERR_KEY);
+ * up_j [O][rank] (x 1 x 1), down_j [rank][I] (x KH x KW), contiguous device tensors of pairs[j].dtype (GYRE_F32 / BF16 / F16, each
+ * pair its own), rank >= 1, at most 8 pairs; scale_j = user scale * alpha / rank.  n_pairs == 0 writes exactly what
+ * gyre_unet_set_weight writes: that takes a LoRA off again.  Vector keys (biases, norms), more than 8 pairs or rank < 1:
+ * GYRE_ERR_INVALID.  Nothing else is uploaded: a finalized handle stays finalized (the key had been set before), the cached text
+ * contexts are dropped, and the copies the library derives from weights (transposed, LayerNorm-folded, blocked, fragment-ordered,
+ * folded-shortcut) are refreshed on the device by the next forward - all of them, they share one version counter.
+ * Asynchronous on `stream`; base and the factors may be released once the stream has passed this point. */
+typedef struct { const void* up; const void* down; int dtype; int rank; float scale; } gyre_lora_pair;
+int gyre_unet_set_weight_lora(gyre_unet* h, const char* diffusers_key, const void* base, int base_dtype,
+                              const int64_t* shape, int ndim, int n_pairs, const gyre_lora_pair* pairs, void* stream);
 /* 0 when every expected key has been set; otherwise GYRE_ERR_INCOMPLETE (message lists a missing key). */
 int gyre_unet_finalize(gyre_unet* h, void* stream);
 size_t gyre_unet_workspace_bytes(gyre_unet* h, int B, int H, int W, int S);
@@ -496,8 +512,20 @@ int gyre_op_conv3x3_nchw(void* stream, const void* x, int B, int H, int W, int C
 /* Repack helpers used by the tests to build the layouts above from PyTorch-layout f32 tensors */
 int gyre_op_repack_conv_weight(void* stream, const float* w_oihw, int Cout, int Cin, int KH, int KW, int Cin_pad,
                                void* w_krsc_bf16);
+/* The same repack as gyre_unet_set_weight runs it for a weight that carries a folded factor (the softmax scale in to_k): source of
+ * any gyre_dtype, every value round(scale * w), the product and the rounding exactly as the store does them.  The tests compare
+ * gyre_op_repack_lora's bits with it. */
+int gyre_op_repack_conv_weight_scaled(void* stream, const void* w_oihw, int dtype, int Cout, int Cin, int KH, int KW, int Cin_pad,
+                                      float scale, void* w_krsc);
 int gyre_op_repack_linear_weight(void* stream, const float* w_oi, int O, int I, int geglu_interleave, void* w_bf16);
 int gyre_op_repack_bias(void* stream, const float* b, int n, int geglu_interleave, float* out);
+/* The repack of gyre_unet_set_weight_lora as an operator: base (O x I x KH x KW, base_dtype) and n_pairs LoRA factor pairs ->
+ * out [O][KH][KW][I_pad] in the storage type (pad columns zero; KH = KW = 1 for a matrix; geglu != 0: the 16-row value / gate
+ * interleave of gyre_op_repack_linear_weight, the up factor indexed by the SOURCE row), every value
+ * round(scale_p * (base + sum_j scale_j up_j down_j)) with the sum in fp32: r ascending inside a pair, pairs in argument order.
+ * I_pad >= I and a multiple of 4; out is caller-owned, O * KH * KW * I_pad elements. */
+int gyre_op_repack_lora(void* stream, const void* base, int base_dtype, int O, int I, int KH, int KW, int I_pad,
+                        int geglu_interleave, float scale_p, int n_pairs, const gyre_lora_pair* pairs, void* out);
 /* o[B,Nq,H*D] = softmax(q k^T * D^-1/2) v ; q[B,Nq,H*D] (ldq), k[B,Nk,H*D] (ldk), vt[B,H*D,ldvt] (V transposed) */
 int gyre_op_attention(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                       int B, int heads, int Nq, int Nk, int D, void* o, int ldo);
