@@ -84,7 +84,15 @@ class LoraPair(C.Structure):
     _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("dtype", C.c_int), ("rank", C.c_int), ("scale", C.c_float)]
 
 
+class DeltaTerm(C.Structure):
+    """gyre_delta_term (include/gyre_hip.h): one LyCORIS term of a delta-merge repack, device pointers."""
+    _fields_ = [("kind", C.c_int), ("up", C.c_void_p * 2), ("down", C.c_void_p * 2), ("dtype", C.c_int * 2), ("rank", C.c_int * 2),
+                ("w1", C.c_void_p), ("O1", C.c_int), ("I1", C.c_int), ("scale", C.c_float)]
+
+
 LORA_MAX_PAIRS = 8
+DELTA_MAX_TERMS = 8
+DELTA_LORA, DELTA_HADA, DELTA_KRON, DELTA_FULL = 0, 1, 2, 3
 _vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
 _SIGS = {
     "gyre_abi_version": (C.c_int, []),
@@ -97,6 +105,7 @@ _SIGS = {
     "gyre_unet_param_key": (C.c_char_p, [_vp, _i]),
     "gyre_unet_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "gyre_unet_set_weight_lora": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _i, C.POINTER(LoraPair), _vp]),
+    "gyre_unet_set_weight_delta": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _i, C.POINTER(DeltaTerm), _vp]),
     "gyre_unet_finalize": (_i, [_vp, _vp]),
     "gyre_unet_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "gyre_unet_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
@@ -181,6 +190,8 @@ _SIGS = {
     "gyre_op_repack_linear_weight": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "gyre_op_repack_bias": (_i, [_vp, _vp, _i, _i, _vp]),
     "gyre_op_repack_lora": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(LoraPair), _vp]),
+    "gyre_op_repack_delta": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(DeltaTerm), _vp]),
+    "gyre_op_lyco_core": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "gyre_op_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_qkv": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i]),
     "gyre_op_attention_ex": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),

@@ -106,6 +106,28 @@ struct LoraArgs {
 };
 int launch_repack_lora(hipStream_t st, const void* base, int base_dtype, int O, int I, int KH, int KW, int Ipad, int geglu_interleave,
                        float scale_p, const LoraArgs& la, bf16_t* out);
+// fused LyCORIS delta-merge repack (kernels_lyco.hip): launch_repack_lora with TERMS instead of pairs - a low-rank product (LORA), the
+// Hadamard product of two (HADA), a Kronecker product of a dense w1 with a low-rank or dense right factor (KRON), a dense diff
+// (FULL).  Operand layouts, the rank == 0 convention of a dense KRON right factor and the operation order: header of
+// kernels_lyco.hip.  Kind values are those of gyre_delta_term (include/gyre_hip.h).
+#define GYRE_DELTA_MAX_TERMS 8
+enum { DELTA_LORA = 0, DELTA_HADA = 1, DELTA_KRON = 2, DELTA_FULL = 3 };
+struct DeltaArgs {
+    int kind[GYRE_DELTA_MAX_TERMS];
+    const void* up[GYRE_DELTA_MAX_TERMS][2];
+    const void* down[GYRE_DELTA_MAX_TERMS][2];
+    int dtype[GYRE_DELTA_MAX_TERMS][2];
+    int rank[GYRE_DELTA_MAX_TERMS][2];
+    const float* w1[GYRE_DELTA_MAX_TERMS];
+    int O1[GYRE_DELTA_MAX_TERMS], I1[GYRE_DELTA_MAX_TERMS];
+    float s[GYRE_DELTA_MAX_TERMS];
+    int n = 0;
+};
+int launch_repack_delta(hipStream_t st, const void* base, int base_dtype, int O, int I, int KH, int KW, int Ipad, int geglu_interleave,
+                        float scale_p, const DeltaArgs& da, bf16_t* out);
+// out[a][c][t] = sum_b core[a][b][t] * right[b][c]  (fp32, b ascending): a Tucker core folded into the right operand of a term
+int launch_lyco_core(hipStream_t st, const void* core, int core_dtype, const void* right, int right_dtype, int A, int B, int C, int T,
+                     float* out);
 
 // ---- T2I-adapter element-wise ops (kernels_t2i.hip) ----------------------------
 // x NCHW [B][c][H][W] of a runtime dtype (H, W multiples of 8) -> y NHWC storage [B][H/8][W/8][64 c], channel c*64 + dy*8 + dx

@@ -99,6 +99,15 @@ int gyre_unet_set_weight_lora(gyre_unet* h, const char* key, const void* base, i
     h->invalidate_contexts();                    // the cached K / V projections of the text contexts were made with the old weights
     return 0;
 }
+int gyre_unet_set_weight_delta(gyre_unet* h, const char* key, const void* base, int base_dtype, const int64_t* shape, int ndim,
+                               int n_terms, const gyre_delta_term* terms, void* st) {
+    if (!h || !key || !base || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    bool was_set = false;
+    TRY(h->store.set_weight_delta(key, base, base_dtype, shape, ndim, n_terms, terms, (hipStream_t)st, &was_set));
+    if (!was_set) h->finalized = false;          // as gyre_unet_set_weight_lora
+    h->invalidate_contexts();
+    return 0;
+}
 int gyre_unet_finalize(gyre_unet* h, void* st) {
     if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
     TRY(h->store.finalize());
@@ -644,6 +653,17 @@ int gyre_op_repack_lora(void* st, const void* base, int base_dtype, int O, int I
         la.up[j] = pairs[j].up; la.down[j] = pairs[j].down; la.dtype[j] = pairs[j].dtype; la.rank[j] = pairs[j].rank; la.s[j] = pairs[j].scale;
     }
     return launch_repack_lora((hipStream_t)st, base, base_dtype, O, I, KH, KW, I_pad, geglu, scale_p, la, (bf16_t*)out);
+}
+int gyre_op_repack_delta(void* st, const void* base, int base_dtype, int O, int I, int KH, int KW, int I_pad, int geglu, float scale_p,
+                         int n_terms, const gyre_delta_term* terms, void* out) {
+    if (!base || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    DeltaArgs da;
+    TRY(delta_terms_to_args(n_terms, terms, da));
+    return launch_repack_delta((hipStream_t)st, base, base_dtype, O, I, KH, KW, I_pad, geglu, scale_p, da, (bf16_t*)out);
+}
+int gyre_op_lyco_core(void* st, const void* core, int core_dtype, const void* right, int right_dtype, int A, int B, int Cn, int T,
+                      float* out) {
+    return launch_lyco_core((hipStream_t)st, core, core_dtype, right, right_dtype, A, B, Cn, T, out);
 }
 int gyre_op_repack_bias(void* st, const float* b, int n, int geglu, float* out) {
     if (!b || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");

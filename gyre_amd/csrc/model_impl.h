@@ -17,6 +17,22 @@
 #include <vector>
 
 #define TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// gyre_delta_term[] (C ABI) -> DeltaArgs (kernel argument); the operand checks themselves are launch_repack_delta's
+static_assert(GYRE_DELTA_LORA == DELTA_LORA && GYRE_DELTA_HADA == DELTA_HADA && GYRE_DELTA_KRON == DELTA_KRON && GYRE_DELTA_FULL == DELTA_FULL,
+              "term kinds of the C ABI and of the kernel");
+static inline int delta_terms_to_args(int n_terms, const gyre_delta_term* terms, DeltaArgs& da) {
+    if (n_terms < 0 || n_terms > GYRE_DELTA_MAX_TERMS || (n_terms > 0 && !terms)) GYRE_FAIL(GYRE_ERR_INVALID, "0 to 8 delta terms per call");
+    da.n = n_terms;
+    for (int j = 0; j < n_terms; ++j) {
+        da.kind[j] = terms[j].kind;
+        for (int q = 0; q < 2; ++q) {
+            da.up[j][q] = terms[j].up[q]; da.down[j][q] = terms[j].down[q]; da.dtype[j][q] = terms[j].dtype[q]; da.rank[j][q] = terms[j].rank[q];
+        }
+        da.w1[j] = terms[j].w1; da.O1[j] = terms[j].O1; da.I1[j] = terms[j].I1; da.s[j] = terms[j].scale;
+    }
+    return 0;
+}
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int pad8(int c) { return (c + 7) / 8 * 8; }
 
@@ -295,6 +311,41 @@ struct Store {
             TRY(launch_repack_lora(st, src, dtype, O, I, 1, 1, I, 1, 1.f, la, (bf16_t*)p.dev));
         } else {
             TRY(launch_repack_lora(st, src, dtype, O, I, 1, 1, p.i_pad, 0, p.scale, la, (bf16_t*)p.dev));
+        }
+        if (was_set) *was_set = p.set;
+        p.set = true;
+        ++weights_version;
+        return 0;
+    }
+    // set_weight of  base + sum_j scale_j D_j  with LyCORIS terms (gyre_delta_term, reference gyre/pipeline/lycoris.py:99-228): set_weight_lora
+    // with launch_repack_delta in place of launch_repack_lora - same key / shape rules, same version counter, n_terms == 0 writes
+    // set_weight's bits.  Every check (delta_terms_to_args, launch_repack_delta) precedes the launch.
+    int set_weight_delta(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, int n_terms,
+                         const gyre_delta_term* terms, hipStream_t st, bool* was_set) {
+        auto it = by_key.find(key);
+        if (it == by_key.end()) GYRE_FAIL(GYRE_ERR_KEY, std::string("unknown weight key: ") + key);
+        Param& p = *it->second;
+        if (p.kind == PK_VEC || p.kind == PK_VEC_GEGLU) GYRE_FAIL(GYRE_ERR_INVALID, std::string("a LyCORIS delta applies to matrices and convolutions, not to the vector ") + key);
+        if (dtype < 0 || dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
+        bool ok = (int)p.shape.size() == ndim;
+        for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
+        if (!ok) {
+            std::string m = std::string("shape mismatch for ") + key + ": expected [";
+            for (auto d : p.shape) m += std::to_string(d) + ",";
+            m += "] got [";
+            for (int i = 0; i < ndim; ++i) m += std::to_string(shape[i]) + ",";
+            GYRE_FAIL(GYRE_ERR_KEY, m + "]");
+        }
+        DeltaArgs da;
+        TRY(delta_terms_to_args(n_terms, terms, da));
+        const int O = (int)p.shape[0], I = (int)p.shape[1];
+        if (p.kind == PK_CONV3) {
+            TRY(launch_repack_delta(st, src, dtype, O, I, 3, 3, p.i_pad, 0, 1.f, da, (bf16_t*)p.dev));
+        } else if (p.kind == PK_MAT_GEGLU) {
+            if (p.i_pad != I) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "geglu weight with padded K");
+            TRY(launch_repack_delta(st, src, dtype, O, I, 1, 1, I, 1, 1.f, da, (bf16_t*)p.dev));
+        } else {
+            TRY(launch_repack_delta(st, src, dtype, O, I, 1, 1, p.i_pad, 0, p.scale, da, (bf16_t*)p.dev));
         }
         if (was_set) *was_set = p.set;
         p.set = true;

@@ -30,7 +30,11 @@ the adapter once per request, its states added inside the UNet on every step (gy
 hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py): depth maps / depth UNets, ControlNet
 hint handlers, style adapters and co-adapters, masked hints, hints together with hires fix / grafted inpaint / CLIP guidance /
 shard_devices, textual-inversion token embeddings.  CLIP guidance
-is implemented (gyre_amd/clipguided.py over the native input-gradient sweeps).  The safety checker stays the host module the
+is implemented (gyre_amd/clipguided.py over the native input-gradient sweeps).  ``lora=`` takes LoRA files (kohya-ss, diffusers) and,
+as the reference routes them (unified_pipeline.py:2210-2233: what ``detect_lora_type`` refuses goes to ``apply_lycoris``), LyCORIS files
+(LoCon, LoHa, LoKr, full diff; gyre_amd/lycoris.py): one attach for the whole request, every touched weight repacked once on the
+device, taken off again at the start of the next request.  IA3, DyLoRA, sparse-bias LyCORIS modules and cloneofsimo LoRA files raise
+NotImplementedError.  The safety checker stays the host module the
 manager loaded; it is RUN exactly as the reference runs it (``_safety_check``), never skipped silently.
 """
 from __future__ import annotations
@@ -42,6 +46,7 @@ import torch
 
 from . import clipguided as CG
 from . import lora as LR
+from . import lycoris as LY
 from .pipeline import GyrePipeline
 from .text import LPWTextEmbedder
 
@@ -102,7 +107,7 @@ class GyreUnifiedPipeline:
         self._shard_devices: list = []       # engine option "shard_devices": fan one request over these device slots
         self._shard_bit_exact = False
         self._executor = None
-        self._lora_uploads: list = []        # LoraFactors of the last four LoRA tensors mappings seen (_lora_factors)
+        self._lora_uploads: list = []        # LoraFactors / LycoFactors of the last four LoRA / LyCORIS tensors mappings seen (_lora_factors)
         self.clip_default_config = CG.ClipGuidanceConfig()
 
     # ---- what PipelineWrapper / DiffusionPipelineWrapper touch -----------------------------------------------------------
@@ -313,7 +318,8 @@ class GyreUnifiedPipeline:
                     clip_text_embeddings=feats.repeat_interleave(num_images_per_prompt, dim=0))
 
     def _lora_factors(self, tensors):
-        """The uploaded factors of one LoRA tensors mapping (lora.upload_factors), remembered per mapping OBJECT: the reference's
+        """The uploaded factors of one LoRA or LyCORIS tensors mapping (lora.upload_factors, or lycoris.upload_factors for what
+        detect_lora_type refuses - the reference's routing, unified_pipeline.py:2212-2216), remembered per mapping OBJECT: the reference's
         manager keeps a loaded LoRA's dict alive and hands the same object to every request that names it, so its factors go to
         the device once.  Identity-keyed, per UNet object whose shapes the upload was checked against (the entry keeps the mapping
         referenced, its address cannot be recycled), the four most
@@ -324,11 +330,12 @@ class GyreUnifiedPipeline:
             if src is tensors and net is self.unet and f.device == dev:
                 cache.append(cache.pop(i))
                 return f
-        if LR.detect_lora_type(tensors) == "cloneofsimo":
+        lyco = LY.is_lycoris(tensors)
+        if not lyco and LR.detect_lora_type(tensors) == "cloneofsimo":
             raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")
         if dev.type != "cuda":
             self.unet._sync(dev)                            # raises: the native UNet has no CPU path
-        f = LR.upload_factors(self.unet, tensors, dev)
+        f = (LY if lyco else LR).upload_factors(self.unet, tensors, dev)
         cache.append((tensors, self.unet, f))
         del cache[:-4]
         return f
@@ -451,7 +458,7 @@ class GyreUnifiedPipeline:
                 LR.attach_loras(self.unet, [(self._lora_factors(t), lid, sc) for t, lid, sc in specs])
             else:
                 for t, lid, sc in specs:
-                    LR.apply_lora(self.unet, t, lid, sc)
+                    (LY.apply_lycoris if LY.is_lycoris(t) else LR.apply_lora)(self.unet, t, lid, sc)
         steps_seen = []
 
         def cb(info):

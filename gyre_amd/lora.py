@@ -77,6 +77,11 @@ def lora_delta(up: Tensor, down: Tensor, alpha: Optional[Tensor] = None) -> Tens
     raise ValueError(f"Can't apply LoRA of rank-{down.ndim} tensors")
 
 
+def _flat_names(params) -> Dict[str, str]:
+    """kohya / LyCORIS module names (the weight's module path with ``_`` for ``.``) -> weight-parameter name"""
+    return {name[:-len(".weight")].replace(".", "_"): name for name in params if name.endswith(".weight")}
+
+
 def _pairs(unet: torch.nn.Module, lora: Mapping[str, Tensor]):
     """The key rules of both paths: yields (weight-parameter name, up, down, alpha or None) per targeted weight."""
     params = dict(unet.named_parameters())
@@ -84,7 +89,7 @@ def _pairs(unet: torch.nn.Module, lora: Mapping[str, Tensor]):
     if kind == "cloneofsimo":
         raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")
     if kind == "kohya-ss":
-        flat = {name[:-len(".weight")].replace(".", "_"): name for name in params if name.endswith(".weight")}
+        flat = _flat_names(params)
         for key in lora.keys():
             if not key.endswith(".lora_down.weight"):
                 continue
@@ -154,13 +159,23 @@ def _rebuild(unet) -> None:
         unet._invalidate()                       # the native copy is repacked from the merged weights at next use
 
 
+def _refuse_attached(unet) -> None:
+    if (getattr(unet, "_lora_attached", None) or {"loras": {}})["loras"]:
+        raise ValueError("this module has attached (device-path) LoRAs: the two LoRA paths do not stack - detach_loras() first")
+
+
 @torch.no_grad()
 def apply_lora(unet, lora: Mapping[str, Tensor], lora_id, scale: float = 1.0) -> int:
     """Merge one LoRA (a dict of tensors, e.g. safetensors.torch.load_file) under ``lora_id``.  Returns the number of
     weights touched."""
-    if (getattr(unet, "_lora_attached", None) or {"loras": {}})["loras"]:
-        raise ValueError("this module has attached (device-path) LoRAs: the two LoRA paths do not stack - detach_loras() first")
-    deltas = _targets(unet, lora)
+    _refuse_attached(unet)
+    return _merge(unet, _targets(unet, lora), lora_id, scale)
+
+
+@torch.no_grad()
+def _merge(unet, deltas: Dict[str, Tensor], lora_id, scale: float) -> int:
+    """Register ``deltas`` (weight-parameter name -> unscaled fp32 delta: a LoRA's, or a LyCORIS file's from lycoris.apply_lycoris)
+    under ``lora_id`` and rebuild the touched weights."""
     st = _state(unet)
     params = dict(unet.named_parameters())
     for name in deltas:
@@ -194,6 +209,13 @@ class LoraFactors:
 
     def __init__(self, pairs, device, source=None):
         self.pairs, self.device, self.source = pairs, device, source
+
+    def names(self):
+        return self.pairs.keys()
+
+    def hits(self, name) -> list:
+        """What hits the weight ``name``: [(up, down, alpha / r)] (lycoris.LycoFactors answers with its Term objects)."""
+        return [self.pairs[name]] if name in self.pairs else []
 
     def to(self, device):
         """These factors on ``device``: this object where they already are, a NEW one otherwise (an upload may be shared between
@@ -233,15 +255,17 @@ def upload_factors(unet, lora: Mapping[str, Tensor], device=None) -> LoraFactors
 def _attached(unet):
     at = getattr(unet, "_lora_attached", None)
     if at is None:
-        at = {"loras": {}}                       # id -> (LoraFactors, user scale), in attach order
+        at = {"loras": {}}                       # id -> (LoraFactors or lycoris.LycoFactors, user scale), in attach order
         unet._lora_attached = at
     return at
 
 
 def _issue(unet, names) -> None:
-    """gyre_unet_set_weight_lora for each of ``names`` on the module's live handle: the untouched master parameter plus every
-    attached pair that hits the key (none: the base bits).  A module whose native copy is stale anyway (``_dirty``: after
-    ``.to(...)``) is left to ``_sync``, which re-applies the attached set behind its full upload."""
+    """One repack call for each of ``names`` on the module's live handle: the untouched master parameter plus every attached LoRA
+    pair and LyCORIS term that hits the key, in attach order (none: the base bits).  A key hit by LoRA pairs only (or by nothing)
+    goes to gyre_unet_set_weight_lora, one with a LyCORIS term to gyre_unet_set_weight_delta, where a pair is a LORA term - the
+    same kernel arithmetic either way.  A module whose native copy is stale anyway (``_dirty``: after ``.to(...)``) is left to
+    ``_sync``, which re-applies the attached set behind its full upload."""
     import ctypes as C
     from . import _lib
     names = list(names)
@@ -259,10 +283,15 @@ def _issue(unet, names) -> None:
         plan = {}
         for name in names:                       # (scale 0 contributes nothing, as in the host merge)
             w = params[name]
-            plan[name] = [(f.pairs[name], scale) for f, scale in at["loras"].values() if name in f.pairs and scale != 0]
+            plan[name] = [(hit, scale) for f, scale in at["loras"].values() if scale != 0 for hit in f.hits(name)]
             if len(plan[name]) > _lib.LORA_MAX_PAIRS:
-                raise ValueError(f"{len(plan[name])} LoRAs hit {name}: at most {_lib.LORA_MAX_PAIRS} per weight")
-            for (up, down, _), _ in plan[name]:
+                raise ValueError(f"{len(plan[name])} LoRA pairs / LyCORIS terms hit {name}: at most {_lib.LORA_MAX_PAIRS} per weight")
+            for hit, _ in plan[name]:
+                if not isinstance(hit, tuple):
+                    if w.ndim not in (2, 4) or not hit.fits(w):
+                        raise ValueError(f"LyCORIS term does not fit {name} {tuple(w.shape)} (factors uploaded for another model?)")
+                    continue
+                up, down, _ = hit
                 if up.ndim != w.ndim or down.ndim != w.ndim or up.shape[0] != w.shape[0] or up.shape[1] != down.shape[0] \
                         or tuple(down.shape[1:]) != tuple(w.shape[1:]) or not (up.is_contiguous() and down.is_contiguous()):
                     raise ValueError(f"LoRA factors up {tuple(up.shape)} x down {tuple(down.shape)} do not fit {name} "
@@ -273,13 +302,26 @@ def _issue(unet, names) -> None:
                 for name, hits in plan.items():
                     base = params[name].detach()
                     base = (base if base.device == dev else base.to(dev)).contiguous()
-                    arr = (_lib.LoraPair * max(len(hits), 1))()
-                    for j, ((up, down, iscale), scale) in enumerate(hits):
-                        arr[j].up, arr[j].down = up.data_ptr(), down.data_ptr()
-                        arr[j].dtype, arr[j].rank, arr[j].scale = _lib.dtype_code(up), down.shape[0], scale * iscale
                     shape = (C.c_int64 * base.ndim)(*base.shape)
-                    _lib.check(L.gyre_unet_set_weight_lora(C.c_void_p(unet._handle), name.encode(), C.c_void_p(base.data_ptr()),
-                                                           _lib.dtype_code(base), shape, base.ndim, len(hits), arr, C.c_void_p(st)), L)
+                    if all(isinstance(hit, tuple) for hit, _ in hits):
+                        arr = (_lib.LoraPair * max(len(hits), 1))()
+                        for j, ((up, down, iscale), scale) in enumerate(hits):
+                            arr[j].up, arr[j].down = up.data_ptr(), down.data_ptr()
+                            arr[j].dtype, arr[j].rank, arr[j].scale = _lib.dtype_code(up), down.shape[0], scale * iscale
+                        _lib.check(L.gyre_unet_set_weight_lora(C.c_void_p(unet._handle), name.encode(), C.c_void_p(base.data_ptr()),
+                                                               _lib.dtype_code(base), shape, base.ndim, len(hits), arr, C.c_void_p(st)), L)
+                        continue
+                    arr = (_lib.DeltaTerm * len(hits))()
+                    for j, (hit, scale) in enumerate(hits):
+                        if isinstance(hit, tuple):
+                            up, down, iscale = hit
+                            arr[j].kind, arr[j].scale = _lib.DELTA_LORA, scale * iscale
+                            arr[j].up[0], arr[j].down[0] = up.data_ptr(), down.data_ptr()
+                            arr[j].dtype[0], arr[j].rank[0] = _lib.dtype_code(up), down.shape[0]
+                        else:
+                            hit.fill(arr[j], scale)
+                    _lib.check(L.gyre_unet_set_weight_delta(C.c_void_p(unet._handle), name.encode(), C.c_void_p(base.data_ptr()),
+                                                            _lib.dtype_code(base), shape, base.ndim, len(hits), arr, C.c_void_p(st)), L)
         except Exception:
             # some keys may carry the new pairs and others not: the native copy no longer matches any registry state, so the next
             # use uploads everything again and re-applies whatever the caller leaves attached
@@ -294,7 +336,7 @@ def _reapply_attached(unet) -> None:
     """modules._NativeModule._sync, behind a full (dirty) upload: put the attached LoRAs onto the new native copy."""
     at = getattr(unet, "_lora_attached", None)
     if at and at["loras"]:
-        _issue(unet, sorted({n for f, _ in at["loras"].values() for n in f.pairs}))
+        _issue(unet, sorted({n for f, _ in at["loras"].values() for n in f.names()}))
 
 
 def attach_lora(unet, tensors, lora_id, scale: float = 1.0) -> int:
@@ -306,30 +348,33 @@ def attach_lora(unet, tensors, lora_id, scale: float = 1.0) -> int:
 
 def attach_loras(unet, specs) -> list:
     """Several LoRAs at once, ``specs = [(tensors or LoraFactors, lora_id, scale), ...]``: all are registered first and every
-    touched weight is repacked ONCE, with all the pairs that hit it.  Returns the number of weights each one touches."""
+    touched weight is repacked ONCE, with all the pairs that hit it.  Returns the number of weights each one touches.  An entry
+    may also be the LycoFactors of an uploaded LyCORIS file (lycoris.upload_factors; lycoris.attach_adapters routes mappings of
+    either kind); a tensors mapping given here is read as a LoRA and a LyCORIS one is refused by detect_lora_type."""
     if (getattr(unet, "_lora_state", None) or {"loras": {}})["loras"]:
         raise ValueError("this module has host-merged LoRAs (apply_lora): the two LoRA paths do not stack - "
                          "remove_lora_from_model() first")
+    is_factors = lambda t: hasattr(t, "hits")                  # LoraFactors, or the LycoFactors of lycoris.upload_factors
     for tensors, _, _ in specs:                                # format errors come first
-        if not isinstance(tensors, LoraFactors) and detect_lora_type(tensors) == "cloneofsimo":
+        if not is_factors(tensors) and detect_lora_type(tensors) == "cloneofsimo":
             raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")
     dev = unet.device
     unet._sync(dev)                                            # handle exists and holds the current weights (+ what is attached)
-    new = [(t.to(dev) if isinstance(t, LoraFactors) else upload_factors(unet, t, dev), lid, float(scale)) for t, lid, scale in specs]
+    new = [(t.to(dev) if is_factors(t) else upload_factors(unet, t, dev), lid, float(scale)) for t, lid, scale in specs]
     at = _attached(unet)
     before = dict(at["loras"])
     names = set()
     for factors, lid, scale in new:
         old = at["loras"].pop(lid, None)
         at["loras"][lid] = (factors, scale)
-        names |= set(factors.pairs) | (set(old[0].pairs) if old else set())
+        names |= set(factors.names()) | (set(old[0].names()) if old else set())
     try:
         _issue(unet, sorted(names))
     except Exception:                                          # (_issue has left the native copy untouched, or marked it stale)
         at["loras"].clear()
         at["loras"].update(before)
         raise
-    return [len(f.pairs) for f, _, _ in new]
+    return [len(f.names()) for f, _, _ in new]
 
 
 def set_attached_scale(unet, lora_id, scale: float = 1.0) -> None:
@@ -338,7 +383,7 @@ def set_attached_scale(unet, lora_id, scale: float = 1.0) -> None:
         raise KeyError(lora_id)
     factors = at["loras"][lora_id][0]
     at["loras"][lora_id] = (factors, float(scale))
-    _issue(unet, sorted(factors.pairs))
+    _issue(unet, sorted(factors.names()))
 
 
 def detach_loras(unet) -> None:
@@ -346,6 +391,6 @@ def detach_loras(unet) -> None:
     at = getattr(unet, "_lora_attached", None)
     if not at or not at["loras"]:
         return
-    names = sorted({n for f, _ in at["loras"].values() for n in f.pairs})
+    names = sorted({n for f, _ in at["loras"].values() for n in f.names()})
     at["loras"].clear()
     _issue(unet, names)

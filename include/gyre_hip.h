@@ -144,6 +144,29 @@ int gyre_unet_set_weight(gyre_unet* h, const char* diffusers_key, const void* de
 typedef struct { const void* up; const void* down; int dtype; int rank; float scale; } gyre_lora_pair;
 int gyre_unet_set_weight_lora(gyre_unet* h, const char* diffusers_key, const void* base, int base_dtype,
                               const int64_t* shape, int ndim, int n_pairs, const gyre_lora_pair* pairs, void* stream);
+/* Per-request LyCORIS (LoCon, LoHa, LoKr, full diff) the same way.  The reference rebuilds  weight + sum updown  per targeted module
+ * (gyre/pipeline/lycoris.py:99-228, 267-285); here each such delta is one TERM of the repack of the weight it touches:
+ *   packed(key) = round( k * ( base + sum_j scale_j * D_j ) ),  summed in fp32 in term order, one rounding
+ *   GYRE_DELTA_LORA  D = up[0] down[0]                                  up [O][rank] (x 1 x 1), down [rank][I] (x KH x KW)
+ *   GYRE_DELTA_HADA  D = (up[0] down[0]) * (up[1] down[1]) element-wise, each pair with its own rank and dtype
+ *   GYRE_DELTA_KRON  D[o1 O2 + o2][i1 I2 + i2](ky, kx) = w1[o1][i1] * W2[o2][i2](ky, kx),  w1 dense fp32 [O1][I1] with O1 | O, I1 | I;
+ *                    W2 = up[0] [O2][rank] times down[0] [rank][I2] (x KH x KW), or with rank[0] == 0 the dense tensor down[0]
+ *                    [O2][I2] (x KH x KW) (up[0] unused)
+ *   GYRE_DELTA_FULL  D = down[0], a dense [O][I] (x KH x KW) tensor
+ * Operands are contiguous device tensors of dtype[q] (GYRE_F32 / BF16 / F16) per (up, down) pair q.  A Tucker core is folded into the
+ * right operand beforehand with gyre_op_lyco_core.  Same key and shape rules, version counter and finalize behaviour as
+ * gyre_unet_set_weight_lora; 0 to 8 terms, n_terms == 0 writes gyre_unet_set_weight's bits.  GYRE_ERR_INVALID for vector keys,
+ * a null operand, rank < 1 where a rank is needed, and Kronecker factors whose sizes do not multiply to the weight's; every
+ * check precedes the launch and a refused call writes nothing. */
+enum { GYRE_DELTA_LORA = 0, GYRE_DELTA_HADA = 1, GYRE_DELTA_KRON = 2, GYRE_DELTA_FULL = 3 };
+typedef struct {
+    int kind;
+    const void* up[2]; const void* down[2]; int dtype[2]; int rank[2];
+    const float* w1; int O1, I1;
+    float scale;
+} gyre_delta_term;
+int gyre_unet_set_weight_delta(gyre_unet* h, const char* diffusers_key, const void* base, int base_dtype,
+                               const int64_t* shape, int ndim, int n_terms, const gyre_delta_term* terms, void* stream);
 /* 0 when every expected key has been set; otherwise GYRE_ERR_INCOMPLETE (message lists a missing key). */
 int gyre_unet_finalize(gyre_unet* h, void* stream);
 size_t gyre_unet_workspace_bytes(gyre_unet* h, int B, int H, int W, int S);
@@ -526,6 +549,14 @@ int gyre_op_repack_bias(void* stream, const float* b, int n, int geglu_interleav
  * I_pad >= I and a multiple of 4; out is caller-owned, O * KH * KW * I_pad elements. */
 int gyre_op_repack_lora(void* stream, const void* base, int base_dtype, int O, int I, int KH, int KW, int I_pad,
                         int geglu_interleave, float scale_p, int n_pairs, const gyre_lora_pair* pairs, void* out);
+/* The repack of gyre_unet_set_weight_delta as an operator (arguments as gyre_op_repack_lora, terms as gyre_delta_term), and the
+ * core contraction that prepares a Tucker form:  out[a][c][t] = sum_b core[a][b][t] * right[b][c],  core [A][B][T] and right [B][C]
+ * of their own gyre_dtype, out fp32 [A][C][T], b ascending with fused multiply-adds.  core(mid, down) is the down operand of a LoCon
+ * with a mid tensor, core(t, wb) that of a LoHa / LoKr Tucker form, and T = 1 gives w1 = w1a @ w1b. */
+int gyre_op_repack_delta(void* stream, const void* base, int base_dtype, int O, int I, int KH, int KW, int I_pad,
+                         int geglu_interleave, float scale_p, int n_terms, const gyre_delta_term* terms, void* out);
+int gyre_op_lyco_core(void* stream, const void* core, int core_dtype, const void* right, int right_dtype, int A, int B, int C, int T,
+                      float* out);
 /* o[B,Nq,H*D] = softmax(q k^T * D^-1/2) v ; q[B,Nq,H*D] (ldq), k[B,Nk,H*D] (ldk), vt[B,H*D,ldvt] (V transposed) */
 int gyre_op_attention(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                       int B, int heads, int Nq, int Nk, int D, void* o, int ldo);
