@@ -23,6 +23,7 @@ typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8_t;      // MFMA oper
 typedef __attribute__((ext_vector_type(2))) _Float16 bf16x2_t;
 #define GYRE_STORAGE_DTYPE 2                                          /* GYRE_F16 */
 #define GYRE_ONE_BITS 0x3c00                                          /* 1.0 */
+#define GYRE_INF_BITS 0x7c00u                                         /* +inf: larger magnitude bits are NaNs */
 #define GYRE_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_f16
 #define GYRE_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_f16
 // softmax probabilities are packed to the storage type: fp16 ends at 65504, so rows are re-centred (and the optimistic attention pass
@@ -42,6 +43,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 #define GYRE_STORAGE_DTYPE 1                                          /* GYRE_BF16 */
 #define GYRE_ONE_BITS 0x3f80
+#define GYRE_INF_BITS 0x7f80u
 #define GYRE_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #define GYRE_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
 #define GYRE_ATTN_TAU 60.f

@@ -53,12 +53,14 @@ int launch_avgpool2(hipStream_t st, const bf16_t* x, int B, int H, int W, int C,
     return 0;
 }
 
-// x = max(x, 0) in place, 8 storage elements per lane.  bf16 and fp16 both carry the sign in bit 15: a negative element becomes +0.
+// x = max(x, 0) in place, 8 storage elements per lane.  bf16 and fp16 both carry the sign in bit 15: a negative element becomes +0,
+// except a NaN, which stays a NaN whatever its sign (torch.relu propagates it; magnitude bits above the infinity pattern).
 __global__ void k_relu(uint4* __restrict__ x, size_t n8) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n8) return;
     uint4 v = x[i];
-    auto r = [](uint32_t w) -> uint32_t { return w & ((w & 0x8000u ? 0u : 0xffffu) | (w & 0x80000000u ? 0u : 0xffff0000u)); };
+    auto keep = [](uint32_t h) -> bool { return !(h & 0x8000u) || (h & 0x7fffu) > GYRE_INF_BITS; };
+    auto r = [&](uint32_t w) -> uint32_t { return w & ((keep(w & 0xffffu) ? 0xffffu : 0u) | (keep(w >> 16) ? 0xffff0000u : 0u)); };
     v.x = r(v.x); v.y = r(v.y); v.z = r(v.z); v.w = r(v.w);
     x[i] = v;
 }

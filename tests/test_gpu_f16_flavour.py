@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = ["tests/test_gpu_kernels.py", "tests/test_gpu_gemm_ar.py", "tests/test_gpu_gemm_sm.py", "tests/test_gpu_models.py",
          "tests/test_gpu_properties.py", "tests/test_gpu_vjp.py", "tests/test_gpu_bwd_kernels.py", "tests/test_gpu_attn_fwd.py", "tests/test_gpu_norm_fwd.py", "tests/test_gpu_gemm_exact.py", "tests/test_gpu_tome_exact.py", "tests/test_gpu_temb.py", "tests/test_gpu_configs.py",
-         "tests/test_gpu_full_runs.py"]
+         "tests/test_gpu_range.py", "tests/test_gpu_full_runs.py"]
 
 
 @pytest.mark.skipif(_lib.default_storage() == _lib.F16, reason="already inside the fp16 run")
