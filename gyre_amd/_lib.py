@@ -184,6 +184,7 @@ _SIGS = {
     "gyre_op_linear_rowstats": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "gyre_op_conv3x3": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "gyre_op_conv3x3_shortcut": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "gyre_op_compose_proj_out": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "gyre_op_conv3x3_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i]),
     "gyre_op_repack_conv_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "gyre_op_repack_conv_weight_scaled": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),

@@ -10,6 +10,10 @@ int launch_ctx_to_bf16(hipStream_t st, const void* x, int dtype, size_t n, bf16_
 // dst[o][0:inner] = dst[o][inner:2*inner] = src[o][0:inner] (bytes, multiples of 16), o < outer
 int launch_dup_batch(hipStream_t st, const void* src, void* dst, size_t outer, size_t inner_bytes);
 int launch_add_f32(hipStream_t st, float* y, const float* x, size_t n);
+// A Transformer2D's proj_out composed with the FF2 in front of it (C % 64 == 0; Wp [C][C], W2 [C][4C] storage rows, b2 / bp [C] f32 or null):
+//   Wc[n][0:4C] = sum_k Wp[n][k] W2[k][j]  (fp32, k ascending, one rounding to the storage type), Wc[n][4C:5C] = Wp[n][:]   (Wc [C][5C])
+//   bc[n] = sum_k Wp[n][k] b2[k] + bp[n]   (fp32, k ascending)
+int launch_compose_proj(hipStream_t st, const bf16_t* Wp, const bf16_t* W2, const float* b2, const float* bp, int C, bf16_t* Wc, float* bc);
 // debug (GYRE_VERIFY_HINTS=1): flag |= 1 if t[b] != t[0] for some b, |= 2 if the two halves of x (bytes_per_half each) differ
 int launch_verify_hints(hipStream_t st, const int64_t* t, int B, int check_t, const void* x, size_t bytes_per_half, int check_pairs, int* flag);
 int launch_timestep_embedding(hipStream_t st, const int64_t* t, int B, int dim, int flip, float shift, float* out);
@@ -70,6 +74,7 @@ enum : int {
     GEMM_DBG_DEEP_RING        = 0x2000000,   // bit 25: the deep ring at one workgroup per CU also where two 2-stage workgroups fit
     GEMM_DBG_NO_W_BLOCK       = 0x4000000,   // bit 26: row-major weights everywhere (no blocked weight copies)
     GEMM_DBG_TWO_STAGE_CONV   = 0x8000000,   // bit 27: the two-stage K loop for the 128x160 / 256x128 tiles' 3x3 convolutions
+    GEMM_DBG_NO_POUT_FOLD     = 0x10000000,  // bit 28: a Transformer2D's proj_out stays its own launch instead of riding inside the last FF2
 };
 int launch_groupnorm_stats(hipStream_t st, const GnParams& p);   // partial sums + finalize -> scale_shift
 int launch_groupnorm_apply(hipStream_t st, const GnParams& p);   // y = act(a*x+b)

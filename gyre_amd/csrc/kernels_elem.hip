@@ -151,6 +151,79 @@ int launch_add_f32(hipStream_t st, float* y, const float* x, size_t n) {
 }
 
 // ------------------------------------------------------------------------------
+// Composed weights of a Transformer2D's proj_out folded into its last FF2 (launch_compose_proj, kernels.h).  Runs once per weight
+// version and handle, so a plain LDS-tiled fp32 FMA kernel: 64 x 64 outputs per workgroup, 4 x 4 per thread, 16 k per step; every
+// output is ONE fmaf chain over k ascending (the error bound the tests hold it to), then one rounding.  Blocks of the fifth column
+// block (j >= 4C) copy Wp.  The bias kernel is one thread per row.
+// ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_compose_proj(const bf16_t* __restrict__ Wp, const bf16_t* __restrict__ W2, int C,
+                                                      bf16_t* __restrict__ Wc) {
+    __shared__ float sa[16][64 + 4];     // Wp tile, [k][n]
+    __shared__ float sb[16][64 + 4];     // W2 tile, [k][j]
+    const int n0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int ldc = 5 * C, ld2 = 4 * C;
+    if (j0 >= ld2) {                     // [.. | Wp]: 64 x 64 elements, 16 per thread
+        const int r = tid >> 2, c = (tid & 3) * 16;
+        const uint4* src = (const uint4*)(Wp + (size_t)(n0 + r) * C + (j0 - ld2) + c);
+        uint4* dst = (uint4*)(Wc + (size_t)(n0 + r) * ldc + j0 + c);
+        dst[0] = src[0]; dst[1] = src[1];
+        return;
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    for (int k0 = 0; k0 < C; k0 += 16) {
+        {   // Wp[n0 + r][k0 + 4 q .. + 3] -> sa[k][r];  W2[k0 + kk][j0 + 4 jq .. + 3] -> sb[kk][j]
+            const int r = tid >> 2, q = (tid & 3) * 4;
+            const uint2 v = *(const uint2*)(Wp + (size_t)(n0 + r) * C + k0 + q);
+            sa[q + 0][r] = bf16lo(v.x); sa[q + 1][r] = bf16hi(v.x); sa[q + 2][r] = bf16lo(v.y); sa[q + 3][r] = bf16hi(v.y);
+            const int kk = tid >> 4, jq = (tid & 15) * 4;
+            const uint2 u = *(const uint2*)(W2 + (size_t)(k0 + kk) * ld2 + j0 + jq);
+            sb[kk][jq + 0] = bf16lo(u.x); sb[kk][jq + 1] = bf16hi(u.x); sb[kk][jq + 2] = bf16lo(u.y); sb[kk][jq + 3] = bf16hi(u.y);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const float4 a = *(const float4*)&sa[k][ty * 4];
+            const float4 b = *(const float4*)&sb[k][tx * 4];
+            const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint2 o;
+        o.x = pack_bf16x2(acc[i][0], acc[i][1]); o.y = pack_bf16x2(acc[i][2], acc[i][3]);
+        *(uint2*)(Wc + (size_t)(n0 + ty * 4 + i) * ldc + j0 + tx * 4) = o;
+    }
+}
+__global__ __launch_bounds__(64) void k_compose_proj_bias(const bf16_t* __restrict__ Wp, const float* __restrict__ b2,
+                                                          const float* __restrict__ bp, int C, float* __restrict__ bc) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= C) return;
+    float acc = 0.f;
+    if (b2)
+        for (int k = 0; k < C; ++k) acc = fmaf(bf16_to_f32(Wp[(size_t)n * C + k]), b2[k], acc);
+    bc[n] = acc + (bp ? bp[n] : 0.f);
+}
+int launch_compose_proj(hipStream_t st, const bf16_t* Wp, const bf16_t* W2, const float* b2, const float* bp, int C, bf16_t* Wc, float* bc) {
+    if (C < 64 || C % 64 || C > 16384) GYRE_FAIL(-1, "compose_proj: C must be a multiple of 64");
+    if ((((size_t)Wp | (size_t)W2 | (size_t)Wc) & 15) != 0) GYRE_FAIL(-1, "compose_proj: weights need 16-byte alignment");
+    hipLaunchKernelGGL(k_compose_proj, dim3(5 * C / 64, C / 64), dim3(256), 0, st, Wp, W2, C, Wc);
+    GYRE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_compose_proj_bias, dim3((C + 63) / 64), dim3(64), 0, st, Wp, b2, bp, C, bc);
+    GYRE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------
 // out[b][n] = sum_k f(x[b][k]) * W[n][k] + bias[n]   (f = SiLU when act_in_silu: applied to x IN PLACE by a tiny
 // elementwise launch first - inside the dot products it was evaluated once per output column, 367 M exponentials for
 // the batched time_emb_proj of a CFG batch of 16, which made this 46 MB weight stream take 200 us)

@@ -144,6 +144,12 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
         }
     }
     const char* a_tile = (const char*)(p.A + (size_t)m0 * p.lda);
+    // linear mode, second source (A | A2 split at C1 along K: a Transformer2D's proj_out folded into its FF2): the first K step at or past
+    // C1 REPLACES the first source's state - row offsets for lda2, the tile base moved back by C1 so that base + 2 kw stays the
+    // address - like the folded shortcut below.  step_src is called with non-decreasing kc and every piece of a step is requested
+    // before the next step is described, so the first source is dead by then; the split is looked at per K step, not per K slice
+    // (a split-K boundary falls anywhere).  One source: a_split is never reached.
+    int a_split = (MODE == GEMM_LINEAR && p.A2 != p.A) ? p.C1 : 0x7fffffff;
     const int Hlim = p.ups ? (p.Hup ? p.Hup : 2 * p.Hi) : p.Hi, Wlim = p.ups ? (p.Wup ? p.Wup : 2 * p.Wi) : p.Wi;
     const int ups = p.ups ? 1 : 0;
     // conv sources, based at the tile's first sample; a tile spans a handful of samples, so 32-bit offsets suffice
@@ -176,6 +182,15 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
         int kw;
         if (MODE == GEMM_LINEAR) {
             kw = kc * BK;
+            if (kw >= a_split) {                            // (wave-uniform, once)
+                a_split = 0x7fffffff;
+                a_tile = (const char*)(p.A2 + (size_t)m0 * p.lda2) - (size_t)p.C1 * 2;
+#pragma unroll
+                for (int i = 0; i < AP; ++i) {
+                    const unsigned rl = (unsigned)(min(m0 + 8 * (w + NW * i) + prow, p.M - 1) - m0);
+                    vo_a[i] = rl * (unsigned)p.lda2 * 2u + kvs * 16u;
+                }
+            }
             s.ab = live ? a_tile + (size_t)kw * 2 : (const char*)zero;
         } else {
             int c0;
@@ -562,7 +577,8 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
 }
 
 // Shapes the 4s kernels take: bf16 row-major output (or split-K slabs), 16-byte addressable rows, K steps that are
-// whole 64-channel chunks of one source (so a step never needs zero fill along K), at least one K step per split.
+// whole 64-channel chunks of one source (so a step never needs zero fill along K; linear mode: of A or of A2), at least one K
+// step per split.
 bool gemm4s_supports(const GemmParams& p, int cfg) {
     const GemmTile* t = gemm_tile(cfg);
     if (!t || t->kind != GEMM_K_4S) return false;
@@ -573,7 +589,12 @@ bool gemm4s_supports(const GemmParams& p, int cfg) {
     if (p.N % 8) return false;
     if (p.geglu && p.N % 32) return false;
     const int c1 = p.A2 ? p.C1 : (p.mode == GEMM_LINEAR ? p.K : p.Cin);
-    if (p.mode == GEMM_LINEAR) { if (p.K % BK || (p.A2 && p.A2 != p.A)) return false; }
+    if (p.mode == GEMM_LINEAR) {
+        if (p.K % BK) return false;
+        // second source: the 8-wave 256x320 tile only (config 24, the one the planner hands linear problems; the 4-wave tuning forms
+        // keep refusing it, like the folded shortcut), whole 64-channel steps on both sides of the split, 16-byte rows
+        if (p.A2 && p.A2 != p.A && (cfg != 24 || p.C1 <= 0 || p.C1 >= p.K || p.C1 % BK || p.lda2 % 8 || ((size_t)p.A2 & 15))) return false;
+    }
     else if (p.Cin % BK || c1 % BK || p.K != 9 * p.Cin + p.sc_K || (p.sc_K && (p.sc_K % BK || cfg != 24))) return false;
     if (p.mode == GEMM_CONV3) {
         // a tile's rows span at most 256 / (Ho*Wo) + 2 samples; sources are addressed relative to the first of them with

@@ -127,14 +127,19 @@ size_t gyre_unet_workspace_bytes(gyre_unet* h, int B, int H, int W, int S) {
     const bool hu = h->hint_uniform_t, hp = h->hint_cfg_pairs;
     size_t peak = 0;
     bool ok = true;
+    // ... and proj_out folded into FF2 or not (a call with debug taps, or one that found no memory for the composed weights, keeps the
+    // two launches: Exec::proj_out_folds)
     for (int cached = 0; ok && cached <= (cached_too ? 1 : 0); ++cached)
-        for (int pairs = 0; ok && pairs <= 1; ++pairs) {
-            if (h->run(true, nullptr, nullptr, 0, nullptr, nullptr, 0, B, H, W, S, nullptr, 0, nullptr, 0, nullptr, cached != 0, nullptr, 0, 0,
-                       nullptr, nullptr, 0, pairs))
-                ok = false;
-            else
-                peak = std::max(peak, h->ex.arena.peak);
-        }
+        for (int pairs = 0; ok && pairs <= 1; ++pairs)
+            for (int fold = 0; ok && fold <= 1; ++fold) {
+                h->ex.pout_fold_dry = fold;
+                if (h->run(true, nullptr, nullptr, 0, nullptr, nullptr, 0, B, H, W, S, nullptr, 0, nullptr, 0, nullptr, cached != 0, nullptr, 0, 0,
+                           nullptr, nullptr, 0, pairs))
+                    ok = false;
+                else
+                    peak = std::max(peak, h->ex.arena.peak);
+            }
+    h->ex.pout_fold_dry = -1;
     h->hint_uniform_t = hu; h->hint_cfg_pairs = hp;     // (a pending input-gradient pair IS dropped by a dry pass: it shares the executor)
     if (!ok) return 0;
     if (h->ws_memo.size() > 64) h->ws_memo.clear();
@@ -562,6 +567,13 @@ int gyre_op_conv3x3_shortcut(void* st, const void* x, int B, int H, int W, int C
     if (bias_sc) TRY(launch_add_f32((hipStream_t)st, bcat, bias_sc, (size_t)Cout));
     p.W = wcat; p.bias = bcat;
     return launch_gemm((hipStream_t)st, p);
+}
+// The composed weights of a Transformer2D's proj_out folded into its last FF2, as the model runtime makes them (launch_compose_proj):
+// wc_out [C][5C] = [Wp W2 | Wp] in the storage type, bc_out [C] = Wp b2 + bp in fp32.  Wp [C][C], W2 [C][4C] storage rows; C % 64 == 0.
+int gyre_op_compose_proj_out(void* st, const void* wp, const void* w2, const float* b2, const float* bp, int C, void* wc_out, float* bc_out) {
+    if (!wp || !w2 || !wc_out || !bc_out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (C < 64 || C % 64 || C > 16384) GYRE_FAIL(GYRE_ERR_INVALID, "compose_proj_out: C must be a multiple of 64");
+    return launch_compose_proj((hipStream_t)st, (const bf16_t*)wp, (const bf16_t*)w2, b2, bp, C, (bf16_t*)wc_out, bc_out);
 }
 int gyre_op_conv3x3_nchw(void* st, const void* x, int B, int H, int W, int Cin, const void* w, int Cout, const float* bias, void* y,
                          int y_dtype, int force_tiles) {

@@ -181,6 +181,28 @@ struct Store {
         en.version = weights_version;
         return &en;
     }
+    // a Transformer2D's proj_out composed with the FF2 of its last block (Exec::transformer): Wc [C][5C] = [Wp W2 | Wp] and
+    // bc = Wp b2 + bp (launch_compose_proj), keyed by the proj_out weight, made on first use and refreshed after any weight change like
+    // the other derived copies (SD1.5: 124 MB per UNet handle).  An optimisation only: when the buffer cannot be allocated
+    // the answer is "no fold" (nullptr) for this weight version - the caller takes the two launches, and nothing retries before a
+    // weight is set again.
+    struct PfEntry { bf16_t* w = nullptr; float* b = nullptr; size_t elems = 0; uint64_t version = 0, no_fold_version = 0; };
+    std::unordered_map<const void*, PfEntry> pf_cache;
+    PfEntry* pf_lookup(const void* wp, int C, bool* fresh) {
+        PfEntry& en = pf_cache[wp];
+        if (en.no_fold_version == weights_version) return nullptr;
+        const size_t elems = (size_t)C * 5 * C;
+        if (!en.w || en.elems < elems) {
+            if (en.w) { dfree(en.w); en.w = nullptr; en.elems = 0; }   // superseded buffer: released now
+            const size_t wbytes = (elems * 2 + 255) / 256 * 256;
+            char* base = (char*)dmalloc(wbytes + ((size_t)C * 4 + 255) / 256 * 256, false);
+            if (!base) { (void)hipGetLastError(); en.no_fold_version = weights_version; return nullptr; }
+            en.w = (bf16_t*)base; en.b = (float*)(base + wbytes); en.elems = elems; en.version = 0;
+        }
+        *fresh = en.version == weights_version;
+        en.version = weights_version;
+        return &en;
+    }
     ~Store() { for (void* a : allocs) (void)hipFree(a); }
     // returns the cached buffer for `w` (allocating `bytes` on first use) and whether its content is current
     bf16_t* wt_lookup(const void* w, size_t bytes, bool* fresh) {
@@ -416,6 +438,8 @@ struct Exec {
     int cs_unit = 0; // channels per GroupNorm-statistics unit the producers emit (0 = producers emit none; set per call)
     int tome_r = 0;  // ToMe: keys / values merged per self-attention (0 = off; reference option "tome", nonfree/tome_unet.py)
     int tiling = 0;  // circular conv padding: bit 0 along x, bit 1 along y (reference option "tiling", unified_pipeline.py:1671-1712)
+    bool keep_proj_out = false;  // debug taps are set for this call: every Transformer2D keeps proj_out as its own launch
+    int pout_fold_dry = -1;      // workspace sizing: dry passes with the proj_out fold off (0) and on (1); -1 = the rule alone
 
     bool dry() const { return arena.dry; }
     int alloc(Tn& t, int B, int H, int W, int C, size_t elt = 2) {
@@ -625,6 +649,7 @@ struct Exec {
                Tn* cs_for = nullptr) {
         GemmParams p;
         p.A = x; p.lda = lda; p.A2 = x2; p.lda2 = lda2; p.C1 = C1; p.mode = GEMM_LINEAR;
+        if (dry() && lda2 > 0) { p.A = (const bf16_t*)(uintptr_t)256; p.A2 = (const bf16_t*)(uintptr_t)512; }   // (planning: two distinct aligned sources)
         p.W = w; p.K = K; p.N = N; p.M = M; p.bias = bias; p.residual = residual; p.ldr = ldr; p.geglu = geglu;
         p.out = y; p.ldc = ldc; p.out_mode = OUT_BF16;
         p.ar_ok = store != nullptr; p.no_ar = cs_for != nullptr;      // (the A-resident kernel leaves no column statistics)
@@ -927,6 +952,43 @@ struct Exec {
         free(b); free(sc);
         return 0;
     }
+    // Does a Transformer2D of C channels over HW tokens per sample run its proj_out inside the last block's FF2 (proj_out_folded)?
+    // Inference path with a weight store, whole 64-channel K steps on both sides of the split, no circular padding request, no debug
+    // taps; tuning bit 28 of gyre_debug_gemm_ablation = off.  The rule looks at C and the level only, never at the batch: every
+    // split of a request takes the same path (batch-invariant planning stays bit-exact across splits).
+    // Measured per level (SD1.5, batch 16, event times of tools/unet_layers.py with bit 28 on / off, profiles/r07_unet_layers.md;
+    // FF2 -> folded FF2, and the proj_out launch that goes; same kernel and split factor before and after at every level):
+    //   64x64 (C 320,  k_gemm8 256x320):          78.9 -> 88.7 us, proj_out 42 us gone:  -32 us per site
+    //   32x32 (C 640,  k_gemm8 128x160):          62.5 -> 77.9 us, proj_out 28 us gone:  -13 us per site
+    //   16x16 (C 1280, k_gemm4s in 4 K slices):   59.0 -> 68.3 us, proj_out 28 us gone:  -19 us per site
+    //   8x8   (mid,    k_gemm_sm):                37.2 -> 42.8 us, proj_out 14 us gone:   -8 us
+    // Every level wins, so no level is excluded; UNet call 16.56 -> 16.28 ms at batch 16, 5.52 -> 5.44 ms at batch 2 (interleaved
+    // A/B, tools/ab_unet.py), 16 launches fewer.
+    // Floor: C x HW >= 8192 per sample.  Every level of SD1.x / SDXL is far above it (smallest measured: 8x8 at C 1280 = 81920);
+    // below it lie only the levels of the tiny test models at 16x16 latents, where nothing was measured and where the suite pins the
+    // inference path and the activation-keeping pass (which keeps the two launches) to the same bits (tests/test_gpu_vjp.py).
+    bool proj_out_folds(int C, int HW) const {
+        if (!store || tiling || keep_proj_out || C % 64 || (long)C * HW < 8192 || (gemm_planner_state() & GEMM_DBG_NO_POUT_FOLD)) return false;
+        if (dry() && pout_fold_dry >= 0) return pout_fold_dry != 0;
+        return true;
+    }
+    // out = [ff | h] Wc^T + bc + x on the composed weights; *done = false (nothing launched, `out` not allocated) when the composed
+    // weights cannot be allocated: the caller goes on with FF2 and proj_out
+    int proj_out_folded(const Tn& ff, const Tn& h, const Tn& x, const TransW& w, const TBlockW& bw, Tn& out, bool* done) {
+        const int C = w.c, M = x.rows();
+        const bf16_t* wc = nullptr; const float* bc = nullptr;
+        if (!dry()) {
+            bool fresh = false;
+            Store::PfEntry* e = store->pf_lookup(w.pout, C, &fresh);
+            if (!e) return 0;
+            if (!fresh) TRY(launch_compose_proj(st, w.pout, bw.ff2, bw.ff2b, w.poutb, C, e->w, e->b));
+            wc = e->w; bc = e->b;
+        }
+        TRY(alloc(out, x.B, x.H, x.W, C));
+        TRY(linear(ff.p, 4 * C, h.p, C, 4 * C, M, 5 * C, wc, C, bc, x.p, C, 0, out.p, C, nullptr, &out));
+        *done = true;
+        return 0;
+    }
     // x_full != nullptr (inference only): x holds HALF the batch - the two halves of a CFG-parallel call are identical up
     // to the first cross-attention (reference unet/cfg.py:49-57: cat[x, x] against cat[uncond, cond]) - so GroupNorm, proj_in
     // and the first block's self-attention run once per pair; their result, the block input and its row statistics are then
@@ -980,8 +1042,20 @@ struct Exec {
                 TRY(alloc(ff, B, x.H, x.W, 4 * C));
                 TRY(ln_linear(h, l3, bw.ff1, 8 * C, bw.ff1b, 1, ff.p, 4 * C));
                 free(rs2.t);
-                TRY(alloc(h2, B, x.H, x.W, C));
                 const bool more = bi + 1 < w.blocks.size();
+                if (!more && proj_out_folds(C, x.H * x.W)) {
+                    // Round 7: proj_out rides inside the last block's FF2.  Nothing non-linear sits between the two, so
+                    //   out = (ff W2^T + b2 + h) Wp^T + bp + x = [ff | h] [Wp W2 | Wp]^T + (Wp b2 + bp) + x
+                    // is ONE launch over K = 5C on weights composed once per weight version (Store::pf_lookup): no proj_out launch,
+                    // no h2 tensor, one rounding less.  The launch leaves the column statistics proj_out left (cs_for = &out).
+                    bool done = false;
+                    TRY(proj_out_folded(ff, h, x, w, bw, out, &done));
+                    if (done) {
+                        free(ff); free(h);
+                        return 0;
+                    }
+                }
+                TRY(alloc(h2, B, x.H, x.W, C));
                 TRY(linear(ff.p, 4 * C, nullptr, 0, 0, M, 4 * C, bw.ff2, C, bw.ff2b, h.p, C, 0, h2.p, C, more ? &rs3 : nullptr));
                 if (more) rs_h = rs3;
                 free(ff); free(h);
@@ -1290,6 +1364,7 @@ struct gyre_unet {
         vjp.valid = false;                           // the arena is being reused: a pending reverse sweep has lost its activations
         ex.st = st; ex.batch = B;
         ex.cs_unit = gn_unit;                        // producers leave GroupNorm statistics where they can (attach_colstats)
+        ex.keep_proj_out = !dry && !taps.empty();
         Exec& e = ex;
         const int D = c.cross_attention_dim;
         const bool cached = use_ctx_cache;

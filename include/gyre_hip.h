@@ -388,6 +388,8 @@ int gyre_debug_xattn_stamps(void* dev_buf);
  * to_q -> attention -> to_out of SD1.x's 64x64 level in one launch): the three-launch chain as before.  (Bit 7 - the small kernel's
  * LayerNorm fold - went with the code it switched on; the bit is reused:) bit7 = the 1x1 shortcut of a channel-changing / concat resnet
  * stays its own launch instead of riding inside conv2 as extra K steps of the pipelined tile (round 6).
+ * Round 7: bit28 = a Transformer2D's proj_out stays its own launch instead of riding inside the FF2 of its last block as extra K
+ * steps on composed weights.
  * Epilogue ablations (garbage): bit3 = no GELU, bit4 = no stores.
  * These switches are PER CALLING THREAD (thread-local, like gyre_set_batch_invariant): they never change what another thread's
  * handle computes. */
@@ -527,6 +529,11 @@ int gyre_op_conv3x3(void* stream, const void* x, int B, int Hi, int Wi, int Cin,
 int gyre_op_conv3x3_shortcut(void* stream, const void* x, int B, int H, int W, int Cin, const void* w_krsc, int Cout, const float* bias,
                              const void* sx, int C1, const void* sx2, int C2, const void* w_sc, const float* bias_sc, void* ws,
                              size_t ws_bytes, void* y);
+/* The composed weights of a Transformer2D's proj_out folded into the FF2 of its last block (round 7), as the model handles make them
+ * once per weight version: wc_out [C][5C] = [Wp W2 | Wp] in the storage type (fp32 sums over k ascending, one rounding), bc_out [C] =
+ * Wp b2 + bp in fp32 (b2 / bp may be NULL).  wp [C][C] and w2 [C][4C] are storage rows (gyre_op_repack_linear_weight); C % 64 == 0. */
+int gyre_op_compose_proj_out(void* stream, const void* wp, const void* w2, const float* b2, const float* bp, int C, void* wc_out,
+                             float* bc_out);
 /* The output convolution of the UNet / VAE decoder (3x3, stride 1, zero padding 1, Cout <= 16) written as NCHW y
  * [B][Cout][H][W] of dtype y_dtype (0 f32, 1 bf16, 2 f16), as the models' last launch does: the dedicated kernel
  * (kernels_conv_out.hip) where Cin % 64 == 0, the tile kernels otherwise; force_tiles != 0 takes the tile kernels anyway. */
