@@ -70,6 +70,14 @@ class T2ICfg(C.Structure):
                 ("nums_rb", C.c_int32), ("ksize", C.c_int32), ("sk", C.c_int32), ("use_conv", C.c_int32)]
 
 
+class CtrlCfg(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("n_levels", C.c_int32), ("block_out_channels", C.c_int32 * MAX_LEVELS),
+                ("layers_per_block", C.c_int32), ("attn_levels", C.c_int32 * MAX_LEVELS), ("num_heads", C.c_int32 * MAX_LEVELS),
+                ("transformer_depth", C.c_int32 * MAX_LEVELS), ("cross_attention_dim", C.c_int32), ("norm_num_groups", C.c_int32),
+                ("use_linear_projection", C.c_int32), ("flip_sin_to_cos", C.c_int32), ("freq_shift", C.c_float),
+                ("cond_channels", C.c_int32), ("cond_embed_channels", C.c_int32 * 4)]
+
+
 class GemmTestArgs(C.Structure):
     """gyre_gemm_test_args (include/gyre_hip.h): one GEMM / conv launch field by field, for tests and tuning."""
     _fields_ = [(n, C.c_int32) for n in ("conv", "M", "K", "N", "geglu", "B", "Hi", "Wi", "Cin", "stride", "pad", "ups", "Hup", "Wup",
@@ -146,6 +154,16 @@ _SIGS = {
     "gyre_t2i_finalize": (_i, [_vp, _vp]),
     "gyre_t2i_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "gyre_t2i_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(_vp), _i, _i]),
+    "gyre_ctrl_create": (_i, [C.POINTER(CtrlCfg), _i, C.POINTER(_vp)]),
+    "gyre_ctrl_destroy": (None, [_vp]),
+    "gyre_ctrl_num_params": (_i, [_vp]),
+    "gyre_ctrl_param_key": (C.c_char_p, [_vp, _i]),
+    "gyre_ctrl_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
+    "gyre_ctrl_finalize": (_i, [_vp, _vp]),
+    "gyre_ctrl_bind_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "gyre_ctrl_bind": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _sz]),
+    "gyre_ctrl_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "gyre_ctrl_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _sz, C.POINTER(_f), _i, _i, _i, C.POINTER(_vp), _i, _i]),
     "gyre_prof_set_mask": (_i, [C.c_uint64]),
     "gyre_prof_num_classes": (_i, []),
     "gyre_prof_class_name": (C.c_char_p, [_i]),
@@ -216,6 +234,8 @@ _SIGS = {
     "gyre_op_pixel_unshuffle8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "gyre_op_avgpool2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "gyre_op_relu": (_i, [_vp, _vp, _sz]),
+    "gyre_op_silu": (_i, [_vp, _vp, _sz]),
+    "gyre_op_ctrl_emit": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _i]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

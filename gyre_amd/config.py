@@ -100,6 +100,59 @@ def tiny_vae() -> VAEConfig:
     return VAEConfig(block_out_channels=(32, 64, 64, 64), sample_size=64)
 
 
+@dataclass(frozen=True)
+class ControlNetConfig:
+    """diffusers ``ControlNetModel`` config.json fields the native control model reads: the encoder half of the UNet's, the channels
+    of the hint image and the widths of its conditioning embedding.  Also answers ``config.get(name, default)`` - the reference asks
+    ``controlnet.config.get("global_pool_conditions", False)`` (unified_pipeline.py:983)."""
+    in_channels: int = 4
+    block_out_channels: Tuple[int, ...] = (320, 640, 1280, 1280)
+    layers_per_block: int = 2
+    attn_levels: Tuple[bool, ...] = (True, True, True, False)
+    num_heads: Tuple[int, ...] = (8, 8, 8, 8)
+    cross_attention_dim: int = 768
+    norm_num_groups: int = 32
+    transformer_depth: Tuple[int, ...] = (1, 1, 1, 1)
+    use_linear_projection: bool = False
+    flip_sin_to_cos: bool = True
+    freq_shift: float = 0.0
+    conditioning_channels: int = 3
+    conditioning_embedding_out_channels: Tuple[int, ...] = (16, 32, 96, 256)
+    controlnet_conditioning_channel_order: str = "rgb"
+    global_pool_conditions: bool = False
+    _diffusers_version: str = "0.16.0"
+
+    @property
+    def time_embed_dim(self) -> int:
+        return self.block_out_channels[0] * 4
+
+    @property
+    def n_residuals(self) -> int:
+        """down residuals: conv_in, one per layer, one per downsampler (12 for SD1.x); the mid residual comes on top"""
+        n = len(self.block_out_channels)
+        return 1 + n * self.layers_per_block + (n - 1)
+
+    def get(self, name, default=None):
+        return getattr(self, name, default)
+
+    def __contains__(self, name):
+        return hasattr(self, name)
+
+    def to_dict(self):
+        return asdict(self)
+
+
+def sd15_controlnet(**kw) -> ControlNetConfig:
+    """The SD1.x ControlNet (lllyasviel/sd-controlnet-*, control_v11*): SD1.x encoder, 3-channel hint, embedding 16/32/96/256."""
+    return ControlNetConfig(**kw)
+
+
+def tiny_controlnet(**kw) -> ControlNetConfig:
+    """The same topology at the widths of tiny_unet, conditioning embedding 16/32/48/64."""
+    return ControlNetConfig(**{**dict(block_out_channels=(32, 64, 128, 128), num_heads=(2, 2, 4, 4), cross_attention_dim=64,
+                                      conditioning_embedding_out_channels=(16, 32, 48, 64)), **kw})
+
+
 class T2IConfig(dict):
     """Configuration of a T2I adapter: a mapping that also reads as attributes - the reference asks both ``"cin" in
     model.config`` and ``model.config.cin`` (unified_pipeline.py:869)."""

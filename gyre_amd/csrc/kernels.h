@@ -143,6 +143,13 @@ int launch_relu(hipStream_t st, bf16_t* x, size_t n);                      // in
 // y NCHW [B][C][HW] of a runtime dtype = the first C channels of x NHWC [B][HW][Cpad]
 int launch_nhwc_to_nchw(hipStream_t st, const bf16_t* x, int B, int C, int HW, int Cpad, void* y, int dtype);
 
+// ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
+int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
+// out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):
+// accumulate == 0 assigns and writes every other sample of `out` as zero, accumulate == 1 adds and leaves the others alone
+int launch_ctrl_emit(hipStream_t st, const bf16_t* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
+                     int out_dtype, int out_B, int out_b0);
+
 // ---- MFMA GEMM / implicit-GEMM conv (kernels_gemm.hip) -------------------------
 enum { GEMM_LINEAR = 0, GEMM_CONV3 = 1 };
 enum { OUT_BF16 = 0, OUT_NCHW = 1, OUT_BF16_T = 2 };

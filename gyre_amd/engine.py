@@ -26,10 +26,12 @@ into PNG artifacts.  What this class has to honour is therefore exactly what the
   * no-op memory knobs (attention / VAE slicing, xformers): 288 GB of HBM3E, the whole batch stays resident.
 
 Hint images handled by a T2I adapter (gyre_amd/t2i.py GyreHipT2IAdapter through the engine's ``hintset_manager``) run natively:
-the adapter once per request, its states added inside the UNet on every step (gyre_amd/hints.py).  Features outside the native
-hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py): depth maps / depth UNets, ControlNet
-hint handlers, style adapters and co-adapters, masked hints, hints together with hires fix / grafted inpaint / CLIP guidance /
-shard_devices, textual-inversion token embeddings.  CLIP guidance
+the adapter once per request, its states added inside the UNet on every step (gyre_amd/hints.py).  Hint images handled by a ControlNet
+(gyre_amd/controlnet.py GyreHipControlNet) run natively as well: the hint image and the text context are bound once per request, the
+control model runs once per UNet evaluation and its residuals go to the UNet's residual inputs (schedulers.UNetWithControlnet).
+Features outside the native hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py): depth maps /
+depth UNets, foreign hint handlers, style adapters and co-adapters, masked hints, hints together with hires fix / grafted inpaint /
+CLIP guidance / shard_devices, ControlNet hints with a 9-channel inpaint UNet, textual-inversion token embeddings.  CLIP guidance
 is implemented (gyre_amd/clipguided.py over the native input-gradient sweeps).  ``lora=`` takes LoRA files (kohya-ss, diffusers) and,
 as the reference routes them (unified_pipeline.py:2210-2233: what ``detect_lora_type`` refuses goes to ``apply_lycoris``), LyCORIS files
 (LoCon, LoHa, LoKr, full diff; gyre_amd/lycoris.py): one attach for the whole request, every touched weight repacked once on the
@@ -342,9 +344,11 @@ class GyreUnifiedPipeline:
 
     def _hints(self, hint_images, mask_image) -> list:
         """The reference's hint loop (unified_pipeline.py:1994-2047) for what is native: every hint image needs exactly one model
-        from the hintset manager and that model must be a GyreHipT2IAdapter.  Depth hints routed to a depth UNet and ControlNet
-        handlers stay NotImplementedError; a hint type nobody handles is the reference's EnvironmentError."""
-        from .hints import T2IHint
+        from the hintset manager and that model must be a GyreHipT2IAdapter (-> hints.T2IHint) or a GyreHipControlNet
+        (-> hints.ControlNetHint; same priority and weight mapping).  Depth hints routed to a depth UNet and foreign handlers stay
+        NotImplementedError; a hint type nobody handles is the reference's EnvironmentError."""
+        from .controlnet import GyreHipControlNet
+        from .hints import ControlNetHint, T2IHint
         from .t2i import GyreHipT2IAdapter
         hints = []
         for hint_image in hint_images or ():
@@ -362,6 +366,12 @@ class GyreUnifiedPipeline:
             if len(models) != 1:
                 raise ValueError(f"Unknown set of hint models: {models.keys()}")
             _, model = models.popitem()
+            if isinstance(model, GyreHipControlNet):
+                if mask_image is not None:
+                    raise NotImplementedError("ControlNet hints together with a mask (the reference resizes it for the hint with an unpinned lanczos)")
+                hints.append(ControlNetHint(model, hint_image.image, mask=None, weight=weight, soft_injection=priority != "balanced",
+                                            cfg_only=priority == "hint"))
+                continue
             if not isinstance(model, GyreHipT2IAdapter):
                 raise NotImplementedError(f"hint model {type(model).__name__} (ControlNet and foreign adapters are outside the native hot path)")
             hints.append(T2IHint(model, hint_image.image, mask=None, weight=weight, soft_injection=priority != "balanced",
@@ -386,9 +396,12 @@ class GyreUnifiedPipeline:
                  cfg_execution: str = "parallel"):
         if depth_map is not None:
             raise NotImplementedError("depth-map conditioning (depth UNet) is outside the native hot path")
-        t2i_hints = self._hints(hint_images, mask_image)
-        if t2i_hints and len(self._shard_devices) > 1:
-            raise NotImplementedError("hint images together with shard_devices (the adapter states live on one device slot)")
+        from .hints import ControlNetHint
+        all_hints = self._hints(hint_images, mask_image)
+        t2i_hints = [h for h in all_hints if not isinstance(h, ControlNetHint)]
+        controlnet_hints = [h for h in all_hints if isinstance(h, ControlNetHint)]
+        if all_hints and len(self._shard_devices) > 1:
+            raise NotImplementedError("hint images together with shard_devices (the adapter states and the bound control models live on one device slot)")
         if token_embeddings:
             raise NotImplementedError("textual-inversion token embeddings are outside the native hot path")
         if tiling not in (False, None, True, "x", "y", "xy"):
@@ -487,6 +500,8 @@ class GyreUnifiedPipeline:
             request.update(added_cond=added, uncond_added_cond=uadded)
         if t2i_hints:
             request.update(t2i_hints=[h.to(dev) for h in t2i_hints])
+        if controlnet_hints:
+            request.update(controlnet_hints=[h.to(dev) for h in controlnet_hints])
         if len(self._shard_devices) > 1 and B > 1 and not clip_kw and not lora and not self._tome and not tiling:
             # one request over several device slots (engine option "shard_devices"); progress / cancellation are polled once
             # per request here: the replicas run their loops concurrently and a per-step callback has no single owner.

@@ -1,11 +1,15 @@
-"""Host side of hint-image conditioning with T2I adapters.
+"""Host side of hint-image conditioning with T2I adapters and ControlNets.
 
   T2IHint              UnifiedPipelineHint_T2i, standard path       unified_pipeline.py:746-786, 906-919
   combine_t2i_states   UNetWithT2I.__init__, standard branch        unet/core.py:128-206 (with AdapterStateList, :67-93)
+  ControlNetHint       UnifiedPipelineHint_Controlnet               unified_pipeline.py:957-1058 (run per step by
+                                                                    schedulers.UNetWithControlnet, unet/core.py:40-64)
 
 The adapter itself runs natively (gyre_amd/t2i.py); what is here is the per-level weighting of its states and the sums the CFG
 wrappers receive.  Style adapters, co-adapters with their fuser, and masked hints (the mask resize is an unpinned lanczos3) raise
-NotImplementedError.
+NotImplementedError.  The ControlNet itself runs natively too (gyre_amd/controlnet.py): its hint only decides the per-residual scales,
+which half of a CFG call the model sees and where in the shared residual buffers its outputs land; masked ControlNet hints raise for
+the same reason.
 """
 from __future__ import annotations
 
@@ -84,3 +88,69 @@ def combine_t2i_states(hints: Sequence) -> Optional[Dict[str, List[Tensor]]]:
     out = {"u": [sum(i) for i in zip(*us)], "g": [sum(i) for i in zip(*gs)]}
     out["f"] = [torch.cat([u, g], dim=0) for u, g in zip(out["u"], out["g"])]
     return out
+
+
+class ControlNetHint:
+    """One hint image bound to its ControlNet.  ``run`` is called once per UNet evaluation by schedulers.UNetWithControlnet with the
+    CFG side of the calling stack: "g" (guided), "u" (unconditional) or "f" (one call over cat[unconditional, guided])."""
+
+    def __init__(self, model, image: Tensor, mask: Optional[Tensor] = None, weight: float = 1.0, soft_injection: bool = False,
+                 cfg_only: bool = False):
+        if image.ndim == 3:
+            image = image[None]
+        if model.config.get("global_pool_conditions", False):
+            cfg_only, soft_injection, mask = True, False, None        # (the reference ignores a mask here; the alpha plane below too)
+            image = image[:, :3] if image.shape[1] == 4 else image
+        if mask is None and image.shape[1] == 4:
+            mask = image[:, [3]]
+        if mask is not None:
+            mask = normalise_tensor(mask, 1)
+            if mask.mean() == 1.0 and mask.std() == 0.0:              # pure ones: the reference discards it
+                mask = None
+        if mask is not None:
+            raise NotImplementedError("masked ControlNet hints (the reference resizes the mask with an unpinned lanczos3)")
+        self.model, self.image = model, normalise_tensor(image, model.config.get("conditioning_channels", 3))
+        self.weight, self.soft_injection, self.cfg_only = weight, soft_injection, cfg_only
+        self._token = object()                                        # who bound the model last: (token, side)
+        self._ctx = {}                                                # side -> (the stack's context, the context the model sees)
+
+    def scales(self):
+        """weight x logspace(-1, 0, N + 1)[k] for down residual k and the last point for the mid residual; the weight alone without
+        soft injection (N + 1 = 13 for SD)."""
+        n = self.model.config.n_residuals + 1
+        if not self.soft_injection:
+            return [float(self.weight)] * n
+        return [float(self.weight) * float(lw) for lw in torch.logspace(-1, 0, n)]
+
+    def to(self, device=None, dtype=None):
+        self.image = self.image.to(device, dtype)
+        return self
+
+    def _bind(self, side, ctx):
+        """The embedding of the image and the projected context live in the model, one request at a time: bind again only when
+        another hint, another side (sequential CFG alternates two contexts on one model) or another request used it last."""
+        kept = self._ctx.get(side)
+        if kept is None or kept[0] is not ctx:
+            seen = ctx.chunk(2)[-1].contiguous() if (self.cfg_only and side == "f") else ctx
+            kept = self._ctx[side] = (ctx, seen)
+        owner = getattr(self.model, "_bind_owner", None)
+        if owner is None or owner[0] is not self._token or owner[1] != side or owner[2] is not kept[1] or self.model._bound is None:
+            self.model.bind(self.image, kept[1])
+            self.model._bind_owner = (self._token, side, kept[1])
+
+    def run(self, side: str, latents: Tensor, t, encoder_hidden_states: Tensor, out, accumulate: bool):
+        """Adds (accumulate) or assigns this hint's residuals for one UNet call into ``out`` (N + 1 NCHW buffers at the batch of
+        ``latents``).  False when the hint contributes nothing on this side (cfg_only on "u")."""
+        if latents.shape[1] == 9:
+            raise NotImplementedError("ControlNet hints with a 9-channel inpaint UNet (the reference resizes its mask with an unpinned lanczos)")
+        x, B = latents[:, 0:4], latents.shape[0]
+        if self.cfg_only and side == "u":
+            return False
+        self._bind(side, encoder_hidden_states)
+        if self.cfg_only and side == "f":                             # the guided half only, into the upper half; the lower half is zero
+            x = x.chunk(2)[-1]
+            t = t.chunk(2)[-1] if isinstance(t, torch.Tensor) and t.ndim > 0 and t.numel() > 1 else t
+            self.model(x, t, scales=self.scales(), out=out, accumulate=accumulate, out_batch=B, out_offset=B - x.shape[0])
+        else:
+            self.model(x, t, scales=self.scales(), out=out, accumulate=accumulate)
+        return True

@@ -262,20 +262,23 @@ class GyrePipeline:
             leaf.blend_orig, leaf.blend_mask = orig, leaf.latent_mask
 
     def _bind_leaf(self, leaf, *, text_embeddings, uncond_embeddings, guidance_scale, cfg_execution, B, added_cond,
-                   uncond_added_cond, cfg_embeddings, clip_mode=None, t2i_states=None):
+                   uncond_added_cond, cfg_embeddings, clip_mode=None, t2i_states=None, controlnet_hints=None):
         """UNet stack of one leaf: embeddings (+ T2I-adapter states) -> extra channels -> CFG (unified_pipeline.py:2235-2337,
         2408-2430).  t2i_states: combine_t2i_states' {"g", "u", "f"} at batch B / B / 2B (reference UNetWithT2I, unet/core.py:96-218:
-        "g" to the conditional side, "u" to the unconditional one, "f" to the CFG-parallel call)."""
+        "g" to the conditional side, "u" to the unconditional one, "f" to the CFG-parallel call).  controlnet_hints: the request's
+        hints.ControlNetHint objects; each side gets its own UNetWithControlnet (and residual buffers) between the embeddings and the
+        UNet, told which side it is (the reference's cfg_meta)."""
         st = t2i_states or {}
 
-        def bind(emb, added=None, states=None):
-            u = S.UNetWithEmbeddings(leaf.unet, emb, added) if states is None else S.UNetWithEmbeddings(leaf.unet, emb, added, states)
+        def bind(emb, added=None, states=None, side=None):
+            unet = S.UNetWithControlnet(leaf.unet, controlnet_hints, side) if (controlnet_hints and side) else leaf.unet
+            u = S.UNetWithEmbeddings(unet, emb, added) if states is None else S.UNetWithEmbeddings(unet, emb, added, states)
             return S.UnetWithExtraChannels(u, leaf.extra) if leaf.extra is not None else u
 
         if guidance_scale > 1.0:
             if cfg_execution == "sequential":
-                leaf.eps_unet = S.CFGUNet_Sequential(bind(text_embeddings, added_cond, st.get("g")),
-                                                     bind(uncond_embeddings, uncond_added_cond, st.get("u")), guidance_scale, B)
+                leaf.eps_unet = S.CFGUNet_Sequential(bind(text_embeddings, added_cond, st.get("g"), "g"),
+                                                     bind(uncond_embeddings, uncond_added_cond, st.get("u"), "u"), guidance_scale, B)
             else:
                 both = None
                 if added_cond is not None:
@@ -284,9 +287,9 @@ class GyrePipeline:
                 # tensor identity, and the leaves of a hires / graft tree alternate on the same UNet every step
                 if cfg_embeddings.get("both") is None:
                     cfg_embeddings["both"] = torch.cat([uncond_embeddings, text_embeddings])
-                leaf.eps_unet = S.CFGUNet_Parallel(bind(cfg_embeddings["both"], both, st.get("f")), guidance_scale, B)
+                leaf.eps_unet = S.CFGUNet_Parallel(bind(cfg_embeddings["both"], both, st.get("f"), "f"), guidance_scale, B)
         else:
-            leaf.eps_unet = bind(text_embeddings, added_cond, st.get("g"))
+            leaf.eps_unet = bind(text_embeddings, added_cond, st.get("g"), "g")
         leaf.clip_mode = clip_mode
         if clip_mode is not None:       # ClipGuidedMode.wrap_guidance_unet over the conditional / unconditional stems
             cfg = guidance_scale > 1.0
@@ -333,12 +336,25 @@ class GyrePipeline:
                  clip_gradient_maxloss: Optional[float] = None, vae_cutouts: Optional[int] = None,
                  approx_cutouts: Optional[int] = None, no_cutouts=None, clip_input_ids: Optional[Tensor] = None,
                  clip_text_embeddings: Optional[Tensor] = None, clip_config: Optional[CG.ClipGuidanceConfig] = None,
-                 t2i_hints: Optional[Sequence] = None):
+                 t2i_hints: Optional[Sequence] = None, controlnet_hints: Optional[Sequence] = None):
         """clip_*: CLIP guidance (reference keywords of UnifiedPipeline.__call__, unified_pipeline.py:1756-1764).  The text
         side comes as ``clip_input_ids`` (encoded by clip_model.get_text_features) or ``clip_text_embeddings`` [B, D].
         t2i_hints: gyre_amd.hints.T2IHint objects (hint image bound to its adapter).  Their states are computed once per request
         and added inside the UNet's down path on every step.  Together with hires fix, a grafted inpaint pair or CLIP guidance
-        they are refused (NotImplementedError) before any device work."""
+        they are refused (NotImplementedError) before any device work.
+        controlnet_hints: gyre_amd.hints.ControlNetHint objects (hint image bound to its native ControlNet).  Each model runs once per
+        UNet evaluation on the latents, the timestep and the text context of that evaluation; the hint image and the context are bound
+        once per request.  Refused (NotImplementedError) together with a mask, a 9-channel inpaint UNet, hires fix, a grafted inpaint
+        pair or CLIP guidance."""
+        if controlnet_hints:
+            if clip_guidance_scale and self.clip_model is not None and self.feature_extractor is not None:
+                raise NotImplementedError("ControlNet hints together with CLIP guidance (no input gradients through the control model)")
+            if mask_image is not None:
+                why = "grafted inpaint" if (self.inpaint_unet is not None and self.inpaint_unet is not self.unet and self.grafted_inpaint) \
+                    else "a mask (the reference resizes it for the hint with an unpinned lanczos)"
+                raise NotImplementedError(f"ControlNet hints together with {why}")
+            if self.unet.config.in_channels == 9:
+                raise NotImplementedError("ControlNet hints with a 9-channel inpaint UNet (the reference resizes its mask with an unpinned lanczos)")
         if t2i_hints:
             if clip_guidance_scale and self.clip_model is not None and self.feature_extractor is not None:
                 raise NotImplementedError("T2I hints together with CLIP guidance (no input gradients through adapter states)")
@@ -456,6 +472,8 @@ class GyrePipeline:
             use_hires = not (width <= threshold and height <= threshold)
         if use_hires and t2i_hints:
             raise NotImplementedError("T2I hints together with hires fix (the natural-size leaf needs its own resized hint states)")
+        if use_hires and controlnet_hints:
+            raise NotImplementedError("ControlNet hints together with hires fix (the natural-size leaf needs its own resized hint image)")
         if use_hires and not is_k:
             raise ValueError("Can't use Diffuser schedulers with Hires fix. "
                              "Either use a K-Diffusion scheduler or disable Hires fix.")
@@ -482,6 +500,11 @@ class GyrePipeline:
             if any(s.shape[0] != B for s in t2i_states["g"]):
                 raise ValueError(f"hint image batch must be 1 or the number of seeds ({B})")
             t2i_states["f"] = [torch.cat([u, g], dim=0) for u, g in zip(t2i_states["u"], t2i_states["g"])]
+        if controlnet_hints:
+            for h in controlnet_hints:
+                h.to(dev)
+                if h.image.shape[0] not in (1, B) or h.image.shape[-2:] != (height, width):
+                    raise ValueError(f"a ControlNet hint image must be [1 or {B}, C, {height}, {width}], got {tuple(h.image.shape)}")
         shared = {}
         for leaf in leaves:
             clip_mode = None
@@ -495,7 +518,8 @@ class GyrePipeline:
                                               config=clip_config, generators=generators, latent_scale=self.latent_scale)
             self._bind_leaf(leaf, text_embeddings=text_embeddings, uncond_embeddings=uncond_embeddings,
                             guidance_scale=guidance_scale, cfg_execution=cfg_execution, B=B, added_cond=added_cond,
-                            uncond_added_cond=uncond_added_cond, cfg_embeddings=shared, clip_mode=clip_mode, t2i_states=t2i_states)
+                            uncond_added_cond=uncond_added_cond, cfg_embeddings=shared, clip_mode=clip_mode, t2i_states=t2i_states,
+                            controlnet_hints=controlnet_hints)
         sched.set_eps_unets([l.eps_unet for l in leaves])
         sched.set_timesteps(num_inference_steps, strength=strength if image is not None else None,
                             config=S.SchedulerConfig(eta=eta, karras_rho=karras_rho, churn=churn, churn_tmin=churn_tmin,

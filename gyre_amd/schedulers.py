@@ -174,6 +174,34 @@ class UNetWithEmbeddings:
         return self.unet(latents, t, encoder_hidden_states=self.text_embeddings).sample
 
 
+class UNetWithControlnet:
+    """Runs the ControlNet hints of a request before every UNet call and hands their summed residuals on (reference
+    unet/core.py:40-64).  It sits inside UNetWithEmbeddings, so it sees encoder_hidden_states; ``side`` is the CFG side of the stack
+    ("g", "u" or "f" - the reference's cfg_meta).  Every hint writes into the same N + 1 buffers, allocated at the first call and
+    reused by every step: the first hint that contributes assigns, the later ones accumulate (hints.ControlNetHint.run)."""
+
+    def __init__(self, unet, hints, side: str):
+        self.unet, self.hints, self.side = unet, list(hints), side
+        self._bufs = None
+
+    @property
+    def config(self):
+        return self.unet.config
+
+    def __call__(self, latents: Tensor, t, **kwargs):
+        ctx = kwargs.get("encoder_hidden_states")
+        B, _, H, W = latents.shape
+        key = (B, H, W, latents.device)
+        if self._bufs is None or self._bufs[0] != key:
+            self._bufs = (key, self.hints[0].model.new_outputs(B, H, W, latents.device))
+        bufs, wrote = self._bufs[1], False
+        for hint in self.hints:
+            wrote = hint.run(self.side, latents, t, ctx, bufs, wrote) or wrote
+        if not wrote:                                                  # only cfg_only hints, on the unconditional side
+            return self.unet(latents, t, **kwargs)
+        return self.unet(latents, t, **kwargs, down_block_additional_residuals=bufs[:-1], mid_block_additional_residual=bufs[-1])
+
+
 class UnetWithExtraChannels:
     """Concatenates fixed extra channels (runway inpaint: mask + masked-image latents), reference
     unet/core.py:15-37; the extra channels are repeated when the CFG wrapper doubled the batch."""

@@ -119,6 +119,53 @@ def unet_param_shapes(cfg: UNetConfig) -> Shapes:
     return s
 
 
+def controlnet_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the diffusers ``ControlNetModel`` (reference gyre/pipeline/controlnet/models.py): the UNet's
+    conv_in / time_embedding / down_blocks / mid_block, the conditioning embedding of the hint image (8 convolutions), one 1x1 zero
+    convolution per skip connection and one for the mid block.  cfg: gyre_amd.config.ControlNetConfig."""
+    s: Shapes = OrderedDict()
+    boc = cfg.block_out_channels
+    td = cfg.time_embed_dim
+    s["time_embedding.linear_1.weight"] = (td, boc[0])
+    s["time_embedding.linear_1.bias"] = (td,)
+    s["time_embedding.linear_2.weight"] = (td, td)
+    s["time_embedding.linear_2.bias"] = (td,)
+    s["conv_in.weight"] = (boc[0], cfg.in_channels, 3, 3)
+    s["conv_in.bias"] = (boc[0],)
+
+    def conv(p, o, i, k):
+        s[p + ".weight"] = (o, i, k, k)
+        s[p + ".bias"] = (o,)
+
+    ce = tuple(cfg.conditioning_embedding_out_channels)
+    conv("controlnet_cond_embedding.conv_in", ce[0], cfg.conditioning_channels, 3)
+    for i in range(len(ce) - 1):
+        conv(f"controlnet_cond_embedding.blocks.{2 * i}", ce[i], ce[i], 3)
+        conv(f"controlnet_cond_embedding.blocks.{2 * i + 1}", ce[i + 1], ce[i], 3)
+    conv("controlnet_cond_embedding.conv_out", boc[0], ce[-1], 3)
+    n = len(boc)
+    skip_ch = [boc[0]]
+    cin = boc[0]
+    for i in range(n):
+        for j in range(cfg.layers_per_block):
+            _resnet(s, f"down_blocks.{i}.resnets.{j}", cin, boc[i], td)
+            cin = boc[i]
+            if cfg.attn_levels[i]:
+                _transformer(s, f"down_blocks.{i}.attentions.{j}", cin, cfg.cross_attention_dim,
+                             cfg.transformer_depth[i], cfg.use_linear_projection)
+            skip_ch.append(cin)
+        if i < n - 1:
+            conv(f"down_blocks.{i}.downsamplers.0.conv", cin, cin, 3)
+            skip_ch.append(cin)
+    _resnet(s, "mid_block.resnets.0", cin, cin, td)
+    _transformer(s, "mid_block.attentions.0", cin, cfg.cross_attention_dim, cfg.transformer_depth[-1], cfg.use_linear_projection)
+    _resnet(s, "mid_block.resnets.1", cin, cin, td)
+    for k, c in enumerate(skip_ch):
+        conv(f"controlnet_down_blocks.{k}", c, c, 1)
+    conv("controlnet_mid_block", cin, cin, 1)
+    return s
+
+
 def _vae_attn(s, p, c):
     # diffusers 0.16 AttentionBlock names (reference pins diffusers ~= 0.16.0)
     s[p + ".group_norm.weight"] = (c,)

@@ -102,9 +102,29 @@ typedef struct {
     int32_t use_conv;                /* main: 1 = stride-2 conv downsampling (down_opt.op), 0 = 2x2 average pool */
 } gyre_t2i_cfg;
 
+/* ControlNet (reference gyre/pipeline/controlnet/models.py ControlNetModel): the encoder-relevant fields of gyre_unet_cfg, the channels
+ * of the hint image and the widths of its conditioning embedding. */
+typedef struct {
+    int32_t in_channels;             /* 4 */
+    int32_t n_levels;                /* 4 */
+    int32_t block_out_channels[GYRE_MAX_LEVELS]; /* 320,640,1280,1280 */
+    int32_t layers_per_block;        /* 2 */
+    int32_t attn_levels[GYRE_MAX_LEVELS];        /* 1,1,1,0 */
+    int32_t num_heads[GYRE_MAX_LEVELS];          /* 8,8,8,8 */
+    int32_t transformer_depth[GYRE_MAX_LEVELS];  /* 1,1,1,1 */
+    int32_t cross_attention_dim;     /* 768 */
+    int32_t norm_num_groups;         /* 32 */
+    int32_t use_linear_projection;   /* 0 for SD1.x */
+    int32_t flip_sin_to_cos;         /* 1 */
+    float   freq_shift;              /* 0 */
+    int32_t cond_channels;           /* 3: channels of the hint image */
+    int32_t cond_embed_channels[4];  /* 16,32,96,256 (multiples of 8) */
+} gyre_ctrl_cfg;
+
 typedef struct gyre_unet gyre_unet;
 typedef struct gyre_vae gyre_vae;
 typedef struct gyre_t2i gyre_t2i;
+typedef struct gyre_ctrl gyre_ctrl;
 
 /* ---- library ---------------------------------------------------------- */
 int gyre_abi_version(void);
@@ -316,6 +336,34 @@ size_t gyre_t2i_workspace_bytes(gyre_t2i* h, int B, int H, int W);
  * of 8; n = n_levels).  The stride-2 conv downsampling (use_conv) rounds an odd size up, the average pool down, as torch does. */
 int gyre_t2i_forward(gyre_t2i* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                      void* workspace, size_t workspace_bytes, void* const* features_out_nchw, int n, int out_dtype);
+
+/* ---- ControlNet ------------------------------------------------------------ */
+/* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
+ * controlnet_cond_embedding.{conv_in, blocks.0..5, conv_out}, controlnet_down_blocks.0..N-1 and controlnet_mid_block, with
+ * N = 1 + n_levels * layers_per_block + (n_levels - 1) skip connections (12 for SD1.x).  Same weight store, workspace and dry-run
+ * sizing rules as the UNet.  The model runs in two parts:
+ *   bind, once per request: the conditioning embedding of image[image_B, cond_channels, image_H, image_W] (image_H, image_W
+ *     multiples of 8; image_B == B, or 1: the one image serves every sample) and the cross-attention K / V of context[B, S, D]
+ *     through this model's own weights, both kept in buffers the handle owns (a set_weight call drops them);
+ *   forward, once per step: x[B, in_channels, H, W] and t[B] -> N + 1 residuals, the k-th being scales[k] (host floats) times the zero
+ *     convolution of the k-th skip connection (conv_in first), the last that of the mid block.  They go to samples
+ *     [out_b0, out_b0 + B) of outs[k] [out_B, C_k, H_k, W_k] NCHW of out_dtype: accumulate == 0 assigns and writes every other
+ *     sample of outs[k] as zero (the unconditional half of a cfg_only hint), accumulate == 1 adds (one fp32 add, one rounding) and
+ *     leaves the other samples alone (the sum over several control models).
+ * forward before bind, a batch other than the bound one, and an H x W other than the bound image's size / 8: GYRE_ERR_INVALID. */
+int gyre_ctrl_create(const gyre_ctrl_cfg* cfg, int device, gyre_ctrl** out);
+void gyre_ctrl_destroy(gyre_ctrl* h);
+int gyre_ctrl_num_params(const gyre_ctrl* h);
+const char* gyre_ctrl_param_key(const gyre_ctrl* h, int i);
+int gyre_ctrl_set_weight(gyre_ctrl* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_ctrl_finalize(gyre_ctrl* h, void* stream);
+size_t gyre_ctrl_bind_workspace_bytes(gyre_ctrl* h, int image_B, int image_H, int image_W, int B);
+int gyre_ctrl_bind(gyre_ctrl* h, void* stream, const void* image_nchw, int image_dtype, int image_B, int image_H, int image_W,
+                   const void* context, int ctx_dtype, int B, int S, void* workspace, size_t workspace_bytes);
+size_t gyre_ctrl_workspace_bytes(gyre_ctrl* h, int B, int H, int W, int S);
+int gyre_ctrl_forward(gyre_ctrl* h, void* stream, const void* x_nchw, int x_dtype, const int64_t* t, int B, int H, int W,
+                      void* workspace, size_t workspace_bytes, const float* scales, int accumulate, int out_B, int out_b0,
+                      void* const* outs_nchw, int n_outs, int out_dtype);
 
 /* ---- per-launch timing with HIP events on the launch stream (bench.py roofline leg) ----
  * mask: bit k enables kernel class k (names from gyre_prof_class_name; they equal the prefix of the
@@ -645,6 +693,12 @@ int gyre_op_nchw_to_nhwc(void* stream, const void* x, int dtype, int B, int C, i
 int gyre_op_pixel_unshuffle8(void* stream, const void* x, int dtype, int B, int c, int H, int W, void* y);
 int gyre_op_avgpool2(void* stream, const void* x, int B, int H, int W, int C, void* y);
 int gyre_op_relu(void* stream, void* x, size_t n);
+/* The element-wise kernels of the ControlNet (kernels_ctrl.hip).  silu: x * sigmoid(x) in place on n storage elements (n % 8 == 0),
+ * fp32 math, one rounding; NaN stays NaN, a finite input stays finite.  ctrl_emit: the residual hand-off described at
+ * gyre_ctrl_forward over f NHWC storage [B][HW][Cpad] (the first C channels; Cpad % 8 == 0). */
+int gyre_op_silu(void* stream, void* x, size_t n);
+int gyre_op_ctrl_emit(void* stream, const void* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
+                      int out_dtype, int out_B, int out_b0);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
