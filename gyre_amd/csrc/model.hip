@@ -68,22 +68,10 @@ static const char* kclass_name(int k) {
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int gyre_unet_create(const gyre_unet_cfg* cfg, int device, gyre_unet** out) {
-    if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    GYRE_HIP_CHECK(hipSetDevice(device));
-    auto* h = new gyre_unet();
-    h->cfg = *cfg; h->store.device = device;
-    int rc = h->build();
-    if (rc) { delete h; return rc; }
-    GYRE_HIP_CHECK(hipDeviceSynchronize());  // creation only: zero-fills of the weight buffers are complete
-    *out = h;
-    return 0;
-}
+int gyre_unet_create(const gyre_unet_cfg* cfg, int device, gyre_unet** out) { return handle_create(cfg, device, out); }
 void gyre_unet_destroy(gyre_unet* h) { delete h; }
-int gyre_unet_num_params(const gyre_unet* h) { return h ? (int)h->store.params.size() : 0; }
-const char* gyre_unet_param_key(const gyre_unet* h, int i) {
-    return (h && i >= 0 && i < (int)h->store.params.size()) ? h->store.params[i]->key.c_str() : nullptr;
-}
+int gyre_unet_num_params(const gyre_unet* h) { return handle_num_params(h); }
+const char* gyre_unet_param_key(const gyre_unet* h, int i) { return handle_param_key(h, i); }
 int gyre_unet_set_weight(gyre_unet* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
     if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     h->finalized = false;
@@ -108,12 +96,7 @@ int gyre_unet_set_weight_delta(gyre_unet* h, const char* key, const void* base, 
     h->invalidate_contexts();
     return 0;
 }
-int gyre_unet_finalize(gyre_unet* h, void* st) {
-    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
-    TRY(h->store.finalize());
-    h->finalized = true;
-    return 0;
-}
+int gyre_unet_finalize(gyre_unet* h, void* st) { return handle_finalize(h); }
 size_t gyre_unet_workspace_bytes(gyre_unet* h, int B, int H, int W, int S) {
     if (!h) return 0;
     // the maximum over the forms a forward of this shape can take: text context passed or cached, CFG halves sharing their
@@ -366,22 +349,10 @@ int gyre_unet_vjp_finish_range(gyre_unet* h, void* st, const void* d_eps, int dd
     return gyre_unet_vjp_reverse(*h, (hipStream_t)st, d_eps, ddt, dx_out, dxdt, b0, nb);
 }
 
-int gyre_vae_create(const gyre_vae_cfg* cfg, int device, gyre_vae** out) {
-    if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    GYRE_HIP_CHECK(hipSetDevice(device));
-    auto* h = new gyre_vae();
-    h->cfg = *cfg; h->store.device = device;
-    int rc = h->build();
-    if (rc) { delete h; return rc; }
-    GYRE_HIP_CHECK(hipDeviceSynchronize());
-    *out = h;
-    return 0;
-}
+int gyre_vae_create(const gyre_vae_cfg* cfg, int device, gyre_vae** out) { return handle_create(cfg, device, out); }
 void gyre_vae_destroy(gyre_vae* h) { delete h; }
-int gyre_vae_num_params(const gyre_vae* h) { return h ? (int)h->store.params.size() : 0; }
-const char* gyre_vae_param_key(const gyre_vae* h, int i) {
-    return (h && i >= 0 && i < (int)h->store.params.size()) ? h->store.params[i]->key.c_str() : nullptr;
-}
+int gyre_vae_num_params(const gyre_vae* h) { return handle_num_params(h); }
+const char* gyre_vae_param_key(const gyre_vae* h, int i) { return handle_param_key(h, i); }
 int gyre_vae_set_weight(gyre_vae* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
     if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);

@@ -7,23 +7,18 @@
 //                                                1x1 "zero convolution" per skip connection and one for the mid block
 //   gyre/pipeline/controlnet/models.py:488-544   forward: conv_in(latents) + embedding, down path, mid block, zero convolutions, scales
 // driven once per denoising step from gyre/pipeline/unet/core.py:40-64; weights are addressed by the diffusers ControlNetModel
-// state-dict keys.  The walk is a second one over the same Exec operations as gyre_unet::run (model_impl.h), which stays as it is:
-// no up path, no conv_out, no ToMe, no input gradients.  What does not depend on the step - the embedding of the hint image and the
-// cross-attention K / V of the text context - is computed once per request (bind) and kept in buffers the handle owns.
+// state-dict keys.  The copied half is the UNet's own: both handles are a UNetTrunk (model_impl.h) - one config check, one registration of
+// time embedding / conv_in / down levels / mid block (the conditioning embedding registers through its hook, between conv_in and
+// down_blocks.0), one project_context, one time_embed prologue.  The walk stays this file's: it emits a zero convolution after
+// every step and has no up path, conv_out, ToMe or input gradients.  What does not depend on the step - the embedding of the hint
+// image and the cross-attention K / V of the text context - is computed once per request (bind) and kept in buffers the handle owns.
 #include "model_impl.h"
 
-struct gyre_ctrl {
+struct gyre_ctrl : UNetTrunk {        // the trunk, then the embedding of the hint image and the zero convolutions
     gyre_ctrl_cfg cfg;
     Store store;
     Exec ex;
     bool finalized = false;
-    int temb_dim = 0, temb_cols = 0, gn_unit = 0;
-    bf16_t *te1w = nullptr, *te2w = nullptr; float *te1b = nullptr, *te2b = nullptr;
-    bf16_t* tproj_w = nullptr; float* tproj_b = nullptr;
-    ConvW conv_in;
-    struct Level { std::vector<ResW> res; std::vector<TransW> attn; ConvW resample; bool has_resample = false; };
-    std::vector<Level> down;
-    ResW mid0, mid1; TransW mid_attn;
     ConvW ce_in, ce_out;                      // controlnet_cond_embedding.conv_in / .conv_out
     std::vector<ConvW> ce_blocks;             // .blocks.0 .. : (stride 1, stride 2) pairs
     std::vector<ConvW> zero;                  // controlnet_down_blocks.k, one per skip connection (1x1)
@@ -37,127 +32,41 @@ struct gyre_ctrl {
     ~gyre_ctrl() { if (emb_buf) (void)hipFree(emb_buf); if (kv_buf) (void)hipFree(kv_buf); }
 
     int n_outputs() const { return (int)zero.size() + 1; }
-    template <typename F> void for_each_cross_attn(F f) {
-        for (auto& lv : down) for (auto& t : lv.attn) for (auto& b : t.blocks) f(b.a2);
-        for (auto& b : mid_attn.blocks) f(b.a2);
-    }
     void reg3(const std::string& key, int cout, int cin, ConvW& c) { c.cin = pad8(cin); c.cout = cout; c.w = store.conv3(key, cout, cin, &c.b); }
     void reg1(const std::string& key, int cout, int cin, ConvW& c) { c.cin = cin; c.cout = cout; c.w = store.mat(key, cout, cin, true, true, &c.b); }
 
     int build() {
         const gyre_ctrl_cfg& c = cfg;
         const int n = c.n_levels;
+        // this model's own checks come before the shared ones (UNetTrunk::check_cfg divides by num_heads)
         if (n < 1 || n > GYRE_MAX_LEVELS) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: n_levels out of range");
         if (c.in_channels < 1 || c.cond_channels < 1 || c.layers_per_block < 1) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: bad channel / layer count");
         for (int i = 0; i < n; ++i) {
-            if (c.block_out_channels[i] < 8 || c.block_out_channels[i] % c.norm_num_groups || c.block_out_channels[i] % 8)
-                GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: block_out_channels must be multiples of norm_num_groups and 8");
-            if (c.attn_levels[i] && (c.num_heads[i] < 1 || c.block_out_channels[i] % c.num_heads[i] || (c.block_out_channels[i] / c.num_heads[i]) % 8))
-                GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: head dim must be a multiple of 8");
+            if (c.block_out_channels[i] < 8) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: block_out_channels must be multiples of norm_num_groups and 8");
+            if (c.attn_levels[i] && c.num_heads[i] < 1) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: head dim must be a multiple of 8");
         }
-        if (c.cross_attention_dim % 8) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: cross_attention_dim must be a multiple of 8");
+        TRY(check_cfg(c, "ctrl: "));
         for (int i = 0; i < 4; ++i)
             if (c.cond_embed_channels[i] < 8 || c.cond_embed_channels[i] % 8)
                 GYRE_FAIL(GYRE_ERR_INVALID, "ctrl: conditioning embedding widths must be positive multiples of 8");
-        ex.groups = c.norm_num_groups;
-        ex.store = &store;
-        gn_unit = 0;
-        for (int i = 0; i < n; ++i) {
-            int a = c.block_out_channels[i] / c.norm_num_groups, b = gn_unit;
-            while (b) { const int t = a % b; a = b; b = t; }
-            gn_unit = a;
-        }
         const int c0 = c.block_out_channels[0];
-        temb_dim = 4 * c0;
-        int total_cols = 2 * c.block_out_channels[n - 1];
-        for (int i = 0; i < n; ++i) total_cols += c.layers_per_block * c.block_out_channels[i];
-        tproj_w = (bf16_t*)store.dmalloc((size_t)total_cols * temb_dim * 2, true);
-        tproj_b = (float*)store.dmalloc((size_t)total_cols * 4, true);
-        if (!tproj_w || !tproj_b) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-
-        te1w = store.mat("time_embedding.linear_1", temb_dim, c0, false, true, &te1b);
-        te2w = store.mat("time_embedding.linear_2", temb_dim, temb_dim, false, true, &te2b);
-        reg3("conv_in", c0, c.in_channels, conv_in);
-        // the embedding of the hint image: conv_in, (stride 1, stride 2) per width change, conv_out up to the UNet's first width
-        reg3("controlnet_cond_embedding.conv_in", c.cond_embed_channels[0], c.cond_channels, ce_in);
-        for (int i = 0; i < 3; ++i) {
-            const int ci = c.cond_embed_channels[i], co = c.cond_embed_channels[i + 1];
-            ce_blocks.emplace_back(); reg3("controlnet_cond_embedding.blocks." + std::to_string(2 * i), ci, ci, ce_blocks.back());
-            ce_blocks.emplace_back(); reg3("controlnet_cond_embedding.blocks." + std::to_string(2 * i + 1), co, ci, ce_blocks.back());
-        }
-        reg3("controlnet_cond_embedding.conv_out", c0, c.cond_embed_channels[3], ce_out);
-        std::vector<int> skip_ch{c0};
-        int cin = c0;
-        down.resize(n);
-        for (int i = 0; i < n; ++i) {
-            const int co = c.block_out_channels[i];
-            const std::string p = "down_blocks." + std::to_string(i);
-            for (int j = 0; j < c.layers_per_block; ++j) {
-                down[i].res.emplace_back();
-                reg_resnet(store, p + ".resnets." + std::to_string(j), cin, co, true, tproj_w, tproj_b, temb_dim, temb_cols, down[i].res.back());
-                cin = co;
-                if (c.attn_levels[i]) {
-                    down[i].attn.emplace_back();
-                    reg_transformer(store, p + ".attentions." + std::to_string(j), cin, c.num_heads[i], c.cross_attention_dim,
-                                    c.transformer_depth[i], c.use_linear_projection != 0, down[i].attn.back());
-                }
-                skip_ch.push_back(cin);
+        TRY(build_trunk(store, ex, c, 0, [&] {
+            // the embedding of the hint image: conv_in, (stride 1, stride 2) per width change, conv_out up to the UNet's first width
+            reg3("controlnet_cond_embedding.conv_in", c.cond_embed_channels[0], c.cond_channels, ce_in);
+            for (int i = 0; i < 3; ++i) {
+                const int ci = c.cond_embed_channels[i], co = c.cond_embed_channels[i + 1];
+                ce_blocks.emplace_back(); reg3("controlnet_cond_embedding.blocks." + std::to_string(2 * i), ci, ci, ce_blocks.back());
+                ce_blocks.emplace_back(); reg3("controlnet_cond_embedding.blocks." + std::to_string(2 * i + 1), co, ci, ce_blocks.back());
             }
-            if (i < n - 1) {
-                down[i].has_resample = true;
-                reg3(p + ".downsamplers.0.conv", cin, cin, down[i].resample);
-                skip_ch.push_back(cin);
-            }
-        }
-        reg_resnet(store, "mid_block.resnets.0", cin, cin, true, tproj_w, tproj_b, temb_dim, temb_cols, mid0);
-        reg_transformer(store, "mid_block.attentions.0", cin, c.num_heads[n - 1], c.cross_attention_dim, c.transformer_depth[n - 1],
-                        c.use_linear_projection != 0, mid_attn);
-        reg_resnet(store, "mid_block.resnets.1", cin, cin, true, tproj_w, tproj_b, temb_dim, temb_cols, mid1);
+            reg3("controlnet_cond_embedding.conv_out", c0, c.cond_embed_channels[3], ce_out);
+        }));
         zero.resize(skip_ch.size());
         for (size_t k = 0; k < skip_ch.size(); ++k) reg1("controlnet_down_blocks." + std::to_string(k), skip_ch[k], skip_ch[k], zero[k]);
-        reg1("controlnet_mid_block", cin, cin, zero_mid);
-        if (temb_cols != total_cols) GYRE_FAIL(GYRE_ERR_INVALID, "internal: temb column count mismatch");
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
+        reg1("controlnet_mid_block", skip_ch.back(), skip_ch.back(), zero_mid);
+        return build_done(store);
     }
 
     // ---- once per request ----------------------------------------------------------------------------------------------------
-    // The cross-attention K / V^T of the text context through this model's own to_k / to_v, as gyre_unet::set_context keeps the UNet's
-    int project_context(hipStream_t st, const void* ctx, int cdt, int B, int S) {
-        const int D = cfg.cross_attention_dim, Spad = (S + 7) / 8 * 8;
-        size_t need = align_up((size_t)B * S * D * 2, 256);
-        for_each_cross_attn([&](AttnW& a) { need += align_up((size_t)B * S * a.c * 2, 256) + align_up((size_t)B * a.c * Spad * 2, 256); });
-        if (need > kv_bytes) {
-            if (kv_buf) { GYRE_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(kv_buf); kv_buf = nullptr; kv_bytes = 0; }
-            GYRE_HIP_CHECK(hipMalloc(&kv_buf, need));
-            kv_bytes = need;
-        }
-        GYRE_HIP_CHECK(hipMemsetAsync(kv_buf, 0, need, st));   // V^T pad columns must be finite
-        char* ptr = (char*)kv_buf;
-        bf16_t* cx = (bf16_t*)ptr; ptr += align_up((size_t)B * S * D * 2, 256);
-        TRY(launch_ctx_to_bf16(st, ctx, cdt, (size_t)B * S * D, cx));
-        kv.clear();
-        int rc = 0;
-        for_each_cross_attn([&](AttnW& a) {
-            if (rc) return;
-            CtxKV e;
-            e.k = (bf16_t*)ptr; ptr += align_up((size_t)B * S * a.c * 2, 256);
-            e.vt = (bf16_t*)ptr; ptr += align_up((size_t)B * a.c * Spad * 2, 256);
-            GemmParams p;
-            p.A = cx; p.lda = D; p.mode = GEMM_LINEAR; p.W = a.wk; p.K = D; p.N = a.c; p.M = B * S; p.bias = a.bk; p.samples = B;
-            p.out = e.k; p.ldc = a.c; p.out_mode = OUT_BF16;
-            rc = launch_gemm(st, p);
-            if (rc) return;
-            GemmParams q;
-            q.A = cx; q.lda = D; q.mode = GEMM_LINEAR; q.W = a.wv; q.K = D; q.N = a.c; q.M = B * S; q.bias = a.bv; q.samples = B;
-            q.out = e.vt; q.out_mode = OUT_BF16_T; q.tokens_per_batch = S; q.ldt = Spad;
-            rc = launch_gemm(st, q);
-            kv.push_back(e);
-        });
-        if (rc) return rc;
-        ctx_S = S;
-        return 0;
-    }
     int silu(Tn& t) { return ex.dry() ? 0 : launch_silu(ex.st, t.p, (size_t)t.rows() * t.C); }
     // The hint image [Bi][cond_channels][H][W] (Bi == B, or 1: the one image serves every sample) -> emb_buf [B][H/8][W/8][C0].
     // A single image is repeated along the batch BEFORE the convolutions: a launch over B samples may plan its tiles and K splits
@@ -226,20 +135,8 @@ struct gyre_ctrl {
         }
         ex.ctx_cache = &kv; ex.ctx_layer = 0;
         Exec& e = ex;
-        Tn xin, cx, emb, t1, t2, tp, bound_emb;
-        TRY(e.alloc(xin, B, H, W, pad8(c.in_channels)));
-        TRY(e.alloc(emb, B, 1, 1, c.block_out_channels[0], 4));
-        TRY(e.alloc(t1, B, 1, 1, temb_dim, 4));
-        TRY(e.alloc(t2, B, 1, 1, temb_dim, 4));
-        TRY(e.alloc(tp, B, 1, 1, temb_cols, 4));
-        if (!dry) {
-            TRY(launch_nchw_to_nhwc(st, x, xdt, B, c.in_channels, H * W, xin.C, xin.p));
-            TRY(launch_timestep_linear(st, t, B, c.block_out_channels[0], c.flip_sin_to_cos, c.freq_shift, (float*)emb.p, te1w, te1b,
-                                       temb_dim, (float*)t1.p, temb_dim));
-            TRY(launch_rowvec_linear(st, (float*)t1.p, B, temb_dim, te2w, te2b, temb_dim, 1, (float*)t2.p, temb_dim));
-            TRY(launch_rowvec_linear(st, (float*)t2.p, B, temb_dim, tproj_w, tproj_b, temb_cols, 1, (float*)tp.p, temb_cols));
-        }
-        e.free(emb); e.free(t1); e.free(t2);
+        Tn xin, cx, tp, bound_emb;
+        TRY(time_embed(e, c, x, xdt, B, H, W, nullptr, 0, 0, t, B, B, nullptr, xin, cx, tp));
         const float* tproj = (const float*)tp.p;
         // conv_in(latents) + embedded hint: the embedding rides as the convolution's residual
         bound_emb.p = (bf16_t*)emb_buf; bound_emb.B = B; bound_emb.H = H; bound_emb.W = W; bound_emb.C = pad8(c.block_out_channels[0]);
@@ -304,34 +201,17 @@ struct gyre_ctrl {
 
 extern "C" {
 
-int gyre_ctrl_create(const gyre_ctrl_cfg* cfg, int device, gyre_ctrl** out) {
-    if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    GYRE_HIP_CHECK(hipSetDevice(device));
-    auto* h = new gyre_ctrl();
-    h->cfg = *cfg; h->store.device = device;
-    int rc = h->build();
-    if (rc) { delete h; return rc; }
-    GYRE_HIP_CHECK(hipDeviceSynchronize());  // creation only: zero-fills of the weight buffers are complete
-    *out = h;
-    return 0;
-}
+int gyre_ctrl_create(const gyre_ctrl_cfg* cfg, int device, gyre_ctrl** out) { return handle_create(cfg, device, out); }
 void gyre_ctrl_destroy(gyre_ctrl* h) { delete h; }
-int gyre_ctrl_num_params(const gyre_ctrl* h) { return h ? (int)h->store.params.size() : 0; }
-const char* gyre_ctrl_param_key(const gyre_ctrl* h, int i) {
-    return (h && i >= 0 && i < (int)h->store.params.size()) ? h->store.params[i]->key.c_str() : nullptr;
-}
+int gyre_ctrl_num_params(const gyre_ctrl* h) { return handle_num_params(h); }
+const char* gyre_ctrl_param_key(const gyre_ctrl* h, int i) { return handle_param_key(h, i); }
 int gyre_ctrl_set_weight(gyre_ctrl* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
     if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     h->finalized = false;
     h->bound = false;                            // the embedding and the projected context were made with the old weights
     return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
 }
-int gyre_ctrl_finalize(gyre_ctrl* h, void* st) {
-    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
-    TRY(h->store.finalize());
-    h->finalized = true;
-    return 0;
-}
+int gyre_ctrl_finalize(gyre_ctrl* h, void* st) { return handle_finalize(h); }
 size_t gyre_ctrl_bind_workspace_bytes(gyre_ctrl* h, int image_B, int image_H, int image_W, int B) {
     if (!h) return 0;
     return h->run_bind(true, nullptr, nullptr, 0, image_B, image_H, image_W, B, nullptr, 0) ? 0 : h->ex.arena.peak;
@@ -345,7 +225,10 @@ int gyre_ctrl_bind(gyre_ctrl* h, void* st, const void* image, int idt, int image
     gyre_launch_counter() = 0;
     h->bound = false;
     TRY(h->run_bind(false, (hipStream_t)st, image, idt, image_B, image_H, image_W, B, ws, wsb));
-    TRY(h->project_context((hipStream_t)st, ctx, cdt, B, S));
+    // the cross-attention K / V^T of the text context through this model's own to_k / to_v, as gyre_unet::set_context keeps the UNet's
+    TRY(project_context((hipStream_t)st, ctx, cdt, B, S, h->cfg.cross_attention_dim, [&](auto f) { h->for_each_cross_attn(f); }, h->kv_buf,
+                        h->kv_bytes, h->kv));
+    h->ctx_S = S;
     h->bound = true;
     return 0;
 }

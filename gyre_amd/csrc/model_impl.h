@@ -1,5 +1,5 @@
-// Model runtime internals shared by model.hip (forward graphs + C ABI) and model_vjp.hip (input-gradient graphs):
-// workspace arena, weight store, per-layer weight records, the op executor and the UNet / VAE graph objects.
+// Model runtime internals shared by model.hip (forward graphs + C ABI), model_vjp.hip (input-gradient graphs), model_ctrl.hip and
+// model_t2i.hip: workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
 #pragma once
 #include "../../include/gyre_hip.h"
 #include "kernels.h"
@@ -105,58 +105,46 @@ struct Store {
     std::vector<std::unique_ptr<Param>> params;
     std::unordered_map<std::string, Param*> by_key;
     std::vector<void*> allocs;
-    // transposed copies of weight matrices for the input-gradient pass (model_vjp.hip), made on first use and refreshed when
-    // any weight was set since (per-request LoRA re-uploads): key = forward weight pointer
-    struct WtEntry { bf16_t* p = nullptr; size_t bytes = 0; uint64_t version = 0; };
-    std::unordered_map<const void*, WtEntry> wt_cache;
-    uint64_t weights_version = 1;
-    // gamma-folded copies of the weights that follow a LayerNorm (GemmParams::ln_colsum), same lifetime rules
-    struct LnEntry { bf16_t* wf = nullptr; float* cs = nullptr; float* bb = nullptr; size_t elems = 0; uint64_t version = 0; };
-    std::unordered_map<const void*, LnEntry> ln_cache;
-    LnEntry* ln_lookup(const void* w, int N, int K, bool* fresh) {
-        LnEntry& en = ln_cache[w];
-        const size_t elems = (size_t)N * K;
-        if (!en.wf || en.elems < elems) {
-            const size_t wbytes = (elems * 2 + 255) / 256 * 256, vbytes = ((size_t)N * 4 + 255) / 256 * 256;
-            char* base = (char*)dmalloc(wbytes + 2 * vbytes, false);
-            if (!base) return nullptr;
-            en.wf = (bf16_t*)base; en.cs = (float*)(base + wbytes); en.bb = (float*)(base + wbytes + vbytes);
-            en.elems = elems; en.version = 0;
-        }
-        *fresh = en.version == weights_version;
-        en.version = weights_version;
-        return &en;
-    }
-    // fragment-ordered copies of the weights the A-resident GEMM kernel reads (GemmParams::w_packed), keyed by the row-major
-    // matrix they were made from (a plain weight or its LayerNorm-folded copy); same lifetime rules
-    std::unordered_map<const void*, WtEntry> ar_cache;
-    std::unordered_map<const void*, int> ar_kind;      // which kernel's order the copy is in (tile config 30 / 31)
-    void* ar_lookup(const void* w, size_t bytes, bool* fresh, int kind = 30) {
-        WtEntry& en = ar_cache[w];
+    uint64_t weights_version = 1;                      // bumped by every set_weight*: what a derived copy is current against
+    // Derived copies of weights, made on first use and refreshed by their user when any weight was set since (per-request LoRA
+    // re-uploads).  One cache for every kind, keyed by (kind, the row-major matrix the copy was made from); the user computes the
+    // size, fills the buffer and decides what a failed allocation means.  Memory per SD1.5 UNet handle and device-slot replica
+    // (DESIGN.md 3): DC_BLOCKED ~1.6 GB (~0.15 GB per VAE handle), DC_TRANSPOSED +1.7 GB, DC_SHORTCUT +0.4 GB, DC_PROJ_OUT 124 MB.
+    enum Kind {
+        DC_TRANSPOSED,   // W^T / rotated conv weights of the input-gradient pass (model_vjp.hip)
+        DC_LN_FOLD,      // gamma-folded weights | column sums | bias after a LayerNorm (GemmParams::ln_colsum)
+        DC_PACKED,       // fragment order of the A-resident GEMM kernel (GemmParams::w_packed); tag = tile config 30 / 31
+        DC_BLOCKED,      // blocked order of the LDS-DMA tile kernels (GemmParams::W_blk), every routed weight with K > 1024
+        DC_SHORTCUT,     // conv2 rows | 1x1 shortcut rows, and the sum of the two biases (GemmParams::sc_*)
+        DC_PROJ_OUT      // proj_out composed with the last FF2: Wc [C][5C] = [Wp W2 | Wp], bc = Wp b2 + bp (Exec::proj_out_folded)
+    };
+    struct DKey {
+        int kind; const void* src;
+        bool operator==(const DKey& o) const { return kind == o.kind && src == o.src; }
+    };
+    struct DKeyHash { size_t operator()(const DKey& k) const { return std::hash<const void*>()(k.src) * 31 + (size_t)k.kind; } };
+    struct Derived { void* p = nullptr; size_t bytes = 0; uint64_t version = 0; int tag = 0; };
+    std::unordered_map<DKey, Derived, DKeyHash> derived_;
+    // The buffer of (kind, src), allocated on first use (a superseded smaller one is released), or nullptr when there is no memory
+    // (the HIP error is cleared).  *fresh: the content was made for the current weights_version and for `tag`; the entry is marked
+    // current, so the caller fills it now when it is not fresh.
+    void* derived(Kind kind, const void* src, size_t bytes, bool* fresh, int tag = 0) {
+        Derived& en = derived_[DKey{kind, src}];
         if (!en.p || en.bytes < bytes) {
-            en.p = (bf16_t*)dmalloc(bytes, false);
+            if (en.p) dfree(en.p);
+            en.p = dmalloc(bytes, false);
+            if (!en.p) { (void)hipGetLastError(); en.bytes = 0; en.version = weights_version; return nullptr; }   // (remembered: derived_failed)
             en.bytes = bytes; en.version = 0;
         }
-        int& k = ar_kind[w];
-        *fresh = en.p && en.version == weights_version && k == kind;
-        if (en.p) { en.version = weights_version; k = kind; }
+        *fresh = en.version == weights_version && en.tag == tag;
+        en.version = weights_version; en.tag = tag;
         return en.p;
     }
-    // blocked copies of the weights the LDS-DMA tile kernels read (GemmParams::W_blk), keyed like the packed copies above
-    // Memory: one extra copy (N * K * 2 bytes) of every weight the planner routes to an LDS-DMA tile with K > 1024 - nearly all 3x3
-    // convs and FF layers: ~1.6 GB per SD1.5 UNet handle, ~0.15 GB per VAE handle, per device-slot replica.  The copy is
-    // an optimisation only: when it cannot be allocated the launch reads the row-major weights (nullptr here, prep_blk goes on).
-    std::unordered_map<const void*, WtEntry> blk_cache;
-    bf16_t* blk_lookup(const void* w, size_t bytes, bool* fresh) {
-        WtEntry& en = blk_cache[w];
-        if (!en.p || en.bytes < bytes) {
-            if (en.p) dfree(en.p);                               // superseded (smaller) buffer: released now, not at Store destruction
-            en.p = (bf16_t*)dmalloc(bytes, false);
-            en.bytes = en.p ? bytes : 0; en.version = 0;
-        }
-        *fresh = en.p && en.version == weights_version;
-        if (en.p) en.version = weights_version;
-        return en.p;
+    // did the allocation of (kind, src) fail under the current weights_version?  (a user to whom the copy is an optimisation only
+    // may then not ask again before a weight is set)
+    bool derived_failed(Kind kind, const void* src) const {
+        auto it = derived_.find(DKey{kind, src});
+        return it != derived_.end() && !it->second.p && it->second.version == weights_version;
     }
     // release one dmalloc'ed buffer early (after the device has finished with it: a superseded cache copy is only replaced between
     // calls of its handle, but kernels of the previous call may still be queued on the stream)
@@ -164,57 +152,7 @@ struct Store {
         for (size_t i = 0; i < allocs.size(); ++i)
             if (allocs[i] == ptr) { allocs[i] = allocs.back(); allocs.pop_back(); (void)hipDeviceSynchronize(); (void)hipFree(ptr); return; }
     }
-    // conv2 rows followed by the 1x1 shortcut's rows, and the sum of the two biases, for the folded form (GemmParams::sc_*): keyed by
-    // the conv weight, made on first use, refreshed after any weight change like the other derived copies (+0.4 GB per SD1.5 UNet handle)
-    struct ScEntry { bf16_t* w = nullptr; float* b = nullptr; size_t elems = 0; uint64_t version = 0; };
-    std::unordered_map<const void*, ScEntry> sc_cache;
-    ScEntry* sc_lookup(const void* w, int N, int Kcat, bool* fresh) {
-        ScEntry& en = sc_cache[w];
-        const size_t elems = (size_t)N * Kcat;
-        if (!en.w || en.elems < elems) {
-            const size_t wbytes = (elems * 2 + 255) / 256 * 256;
-            char* base = (char*)dmalloc(wbytes + ((size_t)N * 4 + 255) / 256 * 256, false);
-            if (!base) return nullptr;
-            en.w = (bf16_t*)base; en.b = (float*)(base + wbytes); en.elems = elems; en.version = 0;
-        }
-        *fresh = en.version == weights_version;
-        en.version = weights_version;
-        return &en;
-    }
-    // a Transformer2D's proj_out composed with the FF2 of its last block (Exec::transformer): Wc [C][5C] = [Wp W2 | Wp] and
-    // bc = Wp b2 + bp (launch_compose_proj), keyed by the proj_out weight, made on first use and refreshed after any weight change like
-    // the other derived copies (SD1.5: 124 MB per UNet handle).  An optimisation only: when the buffer cannot be allocated
-    // the answer is "no fold" (nullptr) for this weight version - the caller takes the two launches, and nothing retries before a
-    // weight is set again.
-    struct PfEntry { bf16_t* w = nullptr; float* b = nullptr; size_t elems = 0; uint64_t version = 0, no_fold_version = 0; };
-    std::unordered_map<const void*, PfEntry> pf_cache;
-    PfEntry* pf_lookup(const void* wp, int C, bool* fresh) {
-        PfEntry& en = pf_cache[wp];
-        if (en.no_fold_version == weights_version) return nullptr;
-        const size_t elems = (size_t)C * 5 * C;
-        if (!en.w || en.elems < elems) {
-            if (en.w) { dfree(en.w); en.w = nullptr; en.elems = 0; }   // superseded buffer: released now
-            const size_t wbytes = (elems * 2 + 255) / 256 * 256;
-            char* base = (char*)dmalloc(wbytes + ((size_t)C * 4 + 255) / 256 * 256, false);
-            if (!base) { (void)hipGetLastError(); en.no_fold_version = weights_version; return nullptr; }
-            en.w = (bf16_t*)base; en.b = (float*)(base + wbytes); en.elems = elems; en.version = 0;
-        }
-        *fresh = en.version == weights_version;
-        en.version = weights_version;
-        return &en;
-    }
     ~Store() { for (void* a : allocs) (void)hipFree(a); }
-    // returns the cached buffer for `w` (allocating `bytes` on first use) and whether its content is current
-    bf16_t* wt_lookup(const void* w, size_t bytes, bool* fresh) {
-        WtEntry& en = wt_cache[w];
-        if (!en.p || en.bytes < bytes) {
-            en.p = (bf16_t*)dmalloc(bytes, false);
-            en.bytes = bytes; en.version = 0;
-        }
-        *fresh = en.p && en.version == weights_version;
-        if (en.p) en.version = weights_version;
-        return en.p;
-    }
     void* dmalloc(size_t bytes, bool zero) {
         void* p = nullptr;
         if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
@@ -260,10 +198,13 @@ struct Store {
         add(key, {n}, PK_VEC, b);
         *out = b;
     }
-    int set_weight(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, hipStream_t st) {
+    // what the three setters share: key lookup, dtype check, shape comparison.  matrices_only ("a LoRA", ...): vector keys are refused
+    int locate(const char* key, int dtype, const int64_t* shape, int ndim, Param** out, const char* matrices_only = nullptr) {
         auto it = by_key.find(key);
         if (it == by_key.end()) GYRE_FAIL(GYRE_ERR_KEY, std::string("unknown weight key: ") + key);
         Param& p = *it->second;
+        if (matrices_only && (p.kind == PK_VEC || p.kind == PK_VEC_GEGLU))
+            GYRE_FAIL(GYRE_ERR_INVALID, std::string(matrices_only) + " applies to matrices and convolutions, not to the vector " + key);
         if (dtype < 0 || dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
         bool ok = (int)p.shape.size() == ndim;
         for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
@@ -274,6 +215,19 @@ struct Store {
             for (int i = 0; i < ndim; ++i) m += std::to_string(shape[i]) + ",";
             GYRE_FAIL(GYRE_ERR_KEY, m + "]");
         }
+        *out = &p;
+        return 0;
+    }
+    // ... and their tail.  *was_set: whether the key had been set before (a first set leaves the handle un-finalized, a later one does not)
+    void mark_set(Param& p, bool* was_set = nullptr) {
+        if (was_set) *was_set = p.set;
+        p.set = true;
+        ++weights_version;
+    }
+    int set_weight(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, hipStream_t st) {
+        Param* pp;
+        TRY(locate(key, dtype, shape, ndim, &pp));
+        Param& p = *pp;
         int O = (int)p.shape[0];
         switch (p.kind) {
             case PK_CONV3: TRY(launch_repack_conv(st, src, dtype, O, (int)p.shape[1], 3, 3, p.i_pad, (bf16_t*)p.dev)); break;
@@ -291,31 +245,18 @@ struct Store {
             case PK_VEC: TRY(launch_cast_f32(st, src, dtype, (size_t)O, 0, (float*)p.dev, p.scale)); break;
             case PK_VEC_GEGLU: TRY(launch_cast_f32(st, src, dtype, (size_t)O, 1, (float*)p.dev)); break;
         }
-        p.set = true;
-        ++weights_version;
+        mark_set(p);
         return 0;
     }
     // set_weight of  base + sum_j scale_j up_j down_j  (per-request LoRA, reference gyre/pipeline/lora.py:96-160) for one matrix /
     // conv key: the low-rank sum joins the repack pass in fp32 (launch_repack_lora), nothing is multiplied out or copied by the
     // caller.  Same key / shape rules as set_weight; n_pairs == 0 writes set_weight's bits (how a LoRA is taken off again).  The
-    // derived copies (wt / ln / ar / blk / sc caches) share the one version counter and are refreshed by the next forward.
-    // *was_set: whether the key had been set before (a first set leaves the handle un-finalized, a later one does not).
+    // derived copies share the one version counter and are refreshed by the next forward.
     int set_weight_lora(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, int n_pairs,
                         const gyre_lora_pair* pairs, hipStream_t st, bool* was_set) {
-        auto it = by_key.find(key);
-        if (it == by_key.end()) GYRE_FAIL(GYRE_ERR_KEY, std::string("unknown weight key: ") + key);
-        Param& p = *it->second;
-        if (p.kind == PK_VEC || p.kind == PK_VEC_GEGLU) GYRE_FAIL(GYRE_ERR_INVALID, std::string("a LoRA applies to matrices and convolutions, not to the vector ") + key);
-        if (dtype < 0 || dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
-        bool ok = (int)p.shape.size() == ndim;
-        for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
-        if (!ok) {
-            std::string m = std::string("shape mismatch for ") + key + ": expected [";
-            for (auto d : p.shape) m += std::to_string(d) + ",";
-            m += "] got [";
-            for (int i = 0; i < ndim; ++i) m += std::to_string(shape[i]) + ",";
-            GYRE_FAIL(GYRE_ERR_KEY, m + "]");
-        }
+        Param* pp;
+        TRY(locate(key, dtype, shape, ndim, &pp, "a LoRA"));
+        Param& p = *pp;
         if (n_pairs < 0 || n_pairs > GYRE_LORA_MAX_PAIRS || (n_pairs > 0 && !pairs)) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: 0 to 8 LoRA pairs per call");
         LoraArgs la;
         la.n = n_pairs;
@@ -334,9 +275,7 @@ struct Store {
         } else {
             TRY(launch_repack_lora(st, src, dtype, O, I, 1, 1, p.i_pad, 0, p.scale, la, (bf16_t*)p.dev));
         }
-        if (was_set) *was_set = p.set;
-        p.set = true;
-        ++weights_version;
+        mark_set(p, was_set);
         return 0;
     }
     // set_weight of  base + sum_j scale_j D_j  with LyCORIS terms (gyre_delta_term, reference gyre/pipeline/lycoris.py:99-228): set_weight_lora
@@ -344,20 +283,9 @@ struct Store {
     // set_weight's bits.  Every check (delta_terms_to_args, launch_repack_delta) precedes the launch.
     int set_weight_delta(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, int n_terms,
                          const gyre_delta_term* terms, hipStream_t st, bool* was_set) {
-        auto it = by_key.find(key);
-        if (it == by_key.end()) GYRE_FAIL(GYRE_ERR_KEY, std::string("unknown weight key: ") + key);
-        Param& p = *it->second;
-        if (p.kind == PK_VEC || p.kind == PK_VEC_GEGLU) GYRE_FAIL(GYRE_ERR_INVALID, std::string("a LyCORIS delta applies to matrices and convolutions, not to the vector ") + key);
-        if (dtype < 0 || dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
-        bool ok = (int)p.shape.size() == ndim;
-        for (int i = 0; ok && i < ndim; ++i) ok = p.shape[i] == shape[i];
-        if (!ok) {
-            std::string m = std::string("shape mismatch for ") + key + ": expected [";
-            for (auto d : p.shape) m += std::to_string(d) + ",";
-            m += "] got [";
-            for (int i = 0; i < ndim; ++i) m += std::to_string(shape[i]) + ",";
-            GYRE_FAIL(GYRE_ERR_KEY, m + "]");
-        }
+        Param* pp;
+        TRY(locate(key, dtype, shape, ndim, &pp, "a LyCORIS delta"));
+        Param& p = *pp;
         DeltaArgs da;
         TRY(delta_terms_to_args(n_terms, terms, da));
         const int O = (int)p.shape[0], I = (int)p.shape[1];
@@ -369,9 +297,7 @@ struct Store {
         } else {
             TRY(launch_repack_delta(st, src, dtype, O, I, 1, 1, p.i_pad, 0, p.scale, da, (bf16_t*)p.dev));
         }
-        if (was_set) *was_set = p.set;
-        p.set = true;
-        ++weights_version;
+        mark_set(p, was_set);
         return 0;
     }
     int finalize() {
@@ -533,7 +459,7 @@ struct Exec {
     int prep_ar(GemmParams& p, const GemmPlan& pl) {
         if (dry() || !pl.ar_pack) return 0;
         bool fresh = false;
-        void* pk = store ? store->ar_lookup(p.W, gemm_ar_packed_bytes(p.N, p.K), &fresh, pl.cfg) : nullptr;
+        void* pk = store ? store->derived(Store::DC_PACKED, p.W, gemm_ar_packed_bytes(p.N, p.K), &fresh, pl.cfg) : nullptr;
         if (!pk) GYRE_FAIL(GYRE_ERR_HIP, "cannot allocate the packed weight copy of the A-resident GEMM");
         if (!fresh) TRY(launch_ar_pack(st, p.W, p.N, p.K, pk));
         p.w_packed = pk;
@@ -543,8 +469,8 @@ struct Exec {
     int prep_blk(GemmParams& p, const GemmPlan& pl) {
         if (dry() || !store || p.W_blk || !pl.w_block) return 0;
         bool fresh = false;
-        bf16_t* b = store->blk_lookup(p.W, (size_t)p.N * p.K * 2, &fresh);
-        if (!b) { (void)hipGetLastError(); return 0; }           // no memory for the copy: the kernels read the row-major weights (W_blk stays null)
+        bf16_t* b = (bf16_t*)store->derived(Store::DC_BLOCKED, p.W, (size_t)p.N * p.K * 2, &fresh);
+        if (!b) return 0;                                        // no memory for the copy: the kernels read the row-major weights (W_blk stays null)
         if (!fresh) TRY(launch_w_block(st, p.W, p.N, p.K, b));
         p.W_blk = b;
         return 0;
@@ -591,14 +517,16 @@ struct Exec {
             fill_shortcut(p, *sc_x, sc_skip);
             if (!dry()) {
                 bool fresh = false;
-                Store::ScEntry* e = store->sc_lookup(w.w, p.N, p.K, &fresh);
-                if (!e) GYRE_FAIL(GYRE_ERR_HIP, "cannot allocate the folded conv + shortcut weights");
+                const size_t wbytes = align_up((size_t)p.N * p.K * 2, 256);               // w | b in one buffer
+                bf16_t* fw = (bf16_t*)store->derived(Store::DC_SHORTCUT, w.w, wbytes + align_up((size_t)p.N * 4, 256), &fresh);
+                if (!fw) GYRE_FAIL(GYRE_ERR_HIP, "cannot allocate the folded conv + shortcut weights");
+                float* fb = (float*)((char*)fw + wbytes);
                 if (!fresh) {
-                    TRY(launch_concat_rows(st, w.w, 9 * x.C, sc_w, p.sc_K, p.N, e->w));
-                    GYRE_HIP_CHECK(hipMemcpyAsync(e->b, w.b, (size_t)p.N * sizeof(float), hipMemcpyDeviceToDevice, st));
-                    if (sc_b) TRY(launch_add_f32(st, e->b, sc_b, (size_t)p.N));
+                    TRY(launch_concat_rows(st, w.w, 9 * x.C, sc_w, p.sc_K, p.N, fw));
+                    GYRE_HIP_CHECK(hipMemcpyAsync(fb, w.b, (size_t)p.N * sizeof(float), hipMemcpyDeviceToDevice, st));
+                    if (sc_b) TRY(launch_add_f32(st, fb, sc_b, (size_t)p.N));
                 }
-                p.W = e->w; p.bias = e->b;
+                p.W = fw; p.bias = fb;
             }
         }
         TRY(attach_colstats(p, y, Ho * Wo));       // every conv output of the UNet feeds a GroupNorm
@@ -741,10 +669,12 @@ struct Exec {
         }
         if (dry()) return 0;
         bool fresh = false;
-        Store::LnEntry* e = store->ln_lookup(p.W, p.N, p.K, &fresh);
-        if (!e) GYRE_FAIL(GYRE_ERR_HIP, "cannot allocate the LayerNorm-folded weight copy");
-        if (!fresh) TRY(launch_ln_fold(st, p.W, p.N, p.K, ln.g, ln.b, p.bias, e->wf, e->cs, e->bb));
-        p.W = e->wf; p.bias = e->bb; p.ln_colsum = e->cs;
+        const size_t wbytes = align_up((size_t)p.N * p.K * 2, 256), vbytes = align_up((size_t)p.N * 4, 256);   // wf | cs | bb in one buffer
+        bf16_t* wf = (bf16_t*)store->derived(Store::DC_LN_FOLD, p.W, wbytes + 2 * vbytes, &fresh);
+        if (!wf) GYRE_FAIL(GYRE_ERR_HIP, "cannot allocate the LayerNorm-folded weight copy");
+        float *cs = (float*)((char*)wf + wbytes), *bb = (float*)((char*)wf + wbytes + vbytes);
+        if (!fresh) TRY(launch_ln_fold(st, p.W, p.N, p.K, ln.g, ln.b, p.bias, wf, cs, bb));
+        p.W = wf; p.bias = bb; p.ln_colsum = cs;
         return 0;
     }
     // y = LayerNorm(x) @ w^T + bias (geglu halves N): one launch when the planner's kernel can fold the norm, else two
@@ -979,10 +909,15 @@ struct Exec {
         const bf16_t* wc = nullptr; const float* bc = nullptr;
         if (!dry()) {
             bool fresh = false;
-            Store::PfEntry* e = store->pf_lookup(w.pout, C, &fresh);
-            if (!e) return 0;
-            if (!fresh) TRY(launch_compose_proj(st, w.pout, bw.ff2, bw.ff2b, w.poutb, C, e->w, e->b));
-            wc = e->w; bc = e->b;
+            // An optimisation only: without memory for the composed weights the answer is "no fold" for this weight version - the
+            // caller takes the two launches, and nothing retries before a weight is set again.
+            if (store->derived_failed(Store::DC_PROJ_OUT, w.pout)) return 0;
+            const size_t wbytes = align_up((size_t)C * 5 * C * 2, 256);                   // w | b in one buffer
+            bf16_t* cw = (bf16_t*)store->derived(Store::DC_PROJ_OUT, w.pout, wbytes + align_up((size_t)C * 4, 256), &fresh);
+            if (!cw) return 0;
+            float* cb = (float*)((char*)cw + wbytes);
+            if (!fresh) TRY(launch_compose_proj(st, w.pout, bw.ff2, bw.ff2b, w.poutb, C, cw, cb));
+            wc = cw; bc = cb;
         }
         TRY(alloc(out, x.B, x.H, x.W, C));
         TRY(linear(ff.p, 4 * C, h.p, C, 4 * C, M, 5 * C, wc, C, bc, x.p, C, 0, out.p, C, nullptr, &out));
@@ -1046,7 +981,7 @@ struct Exec {
                 if (!more && proj_out_folds(C, x.H * x.W)) {
                     // Round 7: proj_out rides inside the last block's FF2.  Nothing non-linear sits between the two, so
                     //   out = (ff W2^T + b2 + h) Wp^T + bp + x = [ff | h] [Wp W2 | Wp]^T + (Wp b2 + bp) + x
-                    // is ONE launch over K = 5C on weights composed once per weight version (Store::pf_lookup): no proj_out launch,
+                    // is ONE launch over K = 5C on weights composed once per weight version (Store::DC_PROJ_OUT): no proj_out launch,
                     // no h2 tensor, one rounding less.  The launch leaves the column statistics proj_out left (cs_for = &out).
                     bool done = false;
                     TRY(proj_out_folded(ff, h, x, w, bw, out, &done));
@@ -1147,6 +1082,173 @@ static void reg_transformer(Store& s, const std::string& p, int c, int heads, in
 }
 
 // ------------------------------------------------------------------------------------------
+// UNet trunk: what the UNet and the ControlNet (a copy of the UNet's encoder) both own and do - time embedding, conv_in, down levels and
+// mid block, their registration, the projection of a text context and the prologue of a walk.  The walks themselves differ in what
+// they do between the steps (CFG-pair prefix, adapters, taps, emits, kept activations) and stay with their owners.
+// ------------------------------------------------------------------------------------------
+// Project a text context through the to_k / to_v of every cross-attention `layers` enumerates (layers(f) calls f(AttnW&) in walk
+// order), once per request: (buf, bytes) grows as needed and holds the bf16 context, then K and V^T per layer (kv).
+template <typename Layers>
+static int project_context(hipStream_t st, const void* ctx, int cdt, int B, int S, int D, Layers layers, void*& buf, size_t& bytes,
+                           std::vector<CtxKV>& kv) {
+    const int Spad = (S + 7) / 8 * 8;
+    size_t need = align_up((size_t)B * S * D * 2, 256);
+    layers([&](AttnW& a) { need += align_up((size_t)B * S * a.c * 2, 256) + align_up((size_t)B * a.c * Spad * 2, 256); });
+    if (need > bytes) {
+        if (buf) { GYRE_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(buf); buf = nullptr; bytes = 0; }
+        GYRE_HIP_CHECK(hipMalloc(&buf, need));
+        bytes = need;
+    }
+    GYRE_HIP_CHECK(hipMemsetAsync(buf, 0, need, st));   // V^T pad columns must be finite
+    char* ptr = (char*)buf;
+    bf16_t* cx = (bf16_t*)ptr; ptr += align_up((size_t)B * S * D * 2, 256);
+    TRY(launch_ctx_to_bf16(st, ctx, cdt, (size_t)B * S * D, cx));
+    kv.clear();
+    int rc = 0;
+    layers([&](AttnW& a) {
+        if (rc) return;
+        CtxKV e;
+        e.k = (bf16_t*)ptr; ptr += align_up((size_t)B * S * a.c * 2, 256);
+        e.vt = (bf16_t*)ptr; ptr += align_up((size_t)B * a.c * Spad * 2, 256);
+        GemmParams p;
+        p.A = cx; p.lda = D; p.mode = GEMM_LINEAR; p.W = a.wk; p.K = D; p.N = a.c; p.M = B * S; p.bias = a.bk; p.samples = B;
+        p.out = e.k; p.ldc = a.c; p.out_mode = OUT_BF16;
+        rc = launch_gemm(st, p);
+        if (rc) return;
+        GemmParams q;
+        q.A = cx; q.lda = D; q.mode = GEMM_LINEAR; q.W = a.wv; q.K = D; q.N = a.c; q.M = B * S; q.bias = a.bv; q.samples = B;
+        q.out = e.vt; q.out_mode = OUT_BF16_T; q.tokens_per_batch = S; q.ldt = Spad;
+        rc = launch_gemm(st, q);
+        kv.push_back(e);
+    });
+    return rc;
+}
+
+struct UNetTrunk {
+    int temb_dim = 0;
+    int temb_cols = 0, temb_total = 0;   // columns of the batched time_emb_proj: registered so far / when the owner is done
+    int gn_unit = 0;     // gcd of block_out_channels / groups: every GroupNorm group (skip concats included) is a whole number of units
+    bf16_t *te1w = nullptr, *te2w = nullptr; float *te1b = nullptr, *te2b = nullptr;
+    bf16_t* tproj_w = nullptr; float* tproj_b = nullptr;
+    ConvW conv_in;
+    struct Level { std::vector<ResW> res; std::vector<TransW> attn; ConvW resample; bool has_resample = false; };
+    std::vector<Level> down;
+    ResW mid0, mid1; TransW mid_attn;
+    std::vector<int> skip_ch;            // channels of the skip connections in the order they are produced, conv_in first
+
+    template <typename F> void for_each_cross_attn(F f) {
+        for (auto& lv : down) for (auto& t : lv.attn) for (auto& b : t.blocks) f(b.a2);
+        for (auto& b : mid_attn.blocks) f(b.a2);
+    }
+    // Validates the fields gyre_unet_cfg and gyre_ctrl_cfg share; the messages carry `pfx`.
+    template <typename Cfg>
+    static int check_cfg(const Cfg& c, const std::string& pfx) {
+        const int n = c.n_levels;
+        if (n < 1 || n > GYRE_MAX_LEVELS) GYRE_FAIL(GYRE_ERR_INVALID, pfx + "n_levels out of range");
+        for (int i = 0; i < n; ++i) {
+            if (c.block_out_channels[i] % c.norm_num_groups || c.block_out_channels[i] % 8)
+                GYRE_FAIL(GYRE_ERR_INVALID, pfx + "block_out_channels must be multiples of norm_num_groups and 8");
+            if (c.attn_levels[i] && (c.block_out_channels[i] % c.num_heads[i] || (c.block_out_channels[i] / c.num_heads[i]) % 8))
+                GYRE_FAIL(GYRE_ERR_INVALID, pfx + "head dim must be a multiple of 8");
+        }
+        if (c.cross_attention_dim % 8) GYRE_FAIL(GYRE_ERR_INVALID, pfx + "cross_attention_dim must be a multiple of 8");
+        return 0;
+    }
+    // Registers time_embedding.*, conv_in, the down levels and the mid block of a checked config, in that order; after_conv_in()
+    // registers what the owner keeps between conv_in and down_blocks.0.  extra_temb_cols: time_emb_proj columns of the resnets the
+    // owner registers afterwards (then it calls build_done).
+    template <typename Cfg, typename Hook>
+    int build_trunk(Store& store, Exec& ex, const Cfg& c, int extra_temb_cols, Hook after_conv_in) {
+        const int n = c.n_levels;
+        ex.groups = c.norm_num_groups;
+        ex.store = &store;
+        gn_unit = 0;
+        for (int i = 0; i < n; ++i) {
+            int a = c.block_out_channels[i] / c.norm_num_groups, b = gn_unit;
+            while (b) { const int t = a % b; a = b; b = t; }
+            gn_unit = a;
+        }
+        const int c0 = c.block_out_channels[0];
+        temb_dim = 4 * c0;
+        temb_total = 2 * c.block_out_channels[n - 1] + extra_temb_cols;
+        for (int i = 0; i < n; ++i) temb_total += c.layers_per_block * c.block_out_channels[i];
+        tproj_w = (bf16_t*)store.dmalloc((size_t)temb_total * temb_dim * 2, true);
+        tproj_b = (float*)store.dmalloc((size_t)temb_total * 4, true);
+        if (!tproj_w || !tproj_b) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
+
+        te1w = store.mat("time_embedding.linear_1", temb_dim, c0, false, true, &te1b);
+        te2w = store.mat("time_embedding.linear_2", temb_dim, temb_dim, false, true, &te2b);
+        conv_in.cin = pad8(c.in_channels); conv_in.cout = c0;
+        conv_in.w = store.conv3("conv_in", c0, c.in_channels, &conv_in.b);
+        after_conv_in();
+        skip_ch.assign(1, c0);
+        int cin = c0;
+        down.resize(n);
+        for (int i = 0; i < n; ++i) {
+            const int co = c.block_out_channels[i];
+            const std::string p = "down_blocks." + std::to_string(i);
+            for (int j = 0; j < c.layers_per_block; ++j) {
+                down[i].res.emplace_back();
+                reg_resnet(store, p + ".resnets." + std::to_string(j), cin, co, true, tproj_w, tproj_b, temb_dim, temb_cols,
+                           down[i].res.back());
+                cin = co;
+                if (c.attn_levels[i]) {
+                    down[i].attn.emplace_back();
+                    reg_transformer(store, p + ".attentions." + std::to_string(j), cin, c.num_heads[i], c.cross_attention_dim,
+                                    c.transformer_depth[i], c.use_linear_projection != 0, down[i].attn.back());
+                }
+                skip_ch.push_back(cin);
+            }
+            if (i < n - 1) {
+                down[i].has_resample = true;
+                down[i].resample.cin = cin; down[i].resample.cout = cin;
+                down[i].resample.w = store.conv3(p + ".downsamplers.0.conv", cin, cin, &down[i].resample.b);
+                skip_ch.push_back(cin);
+            }
+        }
+        reg_resnet(store, "mid_block.resnets.0", cin, cin, true, tproj_w, tproj_b, temb_dim, temb_cols, mid0);
+        reg_transformer(store, "mid_block.attentions.0", cin, c.num_heads[n - 1], c.cross_attention_dim,
+                        c.transformer_depth[n - 1], c.use_linear_projection != 0, mid_attn);
+        reg_resnet(store, "mid_block.resnets.1", cin, cin, true, tproj_w, tproj_b, temb_dim, temb_cols, mid1);
+        return 0;
+    }
+    int build_done(const Store& store) const {
+        if (temb_cols != temb_total) GYRE_FAIL(GYRE_ERR_INVALID, "internal: temb column count mismatch");
+        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
+        return 0;
+    }
+    // What every walk starts with (e.st and the arena are set): the latents -> NHWC xin (Bx samples: the prefix a CFG pair shares takes
+    // half the batch), the bf16 copy cx of a passed text context (cx_S > 0 rows per sample; 0 = none), the time-embedding MLP over
+    // Bt rows (1 = every sample at the same timestep) plus temb_add (SDXL-style added conditioning, emb = time_embedding(t) + aug_emb
+    // from the host), and every resnet's Linear(SiLU(temb)) in one launch -> tp.  Arena order: xin, cx, emb, t1, t2, tp - the
+    // arena is first-fit and its peak is what *_workspace_bytes reports; emb, t1 and t2 go back to it.
+    template <typename Cfg>
+    int time_embed(Exec& e, const Cfg& c, const void* x, int xdt, int Bx, int H, int W, const void* ctx, int cdt, int cx_S,
+                   const int64_t* t, int B, int Bt, const float* temb_add, Tn& xin, Tn& cx, Tn& tp) {
+        const int D = c.cross_attention_dim, c0 = c.block_out_channels[0];
+        hipStream_t st = e.st;
+        Tn emb, t1, t2;
+        TRY(e.alloc(xin, Bx, H, W, pad8(c.in_channels)));
+        if (cx_S) TRY(e.alloc(cx, B, cx_S, 1, D));
+        TRY(e.alloc(emb, B, 1, 1, c0, 4));
+        TRY(e.alloc(t1, B, 1, 1, temb_dim, 4));
+        TRY(e.alloc(t2, B, 1, 1, temb_dim, 4));
+        TRY(e.alloc(tp, B, 1, 1, temb_cols, 4));
+        if (!e.dry()) {
+            TRY(launch_nchw_to_nhwc(st, x, xdt, Bx, c.in_channels, H * W, xin.C, xin.p));
+            if (cx_S) TRY(launch_ctx_to_bf16(st, ctx, cdt, (size_t)B * cx_S * D, cx.p));
+            TRY(launch_timestep_linear(st, t, Bt, c0, c.flip_sin_to_cos, c.freq_shift, (float*)emb.p, te1w, te1b, temb_dim, (float*)t1.p,
+                                       temb_dim));
+            TRY(launch_rowvec_linear(st, (float*)t1.p, Bt, temb_dim, te2w, te2b, temb_dim, 1, (float*)t2.p, temb_dim));
+            if (temb_add) TRY(launch_add_f32(st, (float*)t2.p, temb_add, (size_t)B * temb_dim));
+            TRY(launch_rowvec_linear(st, (float*)t2.p, Bt, temb_dim, tproj_w, tproj_b, temb_cols, 1, (float*)tp.p, temb_cols));
+        }
+        e.free(emb); e.free(t1); e.free(t2);
+        return 0;
+    }
+};
+
+// ------------------------------------------------------------------------------------------
 // UNet
 // ------------------------------------------------------------------------------------------
 // Bookkeeping between the forward and the reverse half of a UNet input-gradient call (model_vjp.hip): one node per resnet
@@ -1166,25 +1268,19 @@ struct UNetVjpState {
     Tn h, cx, tp;
 };
 
-struct gyre_unet {
+struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_out and conv_out
     gyre_unet_cfg cfg;
     Store store;
     Exec ex;
     UNetVjpState vjp;
     bool finalized = false;
-    int temb_dim = 0, temb_cols = 0;
     std::map<std::array<long, 7>, size_t> ws_memo;   // gyre_unet_workspace_bytes: peak per (B, H, W, S, tome_r, cached context, planner state)
     int* hint_flag = nullptr;      // device word of the hint verifier (GYRE_VERIFY_HINTS=1)
     bool hint_uniform_t = false;   // gyre_unet_hint_uniform_timestep: consumed by the next forward
     bool hint_cfg_pairs = false;   // gyre_unet_hint_cfg_pairs: consumed by the next forward
-    int gn_unit = 0;     // gcd of block_out_channels / groups: every GroupNorm group (skip concats included) is a whole number of units
-    bf16_t *te1w, *te2w; float *te1b, *te2b;
-    bf16_t* tproj_w = nullptr; float* tproj_b = nullptr;
-    ConvW conv_in, conv_out;
+    std::vector<Level> up;
     float *ong, *onb;
-    struct Level { std::vector<ResW> res; std::vector<TransW> attn; ConvW resample; bool has_resample = false; };
-    std::vector<Level> down, up;
-    ResW mid0, mid1; TransW mid_attn;
+    ConvW conv_out;
     // debug taps (parity tests): name -> (device f32 NCHW buffer, capacity in bytes); consumed by the next forward
     std::map<std::string, std::pair<float*, size_t>> taps;
     // text-context cache (cross-attention K / V^T per layer, and the bf16 copy of the context)
@@ -1199,8 +1295,7 @@ struct gyre_unet {
     ~gyre_unet() { for (auto& sl : ctx_slots) if (sl.buf) (void)hipFree(sl.buf); }
 
     template <typename F> void for_each_cross_attn(F f) {
-        for (auto& lv : down) for (auto& t : lv.attn) for (auto& b : t.blocks) f(b.a2);
-        for (auto& b : mid_attn.blocks) f(b.a2);
+        UNetTrunk::for_each_cross_attn(f);
         for (auto& lv : up) for (auto& t : lv.attn) for (auto& b : t.blocks) f(b.a2);
     }
     // Project the text context through every cross-attention to_k / to_v once; the denoising loop then calls
@@ -1210,114 +1305,27 @@ struct gyre_unet {
         if (slot < 0 || slot >= GYRE_CTX_SLOTS) GYRE_FAIL(GYRE_ERR_INVALID, "unet: context slot out of range");
         cur_slot = slot;
         CtxSlot& sl = ctx_slots[slot];
-        void*& kv_buf = sl.buf; size_t& kv_bytes = sl.bytes; bool& cache_valid = sl.valid; int &cache_B = sl.B, &cache_S = sl.S;
-        std::vector<CtxKV>& kv_cache = sl.kv;
-        const int D = cfg.cross_attention_dim, Spad = (S + 7) / 8 * 8;
-        size_t need = align_up((size_t)B * S * D * 2, 256);
-        for_each_cross_attn([&](AttnW& a) { need += align_up((size_t)B * S * a.c * 2, 256) + align_up((size_t)B * a.c * Spad * 2, 256); });
-        cache_valid = false;
-        if (need > kv_bytes) {
-            if (kv_buf) { GYRE_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(kv_buf); kv_buf = nullptr; kv_bytes = 0; }
-            GYRE_HIP_CHECK(hipMalloc(&kv_buf, need));
-            kv_bytes = need;
-        }
-        GYRE_HIP_CHECK(hipMemsetAsync(kv_buf, 0, need, st));   // V^T pad columns must be finite
-        char* ptr = (char*)kv_buf;
-        bf16_t* cx = (bf16_t*)ptr; ptr += align_up((size_t)B * S * D * 2, 256);
-        TRY(launch_ctx_to_bf16(st, ctx, cdt, (size_t)B * S * D, cx));
-        kv_cache.clear();
-        int rc = 0;
-        for_each_cross_attn([&](AttnW& a) {
-            if (rc) return;
-            CtxKV e;
-            e.k = (bf16_t*)ptr; ptr += align_up((size_t)B * S * a.c * 2, 256);
-            e.vt = (bf16_t*)ptr; ptr += align_up((size_t)B * a.c * Spad * 2, 256);
-            GemmParams p;
-            p.A = cx; p.lda = D; p.mode = GEMM_LINEAR; p.W = a.wk; p.K = D; p.N = a.c; p.M = B * S; p.bias = a.bk; p.samples = B;
-            p.out = e.k; p.ldc = a.c; p.out_mode = OUT_BF16;
-            rc = launch_gemm(st, p);
-            if (rc) return;
-            GemmParams q;
-            q.A = cx; q.lda = D; q.mode = GEMM_LINEAR; q.W = a.wv; q.K = D; q.N = a.c; q.M = B * S; q.bias = a.bv; q.samples = B;
-            q.out = e.vt; q.out_mode = OUT_BF16_T; q.tokens_per_batch = S; q.ldt = Spad;
-            rc = launch_gemm(st, q);
-            kv_cache.push_back(e);
-        });
-        if (rc) return rc;
-        cache_B = B; cache_S = S; cache_valid = true;
+        sl.valid = false;
+        TRY(project_context(st, ctx, cdt, B, S, cfg.cross_attention_dim, [&](auto f) { for_each_cross_attn(f); }, sl.buf, sl.bytes, sl.kv));
+        sl.B = B; sl.S = S; sl.valid = true;
         return 0;
     }
 
     int build() {
         const gyre_unet_cfg& c = cfg;
         const int n = c.n_levels;
-        if (n < 1 || n > GYRE_MAX_LEVELS) GYRE_FAIL(GYRE_ERR_INVALID, "n_levels out of range");
-        for (int i = 0; i < n; ++i) {
-            if (c.block_out_channels[i] % c.norm_num_groups || c.block_out_channels[i] % 8)
-                GYRE_FAIL(GYRE_ERR_INVALID, "block_out_channels must be multiples of norm_num_groups and 8");
-            if (c.attn_levels[i] && (c.block_out_channels[i] % c.num_heads[i] || (c.block_out_channels[i] / c.num_heads[i]) % 8))
-                GYRE_FAIL(GYRE_ERR_INVALID, "head dim must be a multiple of 8");
-        }
-        if (c.cross_attention_dim % 8) GYRE_FAIL(GYRE_ERR_INVALID, "cross_attention_dim must be a multiple of 8");
-        ex.groups = c.norm_num_groups;
-        ex.store = &store;
-        gn_unit = 0;
-        for (int i = 0; i < n; ++i) {
-            int a = c.block_out_channels[i] / c.norm_num_groups, b = gn_unit;
-            while (b) { const int t = a % b; a = b; b = t; }
-            gn_unit = a;
-        }
-        const int c0 = c.block_out_channels[0];
-        temb_dim = 4 * c0;
-        // total columns of the batched time_emb_proj
-        int total_cols = 0;
-        for (int i = 0; i < n; ++i) total_cols += c.layers_per_block * c.block_out_channels[i];
-        total_cols += 2 * c.block_out_channels[n - 1];
-        for (int i = 0; i < n; ++i) total_cols += (c.layers_per_block + 1) * c.block_out_channels[n - 1 - i];
-        tproj_w = (bf16_t*)store.dmalloc((size_t)total_cols * temb_dim * 2, true);
-        tproj_b = (float*)store.dmalloc((size_t)total_cols * 4, true);
-        if (!tproj_w || !tproj_b) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-
-        te1w = store.mat("time_embedding.linear_1", temb_dim, c0, false, true, &te1b);
-        te2w = store.mat("time_embedding.linear_2", temb_dim, temb_dim, false, true, &te2b);
-        conv_in.cin = pad8(c.in_channels); conv_in.cout = c0;
-        conv_in.w = store.conv3("conv_in", c0, c.in_channels, &conv_in.b);
-        std::vector<int> skip_ch{c0};
-        int cin = c0;
-        down.resize(n);
-        for (int i = 0; i < n; ++i) {
-            const int co = c.block_out_channels[i];
-            for (int j = 0; j < c.layers_per_block; ++j) {
-                std::string p = "down_blocks." + std::to_string(i);
-                down[i].res.emplace_back();
-                reg_resnet(store, p + ".resnets." + std::to_string(j), cin, co, true, tproj_w, tproj_b, temb_dim, temb_cols,
-                           down[i].res.back());
-                cin = co;
-                if (c.attn_levels[i]) {
-                    down[i].attn.emplace_back();
-                    reg_transformer(store, p + ".attentions." + std::to_string(j), cin, c.num_heads[i], c.cross_attention_dim,
-                                    c.transformer_depth[i], c.use_linear_projection != 0, down[i].attn.back());
-                }
-                skip_ch.push_back(cin);
-            }
-            if (i < n - 1) {
-                down[i].has_resample = true;
-                down[i].resample.cin = cin; down[i].resample.cout = cin;
-                down[i].resample.w = store.conv3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv", cin, cin,
-                                                 &down[i].resample.b);
-                skip_ch.push_back(cin);
-            }
-        }
-        reg_resnet(store, "mid_block.resnets.0", cin, cin, true, tproj_w, tproj_b, temb_dim, temb_cols, mid0);
-        reg_transformer(store, "mid_block.attentions.0", cin, c.num_heads[n - 1], c.cross_attention_dim,
-                        c.transformer_depth[n - 1], c.use_linear_projection != 0, mid_attn);
-        reg_resnet(store, "mid_block.resnets.1", cin, cin, true, tproj_w, tproj_b, temb_dim, temb_cols, mid1);
+        TRY(check_cfg(c, ""));
+        int up_cols = 0;                                   // time_emb_proj columns of the up path
+        for (int i = 0; i < n; ++i) up_cols += (c.layers_per_block + 1) * c.block_out_channels[i];
+        TRY(build_trunk(store, ex, c, up_cols, [] {}));
+        std::vector<int> skips = skip_ch;
+        int cin = c.block_out_channels[n - 1];
         up.resize(n);
         for (int i = 0; i < n; ++i) {
             const int lvl = n - 1 - i, co = c.block_out_channels[lvl];
             std::string p = "up_blocks." + std::to_string(i);
             for (int j = 0; j < c.layers_per_block + 1; ++j) {
-                int sk = skip_ch.back(); skip_ch.pop_back();
+                int sk = skips.back(); skips.pop_back();
                 up[i].res.emplace_back();
                 reg_resnet(store, p + ".resnets." + std::to_string(j), cin + sk, co, true, tproj_w, tproj_b, temb_dim,
                            temb_cols, up[i].res.back());
@@ -1338,9 +1346,7 @@ struct gyre_unet {
         store.vec("conv_norm_out.weight", cin, &ong); store.vec("conv_norm_out.bias", cin, &onb);
         conv_out.cin = cin; conv_out.cout = c.out_channels;
         conv_out.w = store.conv3("conv_out", c.out_channels, cin, &conv_out.b);
-        if (temb_cols != total_cols) GYRE_FAIL(GYRE_ERR_INVALID, "internal: temb column count mismatch");
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
+        return build_done(store);
     }
 
     // ControlNet-style residual injection (reference gyre/pipeline/controlnet/unet_patcher.py:30-95, fed by
@@ -1408,25 +1414,8 @@ struct gyre_unet {
                 if (bad & 2) GYRE_FAIL(GYRE_ERR_INVALID, "gyre_unet_hint_cfg_pairs was set, but sample b and sample b + B/2 of this call differ in their latents");
             }
         }
-        Tn xin, cx, emb, t1, t2, tp;
-        TRY(e.alloc(xin, Bp, H, W, pad8(c.in_channels)));
-        if (!cached) TRY(e.alloc(cx, B, S, 1, D));
-        TRY(e.alloc(emb, B, 1, 1, c.block_out_channels[0], 4));
-        TRY(e.alloc(t1, B, 1, 1, temb_dim, 4));
-        TRY(e.alloc(t2, B, 1, 1, temb_dim, 4));
-        TRY(e.alloc(tp, B, 1, 1, temb_cols, 4));
-        if (!dry) {
-            TRY(launch_nchw_to_nhwc(st, x, xdt, Bp, c.in_channels, H * W, xin.C, xin.p));
-            if (!cached) TRY(launch_ctx_to_bf16(st, ctx, cdt, (size_t)B * S * D, cx.p));
-            TRY(launch_timestep_linear(st, t, Bt, c.block_out_channels[0], c.flip_sin_to_cos, c.freq_shift, (float*)emb.p, te1w, te1b,
-                                       temb_dim, (float*)t1.p, temb_dim));
-            TRY(launch_rowvec_linear(st, (float*)t1.p, Bt, temb_dim, te2w, te2b, temb_dim, 1, (float*)t2.p, temb_dim));
-            // SDXL-style added conditioning (text_time): emb = time_embedding(t) + aug_emb, aug_emb from the host
-            if (temb_add) TRY(launch_add_f32(st, (float*)t2.p, temb_add, (size_t)B * temb_dim));
-            // every resnet's Linear(SiLU(temb)) in one launch
-            TRY(launch_rowvec_linear(st, (float*)t2.p, Bt, temb_dim, tproj_w, tproj_b, temb_cols, 1, (float*)tp.p, temb_cols));
-        }
-        e.free(emb); e.free(t1); e.free(t2);
+        Tn xin, cx, tp;
+        TRY(time_embed(e, c, x, xdt, Bp, H, W, ctx, cdt, cached ? 0 : S, t, B, Bt, temb_add, xin, cx, tp));
         const float* tproj = (const float*)tp.p;
 
         auto tap = [&](const std::string& name, const Tn& t, int channels) -> int {
@@ -1715,6 +1704,31 @@ struct gyre_vae {
         return 0;
     }
 };
+
+// ------------------------------------------------------------------------------------------
+// C ABI bodies every handle type shares (gyre_{unet,vae,ctrl,t2i}_create / _num_params / _param_key / _finalize)
+// ------------------------------------------------------------------------------------------
+template <typename H, typename Cfg> static int handle_create(const Cfg* cfg, int device, H** out) {
+    if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    GYRE_HIP_CHECK(hipSetDevice(device));
+    auto* h = new H();
+    h->cfg = *cfg; h->store.device = device;
+    int rc = h->build();
+    if (rc) { delete h; return rc; }
+    GYRE_HIP_CHECK(hipDeviceSynchronize());  // creation only: zero-fills of the weight buffers are complete
+    *out = h;
+    return 0;
+}
+template <typename H> static int handle_num_params(const H* h) { return h ? (int)h->store.params.size() : 0; }
+template <typename H> static const char* handle_param_key(const H* h, int i) {
+    return (h && i >= 0 && i < (int)h->store.params.size()) ? h->store.params[i]->key.c_str() : nullptr;
+}
+template <typename H> static int handle_finalize(H* h) {
+    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
+    TRY(h->store.finalize());
+    h->finalized = true;
+    return 0;
+}
 
 // model_vjp.hip: forward + reverse sweep in one call (dry = size the workspace only)
 int gyre_unet_run_vjp(gyre_unet& u, bool dry, hipStream_t st, const void* x, int xdt, const int64_t* t, const void* ctx, int cdt,

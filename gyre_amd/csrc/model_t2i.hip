@@ -167,33 +167,16 @@ struct gyre_t2i {
 
 extern "C" {
 
-int gyre_t2i_create(const gyre_t2i_cfg* cfg, int device, gyre_t2i** out) {
-    if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    GYRE_HIP_CHECK(hipSetDevice(device));
-    auto* h = new gyre_t2i();
-    h->cfg = *cfg; h->store.device = device;
-    int rc = h->build();
-    if (rc) { delete h; return rc; }
-    GYRE_HIP_CHECK(hipDeviceSynchronize());  // creation only: zero-fills of the weight buffers are complete
-    *out = h;
-    return 0;
-}
+int gyre_t2i_create(const gyre_t2i_cfg* cfg, int device, gyre_t2i** out) { return handle_create(cfg, device, out); }
 void gyre_t2i_destroy(gyre_t2i* h) { delete h; }
-int gyre_t2i_num_params(const gyre_t2i* h) { return h ? (int)h->store.params.size() : 0; }
-const char* gyre_t2i_param_key(const gyre_t2i* h, int i) {
-    return (h && i >= 0 && i < (int)h->store.params.size()) ? h->store.params[i]->key.c_str() : nullptr;
-}
+int gyre_t2i_num_params(const gyre_t2i* h) { return handle_num_params(h); }
+const char* gyre_t2i_param_key(const gyre_t2i* h, int i) { return handle_param_key(h, i); }
 int gyre_t2i_set_weight(gyre_t2i* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
     if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     h->finalized = false;
     return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
 }
-int gyre_t2i_finalize(gyre_t2i* h, void* st) {
-    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
-    TRY(h->store.finalize());
-    h->finalized = true;
-    return 0;
-}
+int gyre_t2i_finalize(gyre_t2i* h, void* st) { return handle_finalize(h); }
 size_t gyre_t2i_workspace_bytes(gyre_t2i* h, int B, int H, int W) {
     if (!h) return 0;
     return h->run(true, nullptr, nullptr, 0, B, H, W, nullptr, 0, nullptr, 0) ? 0 : h->ex.arena.peak;

@@ -8,7 +8,7 @@
 //   gyre_unet_vjp(x, t, ctx, d_eps)        -> eps, d_x
 //   gyre_vae_decode_vjp(z, d_image)        -> image, d_z
 // Transposed weights (W^T for linears, rotated [Cin][3][3][Cout] for convs) are made on first use and kept next to the forward
-// weights (Store::wt_cache, +1.7 GB for SD1.5); every gyre_*_set_weight bumps a version, so a per-request LoRA re-upload
+// weights (Store::derived, DC_TRANSPOSED: +1.7 GB for SD1.5); every gyre_*_set_weight bumps a version, so a per-request LoRA re-upload
 // refreshes them at the next sweep.  Bare op calls (no model handle) transpose into the workspace instead.
 #include "model_impl.h"
 
@@ -20,7 +20,7 @@ int weight_t_linear(Exec& e, const bf16_t* w, int N, int K, Tn& tmp, const bf16_
     if (e.store) {
         if (e.dry()) { *out = nullptr; return 0; }
         bool fresh = false;
-        bf16_t* p = e.store->wt_lookup(w, (size_t)K * N * 2, &fresh);
+        bf16_t* p = (bf16_t*)e.store->derived(Store::DC_TRANSPOSED, w, (size_t)K * N * 2, &fresh);
         if (!p) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed (transposed weight cache)");
         if (!fresh) TRY(launch_transpose(e.st, w, K, N, K, p, N, 1, 0, 0));
         *out = p;
@@ -36,7 +36,7 @@ int weight_t_conv(Exec& e, const bf16_t* w, int co, int cin_pad, Tn& tmp, const 
     if (e.store) {
         if (e.dry()) { *out = nullptr; return 0; }
         bool fresh = false;
-        bf16_t* p = e.store->wt_lookup(w, (size_t)cin_pad * 9 * co * 2, &fresh);
+        bf16_t* p = (bf16_t*)e.store->derived(Store::DC_TRANSPOSED, w, (size_t)cin_pad * 9 * co * 2, &fresh);
         if (!p) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed (transposed weight cache)");
         if (!fresh) TRY(launch_conv_weight_t(e.st, w, co, cin_pad, p));
         *out = p;
@@ -382,23 +382,8 @@ int gyre_unet_vjp_forward(gyre_unet& u, bool dry, hipStream_t st, const void* x,
     e.arena.reset((char*)ws, ws_bytes, dry);
     e.st = st; e.batch = B; e.ctx_cache = nullptr; e.ctx_layer = 0; e.cs_unit = 0;   // the reverse sweep recomputes its own GroupNorm statistics
     const int D = c.cross_attention_dim;
-    Tn xin, cx, emb, t1, t2, tp;
-    TRY(e.alloc(xin, B, H, W, pad8(c.in_channels)));
-    TRY(e.alloc(cx, B, S, 1, D));
-    TRY(e.alloc(emb, B, 1, 1, c.block_out_channels[0], 4));
-    TRY(e.alloc(t1, B, 1, 1, u.temb_dim, 4));
-    TRY(e.alloc(t2, B, 1, 1, u.temb_dim, 4));
-    TRY(e.alloc(tp, B, 1, 1, u.temb_cols, 4));
-    if (!dry) {
-        TRY(launch_nchw_to_nhwc(st, x, xdt, B, c.in_channels, H * W, xin.C, xin.p));
-        TRY(launch_ctx_to_bf16(st, ctx, cdt, (size_t)B * S * D, cx.p));
-        TRY(launch_timestep_linear(st, t, B, c.block_out_channels[0], c.flip_sin_to_cos, c.freq_shift, (float*)emb.p, u.te1w, u.te1b,
-                                   u.temb_dim, (float*)t1.p, u.temb_dim));
-        TRY(launch_rowvec_linear(st, (float*)t1.p, B, u.temb_dim, u.te2w, u.te2b, u.temb_dim, 1, (float*)t2.p, u.temb_dim));
-        if (temb_add) TRY(launch_add_f32(st, (float*)t2.p, temb_add, (size_t)B * u.temb_dim));
-        TRY(launch_rowvec_linear(st, (float*)t2.p, B, u.temb_dim, u.tproj_w, u.tproj_b, u.temb_cols, 1, (float*)tp.p, u.temb_cols));
-    }
-    e.free(emb); e.free(t1); e.free(t2);
+    Tn xin, cx, tp;
+    TRY(u.time_embed(e, c, x, xdt, B, H, W, ctx, cdt, S, t, B, B, temb_add, xin, cx, tp));
     const float* tproj = (const float*)tp.p;
 
     // ---- forward, keeping what the reverse sweep needs (forward activations are not returned to the arena) ----
