@@ -211,6 +211,7 @@ _SIGS = {
     "gyre_op_repack_lora": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(LoraPair), _vp]),
     "gyre_op_repack_delta": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, C.POINTER(DeltaTerm), _vp]),
     "gyre_op_lyco_core": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gyre_op_merge_delta": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(DeltaTerm), _vp, _i]),
     "gyre_op_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_qkv": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i]),
     "gyre_op_attention_ex": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),

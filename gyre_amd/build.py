@@ -34,7 +34,10 @@ PER_FILE_FLAGS = {"kernels_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 # count in vmcnt and may be acknowledged before older loads, which would let the wait pass while a tile is still in
 # flight.  Every compile therefore records the register / scratch use of each kernel (clang remarks), and
 # tests/test_host_cpu.py::test_counted_vmcnt_kernels_do_not_spill checks it.  Kernels listed here drain with vmcnt(0).
-RESOURCE_FILES = ("kernels_attn.hip", "kernels_gemm.hip", "kernels_gemm4s.hip", "kernels_gemm_ar.hip", "kernels_gemm_sm.hip")
+# kernels_lyco.hip has no counted waits; it is recorded because its kernels hold up to 48 accumulator registers per lane next to 17 KB of
+# LDS and must stay free of scratch as well (tests/test_merge_delta_ref_host.py reads k_merge_delta's entry).
+RESOURCE_FILES = ("kernels_attn.hip", "kernels_gemm.hip", "kernels_gemm4s.hip", "kernels_gemm_ar.hip", "kernels_gemm_sm.hip",
+                  "kernels_lyco.hip")
 # k_gemm4s: its LDS-DMA requests are always retired with vmcnt(0); the 256x256 form spills in the epilogue only
 SCRATCH_ALLOWED = ("k_attn3ILi80E", "k_gemm4s")
 RESOURCES_JSON = os.path.join(HERE, "build", "kernel_resources.json")

@@ -130,6 +130,10 @@ struct DeltaArgs {
 };
 int launch_repack_delta(hipStream_t st, const void* base, int base_dtype, int O, int I, int KH, int KW, int Ipad, int geglu_interleave,
                         float scale_p, const DeltaArgs& da, bf16_t* out);
+// the same sum on a plain matrix (k_merge_delta): out [O][I] row-major of out_dtype (0 fp32, 1 bf16, 2 fp16 - in BOTH storage
+// flavours) = round_out(base + sum_j s[j] D_j), no interleave, no pad columns, no folded factor.  I % 4 == 0; out must not overlap
+// base or an operand.  What a host module outside the native store (the CLIP text encoder) gets its per-request adapters with.
+int launch_merge_delta(hipStream_t st, const void* base, int base_dtype, int O, int I, const DeltaArgs& da, void* out, int out_dtype);
 // out[a][c][t] = sum_b core[a][b][t] * right[b][c]  (fp32, b ascending): a Tucker core folded into the right operand of a term
 int launch_lyco_core(hipStream_t st, const void* core, int core_dtype, const void* right, int right_dtype, int A, int B, int C, int T,
                      float* out);

@@ -40,6 +40,21 @@
 // staging phases overlap each other's FMA phases.  The dense forms (KRON dense right factor, FULL) read their operand once per
 // output element, like base.
 //
+// k_merge_delta<OUT>: the same tile with another store policy (lyco_tile<OUT>), for a weight that lives outside the native store - a
+// CLIP text encoder's nn.Linear, a plain row-major [O][I] tensor of the dtype the encoder was loaded in:
+//   out[o][i] = round_out( base[o][i] + sum_j s_j * D_j[o][i] )        OUT = GYRE_F32 | GYRE_BF16 | GYRE_F16, in BOTH storage builds
+// Matrix only (KK = 1), no interleave, no pad columns (I % 4 == 0), no scale_p.  Operation order (restated in
+// tests/merge_delta_ref.py - change both or neither): exactly the one above up to and including the last fma; then
+//   out = round_out(acc)      fp32: acc as it stands, 16 bytes per lane;  bf16 / fp16: (__bf16) / (_Float16) conversion, round to
+//                             nearest even, 8 bytes per lane - explicit conversions, f32_to_bf16 means the BUILD's storage type
+// With no terms and out type = base type this copies base bit for bit (exact conversion to fp32 and back): how an adapter is taken
+// off.  out may overlap neither base nor an operand (other workgroups still read them): launch_merge_delta refuses that, as it
+// refuses everything delta_args_check refuses, before the launch.  The three instantiations have KK, Ipad and geglu as constants:
+// the compiler reports 117 VGPRs, no scratch, 4 waves per SIMD, 17 KB of LDS for each in both builds (gyre_amd/build.py records it,
+// tests/test_merge_delta_ref_host.py reads the record); k_repack_delta, the packed instantiation of the same tile, keeps the numbers
+// stated above.  These are the COMPILER's numbers; the LDS banking statements above are reasoned and hold for both kernels (same
+// staging, same reads); MEASURED is only the request time in profiles/text_adapter_request_time.json.
+//
 // k_lyco_core:  out[a][c][t] = sum_b core[a][b][t] * right[b][c]   (fp32 out, b ascending with fma from 0, inputs of any dtype).
 // down' = core(mid, down) makes a LoCon Tucker form a LORA term, wb' = core(t, wb) a LoHa / LoKr one; with T = 1 it is
 // w1 = w1a @ w1b.  Runs once per uploaded file, one thread per output element.
@@ -96,8 +111,15 @@ __device__ __forceinline__ void lyco_product(float (&d)[4][4], float (*Us)[LYCO_
     }
 }
 
-__global__ __launch_bounds__(256) void k_repack_delta(const void* __restrict__ base, int bdt, int O, int I, int KK, int Ipad, int geglu,
-                                                      float scale_p, DeltaArgs da, bf16_t* __restrict__ out) {
+// The tile of both kernels.  OUT is the store policy: LYCO_OUT_PACKED writes the repacked storage layout (k_repack_delta: tap-major
+// padded columns, GEGLU interleave, round_storage(acc * scale_p)), GYRE_F32 / BF16 / F16 write a row-major [O][I] matrix of that type
+// (k_merge_delta: KK = 1, Ipad = I, geglu = 0 are constants there, acc is rounded as it stands).  Everything in front of the store
+// is the same code.
+#define LYCO_OUT_PACKED (-1)
+template <int OUT>
+__device__ __forceinline__ void lyco_tile(const void* __restrict__ base, int bdt, int O, int I, int KK, int Ipad, int geglu, float scale_p,
+                                          const DeltaArgs& da, void* __restrict__ outv) {
+    if constexpr (OUT != LYCO_OUT_PACKED) { KK = 1; Ipad = I; geglu = 0; }
     __shared__ __attribute__((aligned(16))) float Us[LYCO_RCHUNK][LYCO_LD];
     __shared__ __attribute__((aligned(16))) float Ds[LYCO_RCHUNK][LYCO_LD];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -196,13 +218,33 @@ __global__ __launch_bounds__(256) void k_repack_delta(const void* __restrict__ b
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (!rok[i]) continue;
-        uint32_t h[4];
+        const size_t at = (size_t)(row0 + ty * 4 + i) * Kp + c0;
+        if constexpr (OUT == 0) {                 // fp32: stored as computed, 16 bytes per lane (Kp = I, I % 4 == 0: all 4 columns valid)
+            f32x4_t w = {acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+            *(f32x4_t*)((float*)outv + at) = w;
+        } else {
+            uint32_t h[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) h[j] = lyco_scale_round(ci0 + j < I ? acc[i][j] : 0.f, scale_p);
-        uint2 w;
-        w.x = h[0] | (h[1] << 16); w.y = h[2] | (h[3] << 16);
-        *(uint2*)(out + (size_t)(row0 + ty * 4 + i) * Kp + c0) = w;         // 8 bytes per lane along K
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (OUT == LYCO_OUT_PACKED) h[j] = lyco_scale_round(ci0 + j < I ? acc[i][j] : 0.f, scale_p);
+                else if constexpr (OUT == 1) h[j] = __builtin_bit_cast(uint16_t, (__bf16)acc[i][j]);          // round to nearest even, whatever
+                else h[j] = __builtin_bit_cast(uint16_t, (_Float16)acc[i][j]);                                 // the library's storage type
+            }
+            uint2 w;
+            w.x = h[0] | (h[1] << 16); w.y = h[2] | (h[3] << 16);
+            *(uint2*)((uint16_t*)outv + at) = w;                                // 8 bytes per lane along K
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void k_repack_delta(const void* __restrict__ base, int bdt, int O, int I, int KK, int Ipad, int geglu,
+                                                      float scale_p, DeltaArgs da, bf16_t* __restrict__ out) {
+    lyco_tile<LYCO_OUT_PACKED>(base, bdt, O, I, KK, Ipad, geglu, scale_p, da, out);
+}
+
+template <int OUT>
+__global__ __launch_bounds__(256) void k_merge_delta(const void* __restrict__ base, int bdt, int O, int I, DeltaArgs da, void* __restrict__ out) {
+    lyco_tile<OUT>(base, bdt, O, I, 1, I, 0, 1.f, da, out);
 }
 
 __global__ __launch_bounds__(256) void k_lyco_core(const void* __restrict__ core, int cdt, const void* __restrict__ right, int rdt,
@@ -258,6 +300,45 @@ int launch_repack_delta(hipStream_t st, const void* base, int base_dtype, int O,
     GyreProfScope prof_(KC_LORA, st, flops, (double)O * Kp * 2.0 + (double)O * I * KH * KW * (base_dtype == 0 ? 4.0 : 2.0));
     hipLaunchKernelGGL(k_repack_delta, dim3((Kp + LYCO_TILE - 1) / LYCO_TILE, (O + LYCO_TILE - 1) / LYCO_TILE), dim3(256), 0, st,
                        base, base_dtype, O, I, KH * KW, Ipad, geglu, scale_p, da, out);
+    GYRE_LAUNCH_CHECK();
+    return 0;
+}
+
+// [p, p + bytes) and [q, q + qbytes) share a byte
+static inline bool lyco_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qbytes && b < a + bytes;
+}
+
+int launch_merge_delta(hipStream_t st, const void* base, int base_dtype, int O, int I, const DeltaArgs& da, void* out, int out_dtype) {
+    if (!base || !out) GYRE_FAIL(-1, "merge_delta: null argument");
+    if (O < 1 || I < 1 || I % 4) GYRE_FAIL(-1, "merge_delta: needs O, I >= 1 and I a multiple of 4");
+    if (base_dtype < 0 || base_dtype > 2 || out_dtype < 0 || out_dtype > 2) GYRE_FAIL(-1, "merge_delta: bad base or output dtype");
+    double flops = 0;
+    if (int rc = delta_args_check(da, O, I, 1.0, &flops)) return rc;
+    if ((size_t)O * I >= ((size_t)1 << 31)) GYRE_FAIL(-1, "merge_delta: matrix too large");
+    const size_t esz[3] = {4, 2, 2};
+    const size_t n = (size_t)O * I, obytes = n * esz[out_dtype];
+    if ((uintptr_t)out % (4 * esz[out_dtype])) GYRE_FAIL(-1, "merge_delta: out must be aligned to 4 elements");
+    // the kernel reads base and the operands while other workgroups store: out may share no byte with any of them
+    bool alias = lyco_overlap(out, obytes, base, n * esz[base_dtype]);
+    for (int p = 0; p < da.n; ++p) {
+        const int kind = da.kind[p];
+        const size_t Ro = kind == DELTA_KRON ? (size_t)(O / da.O1[p]) : (size_t)O, Co = kind == DELTA_KRON ? (size_t)(I / da.I1[p]) : (size_t)I;
+        for (int q = 0; q < (kind == DELTA_HADA ? 2 : 1); ++q) {
+            const size_t e = esz[da.dtype[p][q]], r = (size_t)da.rank[p][q];
+            const bool dense = kind == DELTA_FULL || (kind == DELTA_KRON && r == 0);
+            alias |= lyco_overlap(out, obytes, da.down[p][q], (dense ? Ro : r) * Co * e);
+            if (!dense) alias |= lyco_overlap(out, obytes, da.up[p][q], Ro * r * e);
+        }
+        if (kind == DELTA_KRON) alias |= lyco_overlap(out, obytes, da.w1[p], (size_t)da.O1[p] * da.I1[p] * 4);
+    }
+    if (alias) GYRE_FAIL(-1, "merge_delta: out overlaps base or an operand (the caller keeps the original weight)");
+    GyreProfScope prof_(KC_LORA, st, flops, (double)obytes + (double)n * esz[base_dtype]);
+    const dim3 grid((I + LYCO_TILE - 1) / LYCO_TILE, (O + LYCO_TILE - 1) / LYCO_TILE);
+    if (out_dtype == 0) hipLaunchKernelGGL(k_merge_delta<0>, grid, dim3(256), 0, st, base, base_dtype, O, I, da, out);
+    else if (out_dtype == 1) hipLaunchKernelGGL(k_merge_delta<1>, grid, dim3(256), 0, st, base, base_dtype, O, I, da, out);
+    else hipLaunchKernelGGL(k_merge_delta<2>, grid, dim3(256), 0, st, base, base_dtype, O, I, da, out);
     GYRE_LAUNCH_CHECK();
     return 0;
 }

@@ -644,6 +644,13 @@ int gyre_op_repack_delta(void* st, const void* base, int base_dtype, int O, int 
     TRY(delta_terms_to_args(n_terms, terms, da));
     return launch_repack_delta((hipStream_t)st, base, base_dtype, O, I, KH, KW, I_pad, geglu, scale_p, da, (bf16_t*)out);
 }
+int gyre_op_merge_delta(void* st, const void* base, int base_dtype, int O, int I, int n_terms, const gyre_delta_term* terms, void* out,
+                        int out_dtype) {
+    if (!base || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    DeltaArgs da;
+    TRY(delta_terms_to_args(n_terms, terms, da));
+    return launch_merge_delta((hipStream_t)st, base, base_dtype, O, I, da, out, out_dtype);
+}
 int gyre_op_lyco_core(void* st, const void* core, int core_dtype, const void* right, int right_dtype, int A, int B, int Cn, int T,
                       float* out) {
     return launch_lyco_core((hipStream_t)st, core, core_dtype, right, right_dtype, A, B, Cn, T, out);

@@ -31,16 +31,22 @@ the adapter once per request, its states added inside the UNet on every step (gy
 control model runs once per UNet evaluation and its residuals go to the UNet's residual inputs (schedulers.UNetWithControlnet).
 Features outside the native hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py): depth maps /
 depth UNets, foreign hint handlers, style adapters and co-adapters, masked hints, hints together with hires fix / grafted inpaint /
-CLIP guidance / shard_devices, ControlNet hints with a 9-channel inpaint UNet, textual-inversion token embeddings.  CLIP guidance
+CLIP guidance / shard_devices, ControlNet hints with a 9-channel inpaint UNet.  CLIP guidance
 is implemented (gyre_amd/clipguided.py over the native input-gradient sweeps).  ``lora=`` takes LoRA files (kohya-ss, diffusers) and,
 as the reference routes them (unified_pipeline.py:2210-2233: what ``detect_lora_type`` refuses goes to ``apply_lycoris``), LyCORIS files
 (LoCon, LoHa, LoKr, full diff; gyre_amd/lycoris.py): one attach for the whole request, every touched weight repacked once on the
 device, taken off again at the start of the next request.  IA3, DyLoRA, sparse-bias LyCORIS modules and cloneofsimo LoRA files raise
-NotImplementedError.  The safety checker stays the host module the
+NotImplementedError.  The text side of a request (gyre_amd/text_adapters.py, SD1.x / 2.x engines): the ``lora_te_`` entries of the same
+files are merged into the text encoder's Linear weights (one gyre_op_merge_delta per touched weight, scaled by the ``"text_encoder"`` /
+``"*"`` weights as the reference's loop leaves them; a file with nothing but ``lora_te_`` entries works), and ``token_embeddings=``
+(textual inversion) adds its tokens to the request's own copy of the tokenizer and its rows to the token table; both are taken off at
+the start of the next request, before the prompts are encoded.  SDXL engines (``text_time``) raise NotImplementedError for
+``token_embeddings`` and ignore ``lora_te*`` entries.  The safety checker stays the host module the
 manager loaded; it is RUN exactly as the reference runs it (``_safety_check``), never skipped silently.
 """
 from __future__ import annotations
 
+import copy
 import functools
 from typing import Any, Callable, List, Optional
 
@@ -49,6 +55,7 @@ import torch
 from . import clipguided as CG
 from . import lora as LR
 from . import lycoris as LY
+from . import text_adapters as TA
 from .pipeline import GyrePipeline
 from .text import LPWTextEmbedder
 
@@ -100,6 +107,7 @@ class GyreUnifiedPipeline:
         self.safety_checker, self.feature_extractor = safety_checker, feature_extractor
         self.clip_model, self.clip_tokenizer = clip_model, clip_tokenizer
         self.hintset_manager, self.depth_unet = hintset_manager, depth_unet
+        self.inpaint_text_encoder = inpaint_text_encoder
         self.progress_bar: Optional[Callable] = None
         self._grafted_inpaint: Any = False
         self._hires_fix, self._hires_threshold_fraction = True, 0.0333
@@ -110,6 +118,7 @@ class GyreUnifiedPipeline:
         self._shard_bit_exact = False
         self._executor = None
         self._lora_uploads: list = []        # LoraFactors / LycoFactors of the last four LoRA / LyCORIS tensors mappings seen (_lora_factors)
+        self._text_uploads: list = []        # ... and their text-encoder sides (text_adapters.TextFactors, _text_factors)
         self.clip_default_config = CG.ClipGuidanceConfig()
 
     # ---- what PipelineWrapper / DiffusionPipelineWrapper touch -----------------------------------------------------------
@@ -197,7 +206,8 @@ class GyreUnifiedPipeline:
                 raise ValueError(f"Unknown option {key}: {value} passed to UnifiedPipeline")
 
     # ---- text -------------------------------------------------------------------------------------------------------------
-    def _embed(self, prompt, negative_prompt, B, num_images_per_prompt, do_cfg, max_embeddings_multiples):
+    def _embed(self, prompt, negative_prompt, B, num_images_per_prompt, do_cfg, max_embeddings_multiples, tokenizer=None):
+        """tokenizer: the request's own copy when it carries token embeddings (default: self.tokenizer)."""
         def frags(p):                                       # str | Prompt | list | PromptBatch -> list of [(text, weight)] / str
             if p is None:
                 return None
@@ -223,9 +233,10 @@ class GyreUnifiedPipeline:
             tower = getattr(te, "text_model", te)
             return tower.final_layer_norm(out.hidden_states[-2]).float()
         encode.device = dev
-        tok = self.tokenizer
+        tok = self.tokenizer if tokenizer is None else tokenizer
 
         def tokenize(text):
+            text = TA.replace_text(tok, text)               # a multi-vector embedding's <name> -> its sub-tokens, before tokenising
             return tok(text, add_special_tokens=False)["input_ids"] if callable(tok) else tok.encode(text)[1:-1]
         emb = LPWTextEmbedder(encode, tokenize, max_embeddings_multiples)
         cond, unc = emb.get_embeddings(pos, neg if do_cfg else None)
@@ -273,7 +284,6 @@ class GyreUnifiedPipeline:
             scale = None
         if not scale:
             return {}
-        import copy
         cfg = copy.copy(self.clip_default_config)
         cfg.guidance_scale = scale
         if base is not None:
@@ -342,6 +352,52 @@ class GyreUnifiedPipeline:
         del cache[:-4]
         return f
 
+    def _text_factors(self, text_encoder, tensors):
+        """The text-encoder side of one LoRA / LyCORIS tensors mapping (text_adapters.upload_text_factors), remembered like
+        _lora_factors: per mapping OBJECT and encoder object, the four most recently used."""
+        dev = TA._device_of(text_encoder)
+        cache = self._text_uploads
+        for i, (src, te, f) in enumerate(cache):
+            if src is tensors and te is text_encoder and f.device == dev:
+                cache.append(cache.pop(i))
+                return f
+        f = TA.upload_text_factors(text_encoder, tensors, dev)
+        cache.append((tensors, text_encoder, f))
+        del cache[:-4]
+        return f
+
+    def _text_encoders(self) -> list:
+        """Every distinct text encoder a request may use (the reference's all_text_encoders, unified_pipeline.py:2187-2188)."""
+        out = []
+        for te in (self.text_encoder, getattr(self, "inpaint_text_encoder", None)):
+            if te is not None and not any(te is o for o in out):
+                out.append(te)
+        return out
+
+    def _text_side(self, lora_specs, token_embeddings):
+        """The text side of a request (unified_pipeline.py:1855-1868, 2190-2233), in front of the prompt encoding: what the previous
+        request left on every text encoder goes (attached lora_te_ terms, added token rows), then this request's token embeddings
+        and the lora_te_ entries of its ``lora_specs = [(tensors, weights)]`` go on.  Returns the tokenizer to encode the prompts
+        with: self.tokenizer, or the request's own copy with the embeddings' tokens added."""
+        encoders = self._text_encoders()
+        tokenizer = self.tokenizer
+        if token_embeddings:
+            for te in encoders:
+                TA.check_ti(te, token_embeddings)           # a wrong dimension raises before anything changed
+        for te in encoders:
+            TA.detach(te)
+            TA.match_encoder_to_tokenizer(self.tokenizer, te)
+        if token_embeddings:
+            tokenizer = copy.deepcopy(self.tokenizer)       # tokens added for this call only; clip_tokenizer stays as it is
+            flattened = TA.apply_ti_to_tokenizer(tokenizer, token_embeddings)
+            for te in encoders:
+                TA.apply_ti_to_encoder(tokenizer, te, flattened)
+        text_specs = [(t, w) for t, w in lora_specs if TA.has_text_keys(t)]
+        if text_specs:
+            for te in encoders:
+                TA.attach(te, [(self._text_factors(te, t), TA.text_scale(w)) for t, w in text_specs])
+        return tokenizer
+
     def _hints(self, hint_images, mask_image) -> list:
         """The reference's hint loop (unified_pipeline.py:1994-2047) for what is native: every hint image needs exactly one model
         from the hintset manager and that model must be a GyreHipT2IAdapter (-> hints.T2IHint) or a GyreHipControlNet
@@ -402,8 +458,6 @@ class GyreUnifiedPipeline:
         controlnet_hints = [h for h in all_hints if isinstance(h, ControlNetHint)]
         if all_hints and len(self._shard_devices) > 1:
             raise NotImplementedError("hint images together with shard_devices (the adapter states and the bound control models live on one device slot)")
-        if token_embeddings:
-            raise NotImplementedError("textual-inversion token embeddings are outside the native hot path")
         if tiling not in (False, None, True, "x", "y", "xy"):
             raise ValueError(f"tiling must be True, False, 'x', 'y' or 'xy', got {tiling!r}")
         if tiling and clip_guidance_scale:
@@ -433,11 +487,22 @@ class GyreUnifiedPipeline:
         do_cfg = guidance_scale > 1.0
         sdxl = getattr(getattr(self.unet, "config", None), "addition_embed_type", None) == "text_time"
         added = uadded = None
+        lora_specs = []
+        for spec in (lora if isinstance(lora, (list, tuple)) else [lora]) if lora else ():
+            tensors, weights = (spec if isinstance(spec, (list, tuple)) else (spec, {}))
+            lora_specs.append((tensors, weights))
+        if sdxl:
+            # SDXL files name two towers (lora_te1_ / lora_te2_), a key space the reference does not have: their text side stays
+            # ignored, and token embeddings (one vector per tower) stay refused
+            if token_embeddings:
+                raise NotImplementedError("textual-inversion token embeddings on an SDXL engine (two text towers)")
+        else:
+            tokenizer = self._text_side(lora_specs, token_embeddings)
         if sdxl:
             cond, unc, added, uadded = self._embed_sdxl(prompt, negative_prompt, B, num_images_per_prompt, do_cfg,
                                                         max_embeddings_multiples, height, width)
         else:
-            cond, unc = self._embed(prompt, negative_prompt, B, num_images_per_prompt, do_cfg, max_embeddings_multiples)
+            cond, unc = self._embed(prompt, negative_prompt, B, num_images_per_prompt, do_cfg, max_embeddings_multiples, tokenizer)
         if strength is None:
             strength = 0.8
         dev = self.execution_device
@@ -461,10 +526,9 @@ class GyreUnifiedPipeline:
             LR.detach_loras(u)                              # ... and what the previous request attached on the device path
             if hasattr(u, "set_tome"):                      # the reference patches ToMe into self.unet only (:1580-1584)
                 u.set_tome(self._tome if u is self.unet else 0)
-        if lora:
+        if lora_specs:                                      # (a file with lora_te_ entries only touches no UNet weight: an empty attach)
             specs = []
-            for i, spec in enumerate(lora if isinstance(lora, (list, tuple)) else [lora]):
-                tensors, weights = (spec if isinstance(spec, (list, tuple)) else (spec, {}))
+            for i, (tensors, weights) in enumerate(lora_specs):
                 scale = (weights or {}).get("unet", 1.0) if isinstance(weights, dict) else 1.0
                 specs.append((tensors, f"request-{i}", scale))
             if hasattr(self.unet, "_sync"):                 # native UNet: merged on the device, each touched weight repacked once

@@ -12,7 +12,7 @@ with s = scale * alpha / r (alpha absent -> 1).  Key formats as detected by refe
   kohya-ss   ``lora_unet_<module path with _>.lora_down.weight / .lora_up.weight / .alpha``   (lora.py:271-330)
   diffusers  ``<path>.processor.<to_q|to_k|to_v|to_out>_lora.down.weight / .up.weight``        (lora.py:232-268)
   cloneofsimo needs the un-vendored lora_diffusion submodule's module-search order -> NotImplementedError.
-Text-encoder entries (``lora_te_``) are ignored here (CLIP stays host PyTorch and keeps the reference's own path).
+Text-encoder entries (``lora_te_``) are ignored here: they are gyre_amd/text_adapters.py's.
 
 The touched base weights are kept (CPU copies) so that removing / re-scaling restores them bit-exactly.
 

@@ -20,8 +20,8 @@ File scale: the ``scale`` key when present and non-zero, else ``alpha / dim`` wh
 wXb.shape[0] (LoHa, LoKr), none for Full (its alpha is ignored); a LoKr's alpha reads as absent when neither w1_a nor w2_a exists.
 With two decomposed sides of different rank the reference's dim depends on the iteration order of a Python set: ValueError here.
 IA3 (``weight`` / ``on_input``: the reference's own handler cannot run either, it stores ``.weight`` and reads ``.w``), DyLoRA
-(``dyn_up`` / ``dyn_down``) and sparse bias (``bias_*``) are NotImplementedError at parse time.  ``lora_te_`` entries are ignored (CLIP
-stays host PyTorch); another prefix is a ValueError, a ``lora_unet_`` key without a module a RuntimeError, as in the reference.
+(``dyn_up`` / ``dyn_down``) and sparse bias (``bias_*``) are NotImplementedError at parse time.  ``lora_te_`` entries are ignored here (they are
+gyre_amd/text_adapters.py's); another prefix is a ValueError, a ``lora_unet_`` key without a module a RuntimeError, as in the reference.
 
 Deliberate deviation (the one lora.py makes): the reference adds each delta in the weight's own dtype; here base + sum of deltas
 is summed in fp32 and rounded to the storage type once.
@@ -293,19 +293,14 @@ def _core(L, core: Tensor, right: Tensor) -> Tensor:
     return out
 
 
-def upload_factors(unet, tensors, device=None) -> LycoFactors:
-    """Parse ``tensors`` (the key rules of apply_lycoris) and put its terms on ``device`` (default: the module's), each factor in its own
-    dtype.  Tucker cores and a low-rank W1 are contracted once here (gyre_op_lyco_core, fp32); nothing else is multiplied out.
-    Shapes are checked against the weights they target (ValueError)."""
+def make_term(L, fields: Mapping[str, Tensor], w: Tensor, name: str, device) -> Term:
+    """The Term of one module's file tensors for the weight ``w`` (its shape only), operands on ``device`` in their own dtype.
+    Tucker cores and a low-rank W1 are contracted here (gyre_op_lyco_core of the library ``L``, fp32); nothing else is multiplied
+    out.  ValueError where the tensors do not give the weight's shape.  Shared by upload_factors and text_adapters."""
     from . import _lib
-    device = torch.device(device) if device is not None else unet.device
-    if device.type != "cuda":
-        raise _lib.GyreError("LyCORIS factors are prepared on the GPU (gyre_op_lyco_core): the native path has no CPU fallback")
-    L = unet._L() if hasattr(unet, "_L") else _lib.lib()
-    params = dict(unet.named_parameters())
     fix = lambda t: (t if t.dtype in LR._FACTOR_DTYPES else t.to(torch.float32)).detach().to(device).contiguous()
 
-    def product(wa, wb, t, name):
+    def product(wa, wb, t):
         """(up [O', r], down [r, ...]) of one low-rank product; with a core: up = wa^T in fp32, down = core(t, wb)."""
         if t is None:
             wa, wb = fix(wa), fix(wb)
@@ -318,41 +313,51 @@ def upload_factors(unet, tensors, device=None) -> LycoFactors:
             raise ValueError(f"LyCORIS for {name}: t {tuple(t.shape)}, wa {tuple(wa.shape)}, wb {tuple(wb.shape)} do not fit")
         return wa.float().t().contiguous(), _core(L, t, wb)
 
-    terms = {}
-    for name, fields in _modules(unet, tensors):
-        w = params[name]
-        kind, scale = _kind(fields), file_scale(fields)
-        if kind == "locon":
-            up, down, mid = fields["lora_up.weight"], fields["lora_down.weight"], fields.get("lora_mid.weight")
-            if mid is None:
-                term = Term(_lib.DELTA_LORA, [product(up, down, None, name)], scale)
-            else:
-                mid, up, down = fix(mid), fix(up), fix(down)
-                up, down = up.reshape(up.shape[0], -1), down.reshape(down.shape[0], -1)
-                if mid.ndim != 4 or up.shape[1] != mid.shape[0] or down.shape[0] != mid.shape[1]:
-                    raise ValueError(f"LoCon for {name}: up {tuple(up.shape)}, mid {tuple(mid.shape)}, down {tuple(down.shape)} do not fit")
-                term = Term(_lib.DELTA_LORA, [(up.float().contiguous(), _core(L, mid, down.contiguous()))], scale)
-        elif kind == "loha":
-            term = Term(_lib.DELTA_HADA, [product(fields["hada_w1_a"], fields["hada_w1_b"], fields.get("hada_t1"), name),
-                                          product(fields["hada_w2_a"], fields["hada_w2_b"], fields.get("hada_t2"), name)], scale)
-        elif kind == "lokr":
-            if "lokr_w1" in fields:
-                w1 = fix(fields["lokr_w1"]).float().contiguous()
-            else:
-                a, b = fix(fields["lokr_w1_a"]), fix(fields["lokr_w1_b"])
-                if a.ndim != 2 or b.ndim != 2:
-                    raise ValueError(f"LoKr for {name}: w1_a / w1_b must be matrices")
-                w1 = _core(L, a, b).reshape(a.shape[0], b.shape[1])
-            if "lokr_w2" in fields:
-                op = (None, fix(fields["lokr_w2"]))
-            else:
-                op = product(fields["lokr_w2_a"], fields["lokr_w2_b"], fields.get("lokr_t2"), name)
-            term = Term(_lib.DELTA_KRON, [op], scale, w1)
+    kind, scale = _kind(fields), file_scale(fields)
+    if kind == "locon":
+        up, down, mid = fields["lora_up.weight"], fields["lora_down.weight"], fields.get("lora_mid.weight")
+        if mid is None:
+            term = Term(_lib.DELTA_LORA, [product(up, down, None)], scale)
         else:
-            term = Term(_lib.DELTA_FULL, [(None, fix(fields["diff"]))], scale)
-        if w.ndim not in (2, 4) or not term.fits(w):
-            raise ValueError(f"LyCORIS {kind} module for {name}: its tensors do not give the weight's shape {tuple(w.shape)}")
-        terms[name] = term
+            mid, up, down = fix(mid), fix(up), fix(down)
+            up, down = up.reshape(up.shape[0], -1), down.reshape(down.shape[0], -1)
+            if mid.ndim != 4 or up.shape[1] != mid.shape[0] or down.shape[0] != mid.shape[1]:
+                raise ValueError(f"LoCon for {name}: up {tuple(up.shape)}, mid {tuple(mid.shape)}, down {tuple(down.shape)} do not fit")
+            term = Term(_lib.DELTA_LORA, [(up.float().contiguous(), _core(L, mid, down.contiguous()))], scale)
+    elif kind == "loha":
+        term = Term(_lib.DELTA_HADA, [product(fields["hada_w1_a"], fields["hada_w1_b"], fields.get("hada_t1")),
+                                      product(fields["hada_w2_a"], fields["hada_w2_b"], fields.get("hada_t2"))], scale)
+    elif kind == "lokr":
+        if "lokr_w1" in fields:
+            w1 = fix(fields["lokr_w1"]).float().contiguous()
+        else:
+            a, b = fix(fields["lokr_w1_a"]), fix(fields["lokr_w1_b"])
+            if a.ndim != 2 or b.ndim != 2:
+                raise ValueError(f"LoKr for {name}: w1_a / w1_b must be matrices")
+            w1 = _core(L, a, b).reshape(a.shape[0], b.shape[1])
+        if "lokr_w2" in fields:
+            op = (None, fix(fields["lokr_w2"]))
+        else:
+            op = product(fields["lokr_w2_a"], fields["lokr_w2_b"], fields.get("lokr_t2"))
+        term = Term(_lib.DELTA_KRON, [op], scale, w1)
+    else:
+        term = Term(_lib.DELTA_FULL, [(None, fix(fields["diff"]))], scale)
+    if w.ndim not in (2, 4) or not term.fits(w):
+        raise ValueError(f"LyCORIS {kind} module for {name}: its tensors do not give the weight's shape {tuple(w.shape)}")
+    return term
+
+
+def upload_factors(unet, tensors, device=None) -> LycoFactors:
+    """Parse ``tensors`` (the key rules of apply_lycoris) and put its terms on ``device`` (default: the module's), each factor in its own
+    dtype.  Tucker cores and a low-rank W1 are contracted once here (gyre_op_lyco_core, fp32); nothing else is multiplied out.
+    Shapes are checked against the weights they target (ValueError)."""
+    from . import _lib
+    device = torch.device(device) if device is not None else unet.device
+    if device.type != "cuda":
+        raise _lib.GyreError("LyCORIS factors are prepared on the GPU (gyre_op_lyco_core): the native path has no CPU fallback")
+    L = unet._L() if hasattr(unet, "_L") else _lib.lib()
+    params = dict(unet.named_parameters())
+    terms = {name: make_term(L, fields, params[name], name, device) for name, fields in _modules(unet, tensors)}
     return LycoFactors(terms, device, tensors)
 
 

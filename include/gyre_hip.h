@@ -612,6 +612,15 @@ int gyre_op_repack_delta(void* stream, const void* base, int base_dtype, int O, 
                          int geglu_interleave, float scale_p, int n_terms, const gyre_delta_term* terms, void* out);
 int gyre_op_lyco_core(void* stream, const void* core, int core_dtype, const void* right, int right_dtype, int A, int B, int C, int T,
                       float* out);
+/* The same sum on a plain matrix, for a weight that lives outside the native store (a CLIP text encoder's nn.Linear):
+ *   out[o][i] = round_out( base[o][i] + sum_j scale_j * D_j[o][i] ),  summed in fp32 in term order, one rounding to out_dtype
+ * base [O][I] row-major of base_dtype, out [O][I] row-major of out_dtype - GYRE_F32 (stored as computed), GYRE_BF16 or GYRE_F16
+ * (round to nearest even), whichever storage type the library was built for.  Terms and their checks as gyre_op_repack_delta with
+ * KH = KW = 1; no interleave, no pad columns, no folded factor.  n_terms == 0 with out_dtype == base_dtype copies base bit for bit
+ * (how an adapter is taken off).  I % 4 == 0, out aligned to 4 elements, and out must not overlap base or an operand (the caller
+ * keeps the original): GYRE_ERR_INVALID otherwise.  Every check precedes the launch and a refused call writes nothing. */
+int gyre_op_merge_delta(void* stream, const void* base, int base_dtype, int O, int I, int n_terms, const gyre_delta_term* terms,
+                        void* out, int out_dtype);
 /* o[B,Nq,H*D] = softmax(q k^T * D^-1/2) v ; q[B,Nq,H*D] (ldq), k[B,Nk,H*D] (ldk), vt[B,H*D,ldvt] (V transposed) */
 int gyre_op_attention(void* stream, const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt,
                       int B, int heads, int Nq, int Nk, int D, void* o, int ldo);
