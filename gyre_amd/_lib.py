@@ -78,6 +78,24 @@ class CtrlCfg(C.Structure):
                 ("cond_channels", C.c_int32), ("cond_embed_channels", C.c_int32 * 4)]
 
 
+class RRDBCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_in_ch", "num_out_ch", "num_feat", "num_block", "num_grow_ch", "scale", "plus")]
+
+
+class RdbEpilogue(C.Structure):
+    """gyre_rdb_epilogue (include/gyre_hip.h): v = alpha (acc + bias); leaky-relu(0.2) if act; + beta1 r1; + beta2 r2."""
+    _fields_ = [("bias", C.c_void_p), ("alpha", C.c_float), ("act", C.c_int32), ("r1", C.c_void_p), ("ldr1", C.c_int32),
+                ("beta1", C.c_float), ("r2", C.c_void_p), ("ldr2", C.c_int32), ("beta2", C.c_float)]
+
+
+class RdbConvArgs(C.Structure):
+    """gyre_rdb_conv_args (include/gyre_hip.h): one launch of the dense-block convolution, for tests and tuning."""
+    _fields_ = [("x", C.c_void_p)] + [(n, C.c_int32) for n in ("ldx", "Cin", "B", "H", "W", "ups")] + [("w", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("w_rows", "NT", "N_live")] + [("out", C.c_void_p), ("c0", C.c_int32), ("ldo", C.c_int32),
+                                                                        ("epi", C.POINTER(RdbEpilogue)), ("wpack", C.c_void_p),
+                                                                        ("wpack_bytes", C.c_size_t)]
+
+
 class GemmTestArgs(C.Structure):
     """gyre_gemm_test_args (include/gyre_hip.h): one GEMM / conv launch field by field, for tests and tuning."""
     _fields_ = [(n, C.c_int32) for n in ("conv", "M", "K", "N", "geglu", "B", "Hi", "Wi", "Cin", "stride", "pad", "ups", "Hup", "Wup",
@@ -154,6 +172,15 @@ _SIGS = {
     "gyre_t2i_finalize": (_i, [_vp, _vp]),
     "gyre_t2i_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "gyre_t2i_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(_vp), _i, _i]),
+    "gyre_rrdb_create": (_i, [C.POINTER(RRDBCfg), _i, C.POINTER(_vp)]),
+    "gyre_rrdb_destroy": (None, [_vp]),
+    "gyre_rrdb_num_params": (_i, [_vp]),
+    "gyre_rrdb_param_key": (C.c_char_p, [_vp, _i]),
+    "gyre_rrdb_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
+    "gyre_rrdb_finalize": (_i, [_vp, _vp]),
+    "gyre_rrdb_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "gyre_rrdb_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
+    "gyre_rrdb_set_path": (_i, [_vp, _i]),
     "gyre_ctrl_create": (_i, [C.POINTER(CtrlCfg), _i, C.POINTER(_vp)]),
     "gyre_ctrl_destroy": (None, [_vp]),
     "gyre_ctrl_num_params": (_i, [_vp]),
@@ -236,6 +263,10 @@ _SIGS = {
     "gyre_op_avgpool2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "gyre_op_relu": (_i, [_vp, _vp, _sz]),
     "gyre_op_silu": (_i, [_vp, _vp, _sz]),
+    "gyre_op_rdb_tile": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gyre_op_rdb_conv": (_i, [_vp, C.POINTER(RdbConvArgs)]),
+    "gyre_op_rdb_epilogue": (_i, [_vp, _vp, _i, _i, _i, _sz, C.POINTER(RdbEpilogue)]),
+    "gyre_op_pixel_unshuffle": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "gyre_op_ctrl_emit": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _i]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -180,3 +180,36 @@ def t2i_config(type: str = "main", **kw) -> T2IConfig:
 def tiny_t2i(kind: str = "main", **kw) -> T2IConfig:
     """The reference's default adapter of the given kind at the widths of tiny_unet."""
     return t2i_config(kind, **{"channels": (32, 64, 128, 128), **kw})
+
+
+class RRDBConfig(dict):
+    """Configuration of an RRDBNet upscaler (BasicSR ``RRDBNet(num_in_ch, num_out_ch, scale, num_feat, num_block, num_grow_ch)``
+    plus ``plus`` for the reference's ESRGAN+ blocks): a mapping that also reads as attributes."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+# the reference's default configurations (gyre/pipeline/upscalers/upscaler_loader.py:22-40)
+RRDB_DEFAULTS = {"esrgan": dict(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=23, num_grow_ch=32, scale=4),
+                 "esrgan-6B": dict(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=6, num_grow_ch=32, scale=4)}
+RRDB_DEFAULTS["esrgan-plus"] = RRDB_DEFAULTS["esrgan"]
+
+
+def rrdb_config(plus: bool = False, **kw) -> RRDBConfig:
+    """BasicSR's own constructor defaults (scale=4, num_feat=64, num_block=23, num_grow_ch=32) under ``kw``.  Only num_feat = 64
+    and num_grow_ch = 32 are built natively - the widths of every configuration the reference ships."""
+    cfg = RRDBConfig(**{**dict(num_in_ch=3, num_out_ch=3, scale=4, num_feat=64, num_block=23, num_grow_ch=32), **kw}, plus=bool(plus))
+    if cfg["num_feat"] != 64 or cfg["num_grow_ch"] != 32:
+        raise NotImplementedError("RRDBNet: num_feat = 64 and num_grow_ch = 32 are the only widths on the native path")
+    if cfg["scale"] not in (1, 2, 4):
+        raise NotImplementedError(f"RRDBNet: scale must be 1, 2 or 4, got {cfg['scale']}")
+    return cfg
+
+
+def tiny_rrdb(**kw) -> RRDBConfig:
+    """Two RRDBs (six dense blocks, the third-block epilogue included) at the only widths the family has."""
+    return rrdb_config(**{"num_block": 2, **kw})

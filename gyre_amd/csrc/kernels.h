@@ -147,6 +147,37 @@ int launch_relu(hipStream_t st, bf16_t* x, size_t n);                      // in
 // y NCHW [B][C][HW] of a runtime dtype = the first C channels of x NHWC [B][HW][Cpad]
 int launch_nhwc_to_nchw(hipStream_t st, const bf16_t* x, int B, int C, int HW, int Cpad, void* y, int dtype);
 
+// ---- RRDBNet (ESRGAN) upscaler kernels (kernels_rdb.hip) ------------------------
+// The epilogue every convolution of the net shares, fp32, in this order, one rounding to storage:
+//   v = alpha * (acc + bias[n]);  if act: v = v > 0 ? v : 0.2 v;  v += beta1 * r1[pix][n];  v += beta2 * r2[pix][n]
+// bias [N_live] or null; r1 / r2: NHWC slices (first element of the slice, own pixel stride) or null.  r1 may alias the output slice
+// element for element.
+struct RdbEpilogueArgs {
+    const float* bias = nullptr; float alpha = 1.f; int act = 0;
+    const bf16_t* r1 = nullptr; int ldr1 = 0; float beta1 = 0.f;
+    const bf16_t* r2 = nullptr; int ldr2 = 0; float beta2 = 0.f;
+};
+void rdb_tile(int* th, int* tw);                        // output tile of k_rdb_conv (pixels)
+size_t rdb_wpack_bytes(int NT, int Cin);                // bytes of the chunk-ordered weight copy
+// wd [Cin / 32][9][NT][32] <- W [rows][9][Cin] (the library's conv layout), zero rows above `rows` (<= NT)
+int launch_rdb_wpack(hipStream_t st, const bf16_t* W, int rows, int Cin, int NT, bf16_t* wd);
+// 3x3 / stride 1 / zero padding 1 convolution over the first Cin channels (Cin % 32 == 0) of x NHWC [B][H][W] with pixel stride ldx,
+// ups: nearest 2x of x inside the gather (output 2H x 2W); NT = 32 or 64 weight rows in wd, of which the first N_live are written to
+// out[pix][0 .. N_live) (out: first element of the slice, pixel stride ldo) - every other byte of the buffer keeps its bits.
+// GYRE_ERR_UNSUPPORTED outside the domain (NT, Cin % 32, strides % 8, 16-byte alignment, grid limits), nothing written.
+int launch_rdb_conv(hipStream_t st, const bf16_t* x, int ldx, int Cin, int B, int H, int W, int ups, const bf16_t* wd, int NT,
+                    int N_live, bf16_t* out, int ldo, const RdbEpilogueArgs& e);
+// launch_rdb_conv's argument checks alone (no device call): 0, or the status and message the launch would refuse with
+int rdb_conv_check(const bf16_t* x, int ldx, int Cin, int B, int H, int W, int ups, const bf16_t* wd, int NT, int N_live,
+                   const bf16_t* out, int ldo, const RdbEpilogueArgs& e);
+// the same epilogue in place over a stored slice x[pix][0 .. N_live), npix pixels of stride ldo (acc = the stored value)
+int launch_rdb_epilogue(hipStream_t st, bf16_t* x, int ldo, int N_live, size_t npix, const RdbEpilogueArgs& e);
+// x NCHW [B][c][H][W] of a runtime dtype -> y NHWC storage [B][H / r][W / r][rdb_unshuffle_channels(c, r)] in
+// torch.nn.functional.pixel_unshuffle(r) channel order, r = 1, 2 or 4, zero channels up to the next multiple of 32
+int launch_rdb_copy(hipStream_t st, const bf16_t* src, int lds, bf16_t* dst, int ldd, int C, size_t npix);   // dst[pix][0:C) = src[pix][0:C)
+int rdb_unshuffle_channels(int c, int r);
+int launch_pixel_unshuffle(hipStream_t st, const void* x, int dtype, int B, int c, int H, int W, int r, bf16_t* y);
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

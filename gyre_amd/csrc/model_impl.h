@@ -1,5 +1,5 @@
-// Model runtime internals shared by model.hip (forward graphs + C ABI), model_vjp.hip (input-gradient graphs), model_ctrl.hip and
-// model_t2i.hip: workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
+// Model runtime internals shared by model.hip (forward graphs + C ABI), model_vjp.hip (input-gradient graphs), model_ctrl.hip,
+// model_t2i.hip and model_rrdb.hip: workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
 #pragma once
 #include "../../include/gyre_hip.h"
 #include "kernels.h"
@@ -116,7 +116,8 @@ struct Store {
         DC_PACKED,       // fragment order of the A-resident GEMM kernel (GemmParams::w_packed); tag = tile config 30 / 31
         DC_BLOCKED,      // blocked order of the LDS-DMA tile kernels (GemmParams::W_blk), every routed weight with K > 1024
         DC_SHORTCUT,     // conv2 rows | 1x1 shortcut rows, and the sum of the two biases (GemmParams::sc_*)
-        DC_PROJ_OUT      // proj_out composed with the last FF2: Wc [C][5C] = [Wp W2 | Wp], bc = Wp b2 + bp (Exec::proj_out_folded)
+        DC_PROJ_OUT,     // proj_out composed with the last FF2: Wc [C][5C] = [Wp W2 | Wp], bc = Wp b2 + bp (Exec::proj_out_folded)
+        DC_RDB_CHUNKED   // K-chunk order of the dense-block convolution kernel (launch_rdb_wpack, model_rrdb.hip); tag = NT
     };
     struct DKey {
         int kind; const void* src;

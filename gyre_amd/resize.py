@@ -94,6 +94,13 @@ def cubic(x: torch.Tensor) -> torch.Tensor:
     return (1.5 * ax3 - 2.5 * ax2 + 1) * (ax <= 1) + (-0.5 * ax3 + 2.5 * ax2 - 4 * ax + 2) * ((1 < ax) & (ax <= 2))
 
 
+def lanczos3(x: torch.Tensor) -> torch.Tensor:
+    """sinc(x) sinc(x/3) on |x| < 3 (support 6), with the eps guard of lanczos2 - ResizeRight's ``interp_methods.lanczos3``, the
+    kernel of the reference's ``images.resize`` (gyre/images.py:324-340)."""
+    pix = math.pi * x
+    return ((torch.sin(pix) * torch.sin(pix / 3) + _EPS) / ((pix * pix / 3) + _EPS)) * (x.abs() < 3)
+
+
 _GENERAL_CACHE: dict = {}
 
 
@@ -109,7 +116,7 @@ def _weight_matrix_general(in_size: int, out_size: int, scale: float, method: st
     hit = _GENERAL_CACHE.get(key)
     if hit is not None:
         return hit
-    kernel, support = {"cubic": (cubic, 4.0), "lanczos2": (lanczos2, 4.0)}[method]
+    kernel, support = {"cubic": (cubic, 4.0), "lanczos2": (lanczos2, 4.0), "lanczos3": (lanczos3, 6.0)}[method]
     if scale < 1 and antialiasing:
         base, k_support = kernel, support / scale
         kern = lambda a: scale * base(scale * a)
@@ -160,7 +167,7 @@ def resize_right(x: torch.Tensor, out_shape=None, scale_factors=None, interp_met
         oh, ow = int(out_shape[-2]), int(out_shape[-1])
         sh, sw = oh / h, ow / w
     elif scale_factors is not None:
-        sh = sw = float(scale_factors)
+        sh, sw = (float(scale_factors[0]), float(scale_factors[-1])) if isinstance(scale_factors, (tuple, list)) else (float(scale_factors),) * 2
         oh, ow = int(math.ceil(h * sh)), int(math.ceil(w * sw))
     else:
         raise ValueError("pass out_shape or scale_factors")
@@ -178,3 +185,27 @@ def resize_right(x: torch.Tensor, out_shape=None, scale_factors=None, interp_met
 def resize_nearest(x: torch.Tensor, scale: float) -> torch.Tensor:
     hs, ws = int(x.shape[-2] * scale), int(x.shape[-1] * scale)
     return torch.nn.functional.interpolate(x, size=(hs, ws), mode="nearest")
+
+
+def gaussian_blur(x: torch.Tensor, sigma) -> torch.Tensor:
+    """The reference's ``images.gaussianblur`` (gyre/images.py:290-295): torchvision's ``gaussian_blur`` - not a dependency here, so
+    restated, *parity unpinned* - with a kernel size of ceil(6 sigma) made odd per axis: the 1-D kernel exp(-t^2 / (2 sigma^2)) on
+    t = linspace(-(k - 1) / 2, (k - 1) / 2, k) normalised to sum 1, reflect padding, one depthwise convolution with the outer
+    product of the two 1-D kernels.  x: float [B, C, H, W]."""
+    sig = (float(sigma), float(sigma)) if not isinstance(sigma, (tuple, list)) else (float(sigma[0]), float(sigma[1]))
+    ks = [int(math.ceil(s_ * 6)) for s_ in sig]
+    ks = [k - k % 2 + 1 for k in ks]                                  # [kx, ky], as torchvision orders it
+
+    def k1d(k, s_):
+        half = (k - 1) * 0.5
+        t = torch.linspace(-half, half, steps=k, dtype=x.dtype if x.is_floating_point() else torch.float32, device=x.device)
+        pdf = torch.exp(-0.5 * (t / s_).pow(2))
+        return pdf / pdf.sum()
+
+    kx, ky = k1d(ks[0], sig[0]), k1d(ks[1], sig[1])
+    k2d = torch.mm(ky[:, None], kx[None, :])
+    C_ = x.shape[-3]
+    kern = k2d.expand(C_, 1, k2d.shape[0], k2d.shape[1])
+    pad = [ks[0] // 2, ks[0] // 2, ks[1] // 2, ks[1] // 2]
+    xp = torch.nn.functional.pad(x, pad, mode="reflect")
+    return torch.nn.functional.conv2d(xp, kern, groups=C_)

@@ -281,3 +281,28 @@ def t2i_param_shapes(cfg) -> Shapes:
                 conv(p + ".down_opt.op", in_c, in_c, 3)
     conv("conv_in", ch[0], cin, 3)
     return s
+
+
+def rrdb_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of BasicSR's ``RRDBNet`` (and of the reference's ``RRDBNet_Plus`` when cfg["plus"]: one bias-free
+    ``conv1x1`` per dense block); cfg: a mapping as gyre_amd.config.tiny_rrdb returns."""
+    s: Shapes = OrderedDict()
+    nf, gc, scale = cfg["num_feat"], cfg["num_grow_ch"], cfg["scale"]
+    cin = cfg["num_in_ch"] * (4 if scale == 2 else 16 if scale == 1 else 1)
+
+    def conv(p, o, i):
+        s[p + ".weight"] = (o, i, 3, 3)
+        s[p + ".bias"] = (o,)
+
+    conv("conv_first", nf, cin)
+    for i in range(cfg["num_block"]):
+        for j in (1, 2, 3):
+            p = f"body.{i}.rdb{j}"
+            for k in range(5):
+                conv(f"{p}.conv{k + 1}", nf if k == 4 else gc, nf + k * gc)
+            if cfg.get("plus", False):
+                s[p + ".conv1x1.weight"] = (gc, nf, 1, 1)
+    for name in ("conv_body", "conv_up1", "conv_up2", "conv_hr"):
+        conv(name, nf, nf)
+    conv("conv_last", cfg["num_out_ch"], nf)
+    return s

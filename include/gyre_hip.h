@@ -121,10 +121,44 @@ typedef struct {
     int32_t cond_embed_channels[4];  /* 16,32,96,256 (multiples of 8) */
 } gyre_ctrl_cfg;
 
+/* RRDBNet upscaler (BasicSR basicsr/archs/rrdbnet_arch.py RRDBNet; plus = 1: the reference's ResidualDenseBlock_Plus,
+ * gyre/pipeline/upscalers/models/esrgan_plus.py) */
+typedef struct {
+    int32_t num_in_ch;               /* 3 */
+    int32_t num_out_ch;              /* 3 */
+    int32_t num_feat;                /* 64 (the only width built) */
+    int32_t num_block;               /* 23 (esrgan, realesrgan-x4plus), 6 (realesrgan-x4plus-anime) */
+    int32_t num_grow_ch;             /* 32 (the only width built) */
+    int32_t scale;                   /* 4, 2 (pixel-unshuffle by 2 in front) or 1 (by 4) */
+    int32_t plus;                    /* 1 = every dense block carries conv1x1 (ESRGAN+) */
+} gyre_rrdb_cfg;
+
+/* Epilogue of the dense-block convolution kernels, fp32, in this order, one rounding to storage:
+ *   v = alpha * (acc + bias[n]);  if act: v = v > 0 ? v : 0.2f * v;  v += beta1 * r1[pix][n];  v += beta2 * r2[pix][n]
+ * bias: [N_live] floats or NULL.  r1 / r2: first element of an NHWC storage slice with its own pixel stride (elements), or NULL; r1
+ * may alias the output slice element for element. */
+typedef struct {
+    const float* bias; float alpha; int32_t act;
+    const void* r1; int32_t ldr1; float beta1;
+    const void* r2; int32_t ldr2; float beta2;
+} gyre_rdb_epilogue;
+/* One launch of the dense-block convolution: 3x3, stride 1, zero padding 1 over the first Cin channels of x (NHWC storage
+ * [B][H][W], pixel stride ldx; ups = 1: nearest 2x inside the gather, output 2H x 2W), weights w [w_rows][9][Cin] in the library's
+ * conv layout (w_rows <= NT; rows up to NT count as zero), the first N_live output channels written to out[pix][c0 .. c0 + N_live)
+ * of a buffer with pixel stride ldo.  wpack: wpack_bytes >= NT * 9 * Cin * 2 bytes of scratch for the kernel's weight order. */
+typedef struct {
+    const void* x; int32_t ldx, Cin, B, H, W, ups;
+    const void* w; int32_t w_rows, NT, N_live;
+    void* out; int32_t c0, ldo;
+    const gyre_rdb_epilogue* epi;
+    void* wpack; size_t wpack_bytes;
+} gyre_rdb_conv_args;
+
 typedef struct gyre_unet gyre_unet;
 typedef struct gyre_vae gyre_vae;
 typedef struct gyre_t2i gyre_t2i;
 typedef struct gyre_ctrl gyre_ctrl;
+typedef struct gyre_rrdb gyre_rrdb;
 
 /* ---- library ---------------------------------------------------------- */
 int gyre_abi_version(void);
@@ -336,6 +370,27 @@ size_t gyre_t2i_workspace_bytes(gyre_t2i* h, int B, int H, int W);
  * of 8; n = n_levels).  The stride-2 conv downsampling (use_conv) rounds an odd size up, the average pool down, as torch does. */
 int gyre_t2i_forward(gyre_t2i* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                      void* workspace, size_t workspace_bytes, void* const* features_out_nchw, int n, int out_dtype);
+
+/* ---- RRDBNet upscaler ------------------------------------------------------- */
+/* Weight keys are BasicSR's state-dict names: conv_first, body.{i}.rdb{1,2,3}.conv{1..5}.{weight,bias}, body.{i}.rdb{j}.conv1x1.weight
+ * (plus), conv_body, conv_up1, conv_up2, conv_hr, conv_last.  Same weight store, workspace and dry-run sizing rules as the other
+ * handles.  num_feat != 64 or num_grow_ch != 32: GYRE_ERR_UNSUPPORTED at create. */
+int gyre_rrdb_create(const gyre_rrdb_cfg* cfg, int device, gyre_rrdb** out);
+void gyre_rrdb_destroy(gyre_rrdb* h);
+int gyre_rrdb_num_params(const gyre_rrdb* h);
+const char* gyre_rrdb_param_key(const gyre_rrdb* h, int i);
+int gyre_rrdb_set_weight(gyre_rrdb* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_rrdb_finalize(gyre_rrdb* h, void* stream);
+size_t gyre_rrdb_workspace_bytes(gyre_rrdb* h, int B, int H, int W);
+/* out[B, num_out_ch, H * scale, W * scale] = RRDBNet(image[B, num_in_ch, H, W]).  H and W must be multiples of 2 / 4 for scale
+ * 2 / 1 (GYRE_ERR_INVALID otherwise).  A sample's result does not depend on the batch it runs in. */
+int gyre_rrdb_forward(gyre_rrdb* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                      void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
+/* Which kernel the 3x3 convolutions take: 0 auto (the fused dense-block kernel where it measured faster), 1 generic (the planner's
+ * GEMM kernels with bias only, then the epilogue kernel in place), 2 fused everywhere; tuning: 0x100 | mask takes the fused kernel for
+ * exactly the shape groups of the mask (bit 0 conv1-4 of a dense block, 1 conv5, 2 the upsampling convolutions, 3 conv_last,
+ * 4 conv_first / conv_body / conv_hr).  The workspace size depends on the path. */
+int gyre_rrdb_set_path(gyre_rrdb* h, int path);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -708,6 +763,16 @@ int gyre_op_relu(void* stream, void* x, size_t n);
 int gyre_op_silu(void* stream, void* x, size_t n);
 int gyre_op_ctrl_emit(void* stream, const void* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
                       int out_dtype, int out_B, int out_b0);
+/* The kernels of the RRDBNet upscaler (kernels_rdb.hip).  rdb_tile: the output tile (pixels) of the dense-block convolution.
+ * rdb_conv: one launch of it; GYRE_ERR_UNSUPPORTED outside its domain (NT other than 32 / 64, Cin % 32, strides or c0 not multiples of
+ * 8, unaligned buffers, grid limits) and GYRE_ERR_INVALID for bad arguments, nothing written either way.  rdb_epilogue: the same
+ * epilogue in place over x[pix][c0 .. c0 + N_live) of npix pixels with stride ldo (acc = the stored value).  pixel_unshuffle: x NCHW
+ * [B][c][H][W] of a runtime dtype -> y NHWC storage [B][H / r][W / r][c r^2 rounded up to 32] in torch pixel_unshuffle channel
+ * order (r = 1, 2, 4; the padding channels are zeros). */
+int gyre_op_rdb_tile(int* th, int* tw);
+int gyre_op_rdb_conv(void* stream, const gyre_rdb_conv_args* args);
+int gyre_op_rdb_epilogue(void* stream, void* x, int c0, int ldo, int N_live, size_t npix, const gyre_rdb_epilogue* epi);
+int gyre_op_pixel_unshuffle(void* stream, const void* x, int dtype, int B, int c, int H, int W, int r, void* y);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
