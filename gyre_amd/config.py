@@ -213,3 +213,77 @@ def rrdb_config(plus: bool = False, **kw) -> RRDBConfig:
 def tiny_rrdb(**kw) -> RRDBConfig:
     """Two RRDBs (six dense blocks, the third-block epilogue included) at the only widths the family has."""
     return rrdb_config(**{"num_block": 2, **kw})
+
+
+class SwinIRConfig(dict):
+    """Configuration of a SwinIR upscaler - the keyword arguments of the reference's ``SwinIR`` constructor
+    (gyre/pipeline/upscalers/models/network_swinir.py:651-657): a mapping that also reads as attributes."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+# the reference's default configurations (gyre/pipeline/upscalers/upscaler_loader.py:43-69)
+SWINIR_DEFAULTS = {
+    "swinir": dict(upscale=4, in_chans=3, img_size=64, window_size=8, img_range=1.0, depths=[6, 6, 6, 6, 6, 6], embed_dim=180,
+                   num_heads=[6, 6, 6, 6, 6, 6], mlp_ratio=2, upsampler="nearest+conv", resi_connection="1conv"),
+    "swinir-l": dict(upscale=4, in_chans=3, img_size=64, window_size=8, img_range=1.0, depths=[6, 6, 6, 6, 6, 6, 6, 6, 6], embed_dim=240,
+                     num_heads=[8, 8, 8, 8, 8, 8, 8, 8, 8], mlp_ratio=2, upsampler="nearest+conv", resi_connection="3conv")}
+
+# SwinIR.__init__'s own defaults: what a key the caller leaves out means
+_SWINIR_CTOR = dict(img_size=64, patch_size=1, in_chans=3, embed_dim=96, depths=[6, 6, 6, 6], num_heads=[6, 6, 6, 6], window_size=7,
+                    mlp_ratio=4.0, qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.1, norm_layer=None,
+                    ape=False, patch_norm=True, use_checkpoint=False, upscale=2, img_range=1.0, upsampler="", resi_connection="1conv")
+
+
+def swinir_config(**kw) -> SwinIRConfig:
+    """The constructor's defaults under ``kw``, refused (NotImplementedError) outside what the native path builds: window 8,
+    embed_dim = 30 * heads with one head count (at most 8) for all layers, an MLP width that is a multiple of 8, "nearest+conv" with
+    upscale 2 or 4, "1conv" / "3conv", ape=False, patch_norm=True, qkv_bias=True, in_chans=3.  A key that is not a constructor
+    argument is refused too - the reference swallows it in ``**kwargs``; here a folder of another model family fails at its
+    configuration instead of at load_state_dict."""
+    unknown = sorted(set(kw) - set(_SWINIR_CTOR))
+    if unknown:
+        raise NotImplementedError(f"SwinIR: {unknown} are not arguments of the SwinIR constructor (a configuration of another model family?)")
+    cfg = SwinIRConfig(**{**_SWINIR_CTOR, **kw})
+    cfg["depths"], cfg["num_heads"] = [int(d) for d in cfg["depths"]], [int(h) for h in cfg["num_heads"]]
+
+    def refuse(why):
+        raise NotImplementedError(f"SwinIR: {why} is outside the native path")
+
+    size = cfg["img_size"]
+    size = (size, size) if isinstance(size, int) else tuple(size)
+    if cfg["window_size"] != 8:
+        refuse(f"window_size {cfg['window_size']} (8 is built)")
+    if min(size) <= 8 or size[0] % 8 or size[1] % 8:
+        refuse(f"img_size {cfg['img_size']} (multiples of the window above it are built)")
+    if cfg["patch_size"] != 1 or cfg["in_chans"] != 3:
+        refuse("patch_size other than 1 or in_chans other than 3")
+    if cfg["upsampler"] != "nearest+conv" or cfg["upscale"] not in (2, 4):
+        refuse(f"upsampler {cfg['upsampler']!r} at upscale {cfg['upscale']} (nearest+conv at 2 or 4 is built; pixelshuffle, pixelshuffledirect and the denoising form are not)")
+    if cfg["resi_connection"] not in ("1conv", "3conv"):
+        refuse(f"resi_connection {cfg['resi_connection']!r}")
+    if cfg["ape"] or not cfg["patch_norm"] or not cfg["qkv_bias"] or cfg["qk_scale"] is not None:
+        refuse("ape=True, patch_norm=False, qkv_bias=False or a qk_scale")
+    if cfg["norm_layer"] is not None and cfg["norm_layer"] is not __import__("torch").nn.LayerNorm:
+        refuse("a norm_layer other than LayerNorm")
+    heads, depths = cfg["num_heads"], cfg["depths"]
+    if not depths or len(depths) != len(heads) or len(depths) > 16 or min(depths) < 1:
+        refuse(f"depths {depths} with num_heads {heads} (1 to 16 layers, one head count per layer)")
+    if len(set(heads)) != 1 or not 1 <= heads[0] <= 8 or cfg["embed_dim"] != 30 * heads[0]:
+        refuse(f"embed_dim {cfg['embed_dim']} with num_heads {heads} (embed_dim = 30 * heads, the same 1 to 8 heads in every layer)")
+    hidden = int(cfg["embed_dim"] * cfg["mlp_ratio"])
+    if hidden < 8 or hidden % 8:
+        refuse(f"an MLP width of {hidden} (multiples of 8 are built)")
+    if not float(cfg["img_range"]) > 0:
+        raise ValueError("SwinIR: img_range must be positive")
+    return cfg
+
+
+def tiny_swinir(**kw) -> SwinIRConfig:
+    """Two RSTBs of two blocks (plain and shifted windows, both residual levels) at embed 60 / 2 heads, x4, built for 16 x 16 images."""
+    return swinir_config(**{**dict(upscale=4, img_size=16, window_size=8, depths=[2, 2], embed_dim=60, num_heads=[2, 2], mlp_ratio=2,
+                                   upsampler="nearest+conv", resi_connection="1conv"), **kw})

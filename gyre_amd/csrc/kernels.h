@@ -178,6 +178,27 @@ int launch_rdb_copy(hipStream_t st, const bf16_t* src, int lds, bf16_t* dst, int
 int rdb_unshuffle_channels(int c, int r);
 int launch_pixel_unshuffle(hipStream_t st, const void* x, int dtype, int B, int c, int H, int W, int r, bf16_t* y);
 
+// ---- SwinIR upscaler kernels (kernels_swin.hip) ---------------------------------
+// Shifted-window attention over 8 x 8 windows, head dim 30 stored as 32 (arithmetic and layouts: header of kernels_swin.hip).
+//   qkv [B H W][ld_qkv] token order, q / k / v of head h at columns 32 h / 32 (heads + h) / 32 (2 heads + h); o [B H W][ld_o], head h
+//   written at [30 h, 30 h + 30) and nothing else; bias: launch_win_bias's output; shift 0 or 4 (0 when H == 8 or W == 8).
+// The scale 30^-1/2 is applied to the fp32 dot products inside the kernel: the stored q weights and bias are the checkpoint's own.
+// GYRE_ERR_UNSUPPORTED / GYRE_ERR_INVALID outside the domain, nothing written.
+int win_attn_check(const bf16_t* qkv, int ld_qkv, const bf16_t* o, int ld_o, const float* bias, int B, int H, int W, int heads, int shift);
+int launch_win_attn(hipStream_t st, const bf16_t* qkv, int ld_qkv, bf16_t* o, int ld_o, const float* bias, int B, int H, int W, int heads,
+                    int shift);
+// relative_position_bias_table [225][heads] fp32 -> the expanded bias [heads][64 x 64] fp32 in the kernel's register order
+int launch_win_bias(hipStream_t st, const float* table, int heads, float* out);
+// LayerNorm over the first C channels of rows with stride ldx (C <= 512); y rows of stride ldy <= 512: normalised in [0, C), zero in [C, ldy)
+int launch_ln_live(hipStream_t st, const bf16_t* x, int ldx, size_t M, int C, const float* gamma, const float* beta, float eps, bf16_t* y,
+                   int ldy);
+// in place over n contiguous elements (n % 8 == 0): mode 0 erf GELU, mode 1 leaky ReLU of the given slope (the net uses 0.2 and 0.01)
+int launch_swin_act(hipStream_t st, bf16_t* x, size_t n, int mode, float slope);
+// entry: x NCHW [B][3][HW] runtime dtype -> y NHWC storage [B][HW][8] = (x - mean[c]) * range, channels 3 .. 7 zero
+// exit:  x NHWC storage [B][HW][ldx]     -> y NCHW [B][3][HW] runtime dtype = x / range + mean[c]
+int launch_swin_entry(hipStream_t st, const void* x, int dtype, int B, size_t HW, const float* mean3, float range, bf16_t* y);
+int launch_swin_exit(hipStream_t st, const bf16_t* x, int ldx, int B, size_t HW, const float* mean3, float range, void* y, int dtype);
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

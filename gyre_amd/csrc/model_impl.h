@@ -89,7 +89,10 @@ struct Tn {  // NHWC bf16 activation (or a raw byte buffer when C == 0)
 // ------------------------------------------------------------------------------------------
 // weight store
 // ------------------------------------------------------------------------------------------
-enum ParamKind { PK_CONV3 = 0, PK_MAT = 1, PK_VEC = 2, PK_MAT_GEGLU = 3, PK_VEC_GEGLU = 4 };
+enum ParamKind { PK_CONV3 = 0, PK_MAT = 1, PK_VEC = 2, PK_MAT_GEGLU = 3, PK_VEC_GEGLU = 4,
+                 // SwinIR (model_swinir.hip): a fused qkv projection [3 heads 30][I] whose 30-row groups (q, k, v of every head) land at
+                 // 32-row pitch, rows 30 and 31 of a group staying the zeros of the allocation; its bias likewise; a plain fp32 table
+                 PK_MAT_HEAD30 = 5, PK_VEC_HEAD30 = 6, PK_TABLE_F32 = 7 };
 struct Param {
     std::string key;
     std::vector<int64_t> shape;  // PyTorch shape expected from the caller
@@ -117,6 +120,7 @@ struct Store {
         DC_BLOCKED,      // blocked order of the LDS-DMA tile kernels (GemmParams::W_blk), every routed weight with K > 1024
         DC_SHORTCUT,     // conv2 rows | 1x1 shortcut rows, and the sum of the two biases (GemmParams::sc_*)
         DC_PROJ_OUT,     // proj_out composed with the last FF2: Wc [C][5C] = [Wp W2 | Wp], bc = Wp b2 + bp (Exec::proj_out_folded)
+        DC_WIN_BIAS,     // a window attention's relative-position table expanded to [heads][64 x 64] in its kernel's order (launch_win_bias)
         DC_RDB_CHUNKED   // K-chunk order of the dense-block convolution kernel (launch_rdb_wpack, model_rrdb.hip); tag = NT
     };
     struct DKey {
@@ -204,6 +208,8 @@ struct Store {
         auto it = by_key.find(key);
         if (it == by_key.end()) GYRE_FAIL(GYRE_ERR_KEY, std::string("unknown weight key: ") + key);
         Param& p = *it->second;
+        if (matrices_only && p.kind >= PK_MAT_HEAD30)
+            GYRE_FAIL(GYRE_ERR_UNSUPPORTED, std::string(matrices_only) + " is not built for the SwinIR weight " + key);
         if (matrices_only && (p.kind == PK_VEC || p.kind == PK_VEC_GEGLU))
             GYRE_FAIL(GYRE_ERR_INVALID, std::string(matrices_only) + " applies to matrices and convolutions, not to the vector " + key);
         if (dtype < 0 || dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
@@ -245,6 +251,25 @@ struct Store {
             }
             case PK_VEC: TRY(launch_cast_f32(st, src, dtype, (size_t)O, 0, (float*)p.dev, p.scale)); break;
             case PK_VEC_GEGLU: TRY(launch_cast_f32(st, src, dtype, (size_t)O, 1, (float*)p.dev)); break;
+            case PK_MAT_HEAD30: case PK_VEC_HEAD30: {
+                const size_t esz = dtype == 0 ? 4 : 2;
+                for (int g = 0; g < O / 30; ++g) {
+                    if (p.kind == PK_MAT_HEAD30) {
+                        const int I = (int)p.shape[1];
+                        TRY(launch_repack_conv(st, (const char*)src + (size_t)g * 30 * I * esz, dtype, 30, I, 1, 1, p.i_pad,
+                                               (bf16_t*)p.dev + (size_t)g * 32 * p.i_pad));
+                    } else {
+                        TRY(launch_cast_f32(st, (const char*)src + (size_t)g * 30 * esz, dtype, 30, 0, (float*)p.dev + g * 32));
+                    }
+                }
+                break;
+            }
+            case PK_TABLE_F32: {
+                size_t n = 1;
+                for (auto d : p.shape) n *= (size_t)d;
+                TRY(launch_cast_f32(st, src, dtype, n, 0, (float*)p.dev));
+                break;
+            }
         }
         mark_set(p);
         return 0;

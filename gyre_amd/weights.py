@@ -306,3 +306,68 @@ def rrdb_param_shapes(cfg) -> Shapes:
         conv(name, nf, nf)
     conv("conv_last", cfg["num_out_ch"], nf)
     return s
+
+
+SWINIR_BUFFERS = ("attn.relative_position_index", "attn_mask")      # state-dict entries that are buffers: loaded, never read
+
+
+def swinir_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``SwinIR`` (gyre/pipeline/upscalers/models/network_swinir.py) with
+    upsampler "nearest+conv", in state_dict() order and with its two kinds of buffers (SWINIR_BUFFERS): every attention's
+    ``relative_position_index`` and the ``attn_mask`` of the shifted (odd) blocks, built for cfg["img_size"]; cfg: a mapping as
+    gyre_amd.config.tiny_swinir returns."""
+    s: Shapes = OrderedDict()
+    C, heads, upscale = cfg["embed_dim"], cfg["num_heads"], cfg["upscale"]
+    hidden = int(C * cfg["mlp_ratio"])
+    size = cfg["img_size"]
+    size = (size, size) if isinstance(size, int) else tuple(size)
+    three = cfg["resi_connection"] == "3conv"
+
+    def conv(p, o, i, k=3):
+        s[p + ".weight"] = (o, i, k, k)
+        s[p + ".bias"] = (o,)
+
+    def lin(p, o, i):
+        s[p + ".weight"] = (o, i)
+        s[p + ".bias"] = (o,)
+
+    def norm(p):
+        s[p + ".weight"] = (C,)
+        s[p + ".bias"] = (C,)
+
+    def resi(p):
+        if not three:
+            return conv(p, C, C)
+        conv(p + ".0", C // 4, C)
+        conv(p + ".2", C // 4, C // 4, 1)
+        conv(p + ".4", C, C // 4)
+
+    conv("conv_first", C, cfg["in_chans"])
+    norm("patch_embed.norm")
+    for i, depth in enumerate(cfg["depths"]):
+        for j in range(depth):
+            p = f"layers.{i}.residual_group.blocks.{j}"
+            if j % 2:
+                s[p + ".attn_mask"] = (size[0] // 8 * (size[1] // 8), 64, 64)
+            norm(p + ".norm1")
+            s[p + ".attn.relative_position_bias_table"] = (225, heads[i])
+            s[p + ".attn.relative_position_index"] = (64, 64)
+            lin(p + ".attn.qkv", 3 * C, C)
+            lin(p + ".attn.proj", C, C)
+            norm(p + ".norm2")
+            lin(p + ".mlp.fc1", hidden, C)
+            lin(p + ".mlp.fc2", C, hidden)
+        resi(f"layers.{i}.conv")
+    norm("norm")
+    resi("conv_after_body")
+    conv("conv_before_upsample.0", 64, C)
+    conv("conv_up1", 64, 64)
+    if upscale == 4:
+        conv("conv_up2", 64, 64)
+    conv("conv_hr", 64, 64)
+    conv("conv_last", cfg["in_chans"], 64)
+    return s
+
+
+def swinir_is_buffer(key: str) -> bool:
+    return key.endswith(SWINIR_BUFFERS)

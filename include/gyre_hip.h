@@ -154,7 +154,23 @@ typedef struct {
     void* wpack; size_t wpack_bytes;
 } gyre_rdb_conv_args;
 
+/* SwinIR upscaler (the reference's gyre/pipeline/upscalers/models/network_swinir.py, upsampler "nearest+conv").  Built: window 8,
+ * embed_dim = 30 * heads with the same head count (<= 8) in every layer, mlp_hidden % 8 == 0, upscale 2 or 4, in_chans 3. */
+typedef struct {
+    int32_t in_chans;                /* 3 */
+    int32_t embed_dim;               /* 180 (swinir), 240 (swinir-l) */
+    int32_t num_layers;              /* RSTBs: 6 / 9 (<= 16) */
+    int32_t depths[16];              /* blocks per RSTB: 6 */
+    int32_t num_heads[16];           /* 6 / 8 */
+    int32_t window_size;             /* 8 (the only one built) */
+    int32_t mlp_hidden;              /* int(embed_dim * mlp_ratio): 360 / 480 */
+    int32_t upscale;                 /* 4 or 2 */
+    float img_range;                 /* 1.0 */
+    int32_t resi_3conv;              /* 0 = "1conv", 1 = "3conv" */
+} gyre_swinir_cfg;
+
 typedef struct gyre_unet gyre_unet;
+typedef struct gyre_swinir gyre_swinir;
 typedef struct gyre_vae gyre_vae;
 typedef struct gyre_t2i gyre_t2i;
 typedef struct gyre_ctrl gyre_ctrl;
@@ -391,6 +407,25 @@ int gyre_rrdb_forward(gyre_rrdb* h, void* stream, const void* image_nchw, int in
  * exactly the shape groups of the mask (bit 0 conv1-4 of a dense block, 1 conv5, 2 the upsampling convolutions, 3 conv_last,
  * 4 conv_first / conv_body / conv_hr).  The workspace size depends on the path. */
 int gyre_rrdb_set_path(gyre_rrdb* h, int path);
+
+/* ---- SwinIR upscaler -------------------------------------------------------- */
+/* Weight keys are the reference's state-dict names: conv_first, patch_embed.norm, layers.{i}.residual_group.blocks.{j}.{norm1,
+ * attn.relative_position_bias_table, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2}, layers.{i}.conv (3conv: .conv.0 / .2 / .4), norm,
+ * conv_after_body (3conv: .0 / .2 / .4), conv_before_upsample.0, conv_up1, conv_up2 (x4 only), conv_hr, conv_last.  Same weight store,
+ * workspace and dry-run sizing rules as the other handles.  A configuration outside the built list (gyre_swinir_cfg): GYRE_ERR_UNSUPPORTED
+ * at create. */
+int gyre_swinir_create(const gyre_swinir_cfg* cfg, int device, gyre_swinir** out);
+void gyre_swinir_destroy(gyre_swinir* h);
+int gyre_swinir_num_params(const gyre_swinir* h);
+const char* gyre_swinir_param_key(const gyre_swinir* h, int i);
+int gyre_swinir_set_weight(gyre_swinir* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_swinir_finalize(gyre_swinir* h, void* stream);
+size_t gyre_swinir_workspace_bytes(gyre_swinir* h, int B, int H, int W);
+/* out[B, 3, H * upscale, W * upscale] = SwinIR(image[B, 3, H, W]).  H and W must be multiples of 8 (GYRE_ERR_INVALID otherwise; the
+ * reflect padding of check_image_size is the caller's).  Blocks with an odd index use the shift 4, except on an image of one window per
+ * side.  A sample's result does not depend on the batch it runs in. */
+int gyre_swinir_forward(gyre_swinir* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                        void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -773,6 +808,23 @@ int gyre_op_rdb_tile(int* th, int* tw);
 int gyre_op_rdb_conv(void* stream, const gyre_rdb_conv_args* args);
 int gyre_op_rdb_epilogue(void* stream, void* x, int c0, int ldo, int N_live, size_t npix, const gyre_rdb_epilogue* epi);
 int gyre_op_pixel_unshuffle(void* stream, const void* x, int dtype, int B, int c, int H, int W, int r, void* y);
+/* The kernels of the SwinIR upscaler (kernels_swin.hip).  win_bias: relative_position_bias_table [225][heads] fp32 -> bias_out, heads *
+ * 4096 floats in the attention kernel's order.  win_attn: shifted-window attention over 8 x 8 windows, head dim 30 stored as 32: qkv
+ * [B H W][ld_qkv] storage, token order, q / k / v of head h at columns 32 h / 32 (heads + h) / 32 (2 heads + h); o [B H W][ld_o], head h
+ * written at [30 h, 30 h + 30), every other element keeps its bits; bias = win_bias's output; shift 0 or 4 (0 when H == 8 or W == 8);
+ * the scale 30^-1/2 multiplies the fp32 dot products.  GYRE_ERR_UNSUPPORTED / GYRE_ERR_INVALID outside the domain, nothing written.
+ * ln_live: LayerNorm over the first C channels of M rows with stride ldx; y rows of stride ldy: values in [0, C), zeros in [C, ldy).
+ * swin_act: in place on n storage elements (n % 8 == 0), mode 0 = erf GELU, mode 1 = leaky ReLU with the given slope.
+ * swin_entry: x NCHW [B][3][HW] -> y NHWC storage [B][HW][8] = (x - mean[c]) * range, channels 3 .. 7 zero.  swin_exit: x NHWC storage
+ * [B][HW][ldx] -> y NCHW [B][3][HW] = x / range + mean[c]. */
+int gyre_op_win_bias(void* stream, const float* table, int heads, float* bias_out);
+int gyre_op_win_attn(void* stream, const void* qkv, int ld_qkv, void* o, int ld_o, const float* bias, int B, int H, int W, int heads,
+                     int shift);
+int gyre_op_ln_live(void* stream, const void* x, int ldx, size_t M, int C, const float* gamma, const float* beta, float eps, void* y,
+                    int ldy);
+int gyre_op_swin_act(void* stream, void* x, size_t n, int mode, float slope);
+int gyre_op_swin_entry(void* stream, const void* x, int dtype, int B, size_t HW, const float* mean3, float range, void* y);
+int gyre_op_swin_exit(void* stream, const void* x, int ldx, int B, size_t HW, const float* mean3, float range, void* y, int dtype);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
