@@ -267,7 +267,15 @@ int gyre_unet_select_context(gyre_unet* h, int slot) {
 }
 int gyre_unet_debug_tap(gyre_unet* h, const char* name, float* out_nchw_f32, size_t out_bytes) {
     if (!h || !name || !out_nchw_f32) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (!h->tap_channels.count(name)) GYRE_FAIL(GYRE_ERR_INVALID, std::string("debug tap: this UNet has no tensor named ") + name);
     h->taps[name] = {out_nchw_f32, out_bytes};
+    return 0;
+}
+int gyre_unet_debug_grad_tap(gyre_unet* h, const char* name, float* out_nchw_f32, size_t out_bytes) {
+    if (!h || !name || !out_nchw_f32) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (!h->tap_channels.count(name) || !gyre_unet::tap_is_node(name))
+        GYRE_FAIL(GYRE_ERR_INVALID, std::string("gradient tap: this UNet has no node named ") + name);
+    h->gtaps[name] = {out_nchw_f32, out_bytes};
     return 0;
 }
 int gyre_unet_forward_ex(gyre_unet* h, void* st, const void* x, int xdt, const int64_t* t, const void* ctx, int cdt, int B,

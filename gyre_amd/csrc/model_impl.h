@@ -1283,6 +1283,7 @@ struct UNetVjpNode {
     const ResW* rw = nullptr; const TransW* tw = nullptr; const ConvW* cw = nullptr;
     Tn x, skip, r, out; bool has_skip = false;
     ResSave rs; TransSave ts;
+    std::string rn, tn;          // debug-tap names: state-dict prefix of the resnet (or resampling conv) and of the transformer
 };
 struct UNetVjpState {
     bool valid = false, dry = false;
@@ -1309,6 +1310,45 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
     ConvW conv_out;
     // debug taps (parity tests): name -> (device f32 NCHW buffer, capacity in bytes); consumed by the next forward
     std::map<std::string, std::pair<float*, size_t>> taps;
+    // ... and gradient taps: the complete gradient of a node's output, consumed by the next reverse sweep (model_vjp.hip)
+    std::map<std::string, std::pair<float*, size_t>> gtaps;
+    std::map<std::string, int> tap_channels;         // every name a tap may carry -> channels of that tensor (reg_tap_names)
+    static bool tap_is_node(const std::string& name) { return name == "conv_in" || name.find('.') != std::string::npos; }
+    // Names: the levels ("down<i>", "mid", "up<i>": the tensor at the end of a level) and the nodes - the state-dict prefixes of
+    // conv_in, every resnet, every Transformer2D (its output: after proj_out and the residual) and every resampling conv.
+    void reg_tap_names() {
+        const gyre_unet_cfg& c = cfg;
+        const int n = c.n_levels;
+        tap_channels.clear();
+        tap_channels["conv_in"] = c.block_out_channels[0];
+        auto level = [&](const std::string& p, int resnets, bool attn, const char* sampler, int ch) {
+            for (int j = 0; j < resnets; ++j) {
+                tap_channels[p + ".resnets." + std::to_string(j)] = ch;
+                if (attn) tap_channels[p + ".attentions." + std::to_string(j)] = ch;
+            }
+            if (sampler) tap_channels[p + sampler] = ch;
+        };
+        for (int i = 0; i < n; ++i) {
+            level("down_blocks." + std::to_string(i), c.layers_per_block, c.attn_levels[i] != 0, i < n - 1 ? ".downsamplers.0" : nullptr,
+                  c.block_out_channels[i]);
+            tap_channels["down" + std::to_string(i)] = c.block_out_channels[i];
+            const int lvl = n - 1 - i;
+            level("up_blocks." + std::to_string(i), c.layers_per_block + 1, c.attn_levels[lvl] != 0, i < n - 1 ? ".upsamplers.0" : nullptr,
+                  c.block_out_channels[lvl]);
+            tap_channels["up" + std::to_string(i)] = c.block_out_channels[lvl];
+        }
+        level("mid_block", 2, false, nullptr, c.block_out_channels[n - 1]);
+        tap_channels["mid_block.attentions.0"] = tap_channels["mid"] = c.block_out_channels[n - 1];
+    }
+    // copy t (NHWC, storage type) into the buffer `from` holds under `name`, if any: f32 NCHW, t.B samples
+    int tap_copy(const std::map<std::string, std::pair<float*, size_t>>& from, hipStream_t st, const std::string& name, const Tn& t) {
+        auto it = from.find(name);
+        if (it == from.end()) return 0;
+        const int channels = tap_channels.at(name);
+        const size_t need = (size_t)t.B * channels * t.H * t.W * sizeof(float);
+        if (it->second.second < need) GYRE_FAIL(GYRE_ERR_INVALID, "tap buffer too small for " + name);
+        return launch_nhwc_to_nchw_f32(st, t.p, t.B, channels, t.H * t.W, t.C, it->second.first);
+    }
     // text-context cache (cross-attention K / V^T per layer, and the bf16 copy of the context)
     // GYRE_CTX_SLOTS independent entries: a hires-fix / graft tree and CFGUNet_Sequential alternate between contexts on
     // every step (reference unet/cfg.py:27-38, unet/hires_fix.py:123-235); gyre_unet_select_context switches without
@@ -1341,6 +1381,7 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
         const gyre_unet_cfg& c = cfg;
         const int n = c.n_levels;
         TRY(check_cfg(c, ""));
+        reg_tap_names();
         int up_cols = 0;                                   // time_emb_proj columns of the up path
         for (int i = 0; i < n; ++i) up_cols += (c.layers_per_block + 1) * c.block_out_channels[i];
         TRY(build_trunk(store, ex, c, up_cols, [] {}));
@@ -1394,6 +1435,7 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
         if (B < 1 || H < 1 || W < 1 || S < 1) GYRE_FAIL(GYRE_ERR_INVALID, "unet: empty batch / image / context");
         ex.arena.reset((char*)ws, ws_bytes, dry);
         vjp.valid = false;                           // the arena is being reused: a pending reverse sweep has lost its activations
+        if (!dry) gtaps.clear();                     // ... and the gradient taps set for it go with it
         ex.st = st; ex.batch = B;
         ex.cs_unit = gn_unit;                        // producers leave GroupNorm statistics where they can (attach_colstats)
         ex.keep_proj_out = !dry && !taps.empty();
@@ -1444,19 +1486,23 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
         TRY(time_embed(e, c, x, xdt, Bp, H, W, ctx, cdt, cached ? 0 : S, t, B, Bt, temb_add, xin, cx, tp));
         const float* tproj = (const float*)tp.p;
 
-        auto tap = [&](const std::string& name, const Tn& t, int channels) -> int {
-            if (dry) return 0;
-            auto it = taps.find(name);
-            if (it == taps.end()) return 0;
-            const size_t need = (size_t)t.B * channels * t.H * t.W * sizeof(float);
-            if (it->second.second < need) GYRE_FAIL(GYRE_ERR_INVALID, "tap buffer too small for " + name);
-            return launch_nhwc_to_nchw_f32(st, t.p, t.B, channels, t.H * t.W, t.C, it->second.first);
+        const bool tapped = !dry && !taps.empty();
+        auto tap = [&](const std::string& name, const Tn& t) -> int {
+            const int rc = tap_copy(taps, st, name, t);                       // (a tapped call runs no shared CFG prefix: t holds all B samples)
+            if (rc) taps.clear();                                             // a refused tap does not wait for the next call
+            return rc;
         };
+        // node names are put together for a tapped call only
+        auto tap_node = [&](const char* path, int i, const char* kind, int j, const Tn& t) -> int {
+            return tapped ? tap(std::string(path) + "_blocks." + std::to_string(i) + kind + std::to_string(j), t) : 0;
+        };
+        auto tap_level = [&](const char* path, int i, const Tn& t) -> int { return tapped ? tap(path + std::to_string(i), t) : 0; };
         std::vector<Tn> skips;
         Tn h;
         e.batch = Bp;
         TRY(e.conv3(xin, conv_in, 1, 1, 0, nullptr, 0, nullptr, h));
         e.free(xin);
+        if (tapped) TRY(tap("conv_in", h));
         if (pairs) {                                   // the skip connection the up path reads holds all B samples
             Tn hd;
             TRY(e.dup_batch(h, hd));
@@ -1480,10 +1526,12 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
                     continue;
                 }
                 TRY(e.resnet(skips.back(), nullptr, down[i].res[j], tproj, ld_tp, 1e-5f, r));
+                TRY(tap_node("down", i, ".resnets.", j, r));
                 if (c.attn_levels[i]) {
                     Tn a;
                     TRY(e.transformer(r, cx, S, D, down[i].attn[j], a));
                     e.free(r); r = a;
+                    TRY(tap_node("down", i, ".attentions.", j, r));
                 }
                 skips.push_back(r);
             }
@@ -1500,18 +1548,22 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
                 Tn d;
                 TRY(e.conv3(skips.back(), down[i].resample, 2, 1, 0, nullptr, 0, nullptr, d));
                 skips.push_back(d);
+                TRY(tap_node("down", i, ".downsamplers.", 0, d));
             }
             if (adapter && !adapt_before) TRY(adapt());
-            TRY(tap("down" + std::to_string(i), skips.back(), c.block_out_channels[i]));
+            TRY(tap_level("down", i, skips.back()));
         }
         {
             Tn a, b2;
             TRY(e.resnet(skips.back(), nullptr, mid0, tproj, ld_tp, 1e-5f, a));
+            if (tapped) TRY(tap("mid_block.resnets.0", a));
             TRY(e.transformer(a, cx, S, D, mid_attn, b2));
             e.free(a);
+            if (tapped) TRY(tap("mid_block.attentions.0", b2));
             TRY(e.resnet(b2, nullptr, mid1, tproj, ld_tp, 1e-5f, h));
             e.free(b2);
-            TRY(tap("mid", h, c.block_out_channels[n - 1]));
+            if (tapped) TRY(tap("mid_block.resnets.1", h));
+            if (tapped) TRY(tap("mid", h));
         }
         if (down_res) {
             if (n_down_res != (int)skips.size())
@@ -1534,10 +1586,12 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
                 Tn r;
                 TRY(e.resnet(h, &sk, up[i].res[j], tproj, ld_tp, 1e-5f, r));
                 e.free(h); e.free(sk);
+                TRY(tap_node("up", i, ".resnets.", j, r));
                 if (c.attn_levels[lvl]) {
                     Tn a;
                     TRY(e.transformer(r, cx, S, D, up[i].attn[j], a));
                     e.free(r); r = a;
+                    TRY(tap_node("up", i, ".attentions.", j, r));
                 }
                 h = r;
             }
@@ -1545,8 +1599,9 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
                 Tn u;   // resize to the next skip connection's size (= 2x unless the latent size is odd at this level)
                 TRY(e.conv3(h, up[i].resample, 1, 1, 1, nullptr, 0, nullptr, u, skips.back().H, skips.back().W));
                 e.free(h); h = u;
+                TRY(tap_node("up", i, ".upsamplers.", 0, h));
             }
-            TRY(tap("up" + std::to_string(i), h, c.block_out_channels[lvl]));
+            TRY(tap_level("up", i, h));
         }
         if (!dry) taps.clear();
         Tn a;

@@ -392,13 +392,32 @@ int gyre_unet_vjp_forward(gyre_unet& u, bool dry, hipStream_t st, const void* x,
     Node &midn = V.midn, &mid1n = V.mid1n;
     std::vector<Tn>& skips = V.skips;
     Tn h;
+    // debug taps (gyre_unet_debug_tap) are served by this forward too; it runs the same launches with and without them
+    auto tap = [&](const std::string& name, const Tn& t) -> int {
+        if (dry || u.taps.empty()) return 0;
+        const int rc = u.tap_copy(u.taps, st, name, t);
+        if (rc) u.taps.clear();
+        return rc;
+    };
     TRY(e.conv3(xin, u.conv_in, 1, 1, 0, nullptr, 0, nullptr, h));
     skips.push_back(h);
-    auto node_fwd = [&](Node& nd) -> int {
+    TRY(tap("conv_in", h));
+    auto node_fwd = [&](Node& nd, const std::string& p, int j) -> int {
+        nd.rn = p + ".resnets." + std::to_string(j);
         TRY(e.resnet(nd.x, nd.has_skip ? &nd.skip : nullptr, *nd.rw, tproj, u.temb_cols, 1e-5f, nd.r, &nd.rs));
         nd.out = nd.r;
-        if (nd.tw) TRY(e.transformer(nd.r, cx, S, D, *nd.tw, nd.out, &nd.ts));
+        TRY(tap(nd.rn, nd.r));
+        if (nd.tw) {
+            nd.tn = p + ".attentions." + std::to_string(j);
+            TRY(e.transformer(nd.r, cx, S, D, *nd.tw, nd.out, &nd.ts));
+            TRY(tap(nd.tn, nd.out));
+        }
         return 0;
+    };
+    auto sampler_fwd = [&](Node& nd, const std::string& name, int stride, int ups, int Ho, int Wo) -> int {
+        nd.rn = name;
+        TRY(e.conv3(nd.x, *nd.cw, stride, 1, ups, nullptr, 0, nullptr, nd.out, Ho, Wo));
+        return tap(nd.rn, nd.out);
     };
     for (int i = 0; i < n; ++i) {
         for (int j = 0; j < c.layers_per_block; ++j) {
@@ -406,22 +425,24 @@ int gyre_unet_vjp_forward(gyre_unet& u, bool dry, hipStream_t st, const void* x,
             Node& nd = downs.back();
             nd.rw = &u.down[i].res[j]; nd.x = skips.back();
             if (c.attn_levels[i]) nd.tw = &u.down[i].attn[j];
-            TRY(node_fwd(nd));
+            TRY(node_fwd(nd, "down_blocks." + std::to_string(i), j));
             skips.push_back(nd.out);
         }
         if (u.down[i].has_resample) {
             downs.emplace_back();
             Node& nd = downs.back();
             nd.cw = &u.down[i].resample; nd.x = skips.back();
-            TRY(e.conv3(nd.x, *nd.cw, 2, 1, 0, nullptr, 0, nullptr, nd.out));
+            TRY(sampler_fwd(nd, "down_blocks." + std::to_string(i) + ".downsamplers.0", 2, 0, 0, 0));
             skips.push_back(nd.out);
         }
+        TRY(tap("down" + std::to_string(i), skips.back()));
     }
     midn.rw = &u.mid0; midn.tw = &u.mid_attn; midn.x = skips.back();
-    TRY(node_fwd(midn));
+    TRY(node_fwd(midn, "mid_block", 0));
     mid1n.rw = &u.mid1; mid1n.x = midn.out;
-    TRY(node_fwd(mid1n));
+    TRY(node_fwd(mid1n, "mid_block", 1));
     h = mid1n.out;
+    TRY(tap("mid", h));
     size_t sp = skips.size();
     for (int i = 0; i < n; ++i) {
         const int lvl = n - 1 - i;
@@ -430,18 +451,20 @@ int gyre_unet_vjp_forward(gyre_unet& u, bool dry, hipStream_t st, const void* x,
             Node& nd = ups.back();
             nd.rw = &u.up[i].res[j]; nd.x = h; nd.skip = skips[--sp]; nd.has_skip = true;
             if (c.attn_levels[lvl]) nd.tw = &u.up[i].attn[j];
-            TRY(node_fwd(nd));
+            TRY(node_fwd(nd, "up_blocks." + std::to_string(i), j));
             h = nd.out;
         }
         if (u.up[i].has_resample) {
             ups.emplace_back();
             Node& nd = ups.back();
             nd.cw = &u.up[i].resample; nd.x = h;
-            TRY(e.conv3(nd.x, *nd.cw, 1, 1, 1, nullptr, 0, nullptr, nd.out, skips[sp - 1].H, skips[sp - 1].W));
+            TRY(sampler_fwd(nd, "up_blocks." + std::to_string(i) + ".upsamplers.0", 1, 1, skips[sp - 1].H, skips[sp - 1].W));
             h = nd.out;
         }
+        TRY(tap("up" + std::to_string(i), h));
     }
     if (sp != 0) GYRE_FAIL(GYRE_ERR_INVALID, "internal: skip bookkeeping");
+    if (!dry) u.taps.clear();
     Tn a;
     TRY(e.groupnorm(h, nullptr, u.ong, u.onb, 1e-5f, 1, a));
     TRY(e.conv3_nchw(a, u.conv_out, eps_out, odt));
@@ -478,8 +501,15 @@ static void narrow_state(UNetVjpState& V, int b0, int nb) {
 }
 int gyre_unet_vjp_reverse(gyre_unet& u, hipStream_t st, const void* d_eps, int ddt, void* dx_out, int dxdt, int b0, int nb) {
     UNetVjpState& V = u.vjp;
+    // gradient taps (gyre_unet_debug_grad_tap) belong to this sweep, whether it runs or not; they only add copies of gradients the
+    // sweep holds anyway - the launches of the sweep itself are the same with and without them
+    std::map<std::string, std::pair<float*, size_t>> gtaps;
+    if (!V.dry || !V.valid) gtaps.swap(u.gtaps);
     if (!V.valid) GYRE_FAIL(GYRE_ERR_INVALID, "unet vjp: no forward state pending (another call on this handle ran in between)");
     V.valid = false;                                   // one reverse sweep per forward: gradients are freed as they are consumed
+    auto gtap = [&](const std::string& name, const Tn& g) -> int {     // g: the COMPLETE gradient of the output of node `name`
+        return V.dry || gtaps.empty() ? 0 : u.tap_copy(gtaps, st, name, g);
+    };
     const gyre_unet_cfg& c = u.cfg;
     Exec& e = u.ex;
     const bool dry = V.dry;
@@ -504,9 +534,11 @@ int gyre_unet_vjp_reverse(gyre_unet& u, hipStream_t st, const void* d_eps, int d
     auto node_bwd = [&](Node& nd, Tn& g, Tn* dskip) -> int {     // in: gradient of nd.out; out: gradient of nd.x (and of nd.skip)
         if (nd.tw) {
             Tn gr;
+            TRY(gtap(nd.tn, g));
             TRY(transformer_bwd(e, nd.r, cx, S, D, *nd.tw, nd.ts, g, gr));
             e.free(g); g = gr;
         }
+        TRY(gtap(nd.rn, g));
         Tn gin;
         TRY(resnet_bwd(e, nd.x, nd.has_skip ? &nd.skip : nullptr, *nd.rw, tproj, u.temb_cols, 1e-5f, nd.rs, g, gin, dskip));
         e.free(g); g = gin;
@@ -518,6 +550,7 @@ int gyre_unet_vjp_reverse(gyre_unet& u, hipStream_t st, const void* d_eps, int d
         Node& nd = ups[k];
         if (nd.cw) {
             Tn g;
+            TRY(gtap(nd.rn, dh));
             TRY(conv3_bwd(e, dh, *nd.cw, nd.x.C, 1, 1, 1, nd.x.H, nd.x.W, nullptr, g));
             e.free(dh); dh = g;
         } else {
@@ -537,6 +570,7 @@ int gyre_unet_vjp_reverse(gyre_unet& u, hipStream_t st, const void* d_eps, int d
         Node& nd = downs[k];
         if (nd.cw) {
             Tn g;
+            TRY(gtap(nd.rn, dh));
             TRY(conv3_bwd(e, dh, *nd.cw, nd.x.C, 2, 1, 0, nd.x.H, nd.x.W, &dskips[k], g));
             e.free(dh); dh = g;
         } else {
@@ -545,6 +579,7 @@ int gyre_unet_vjp_reverse(gyre_unet& u, hipStream_t st, const void* d_eps, int d
         }
         e.free(dskips[k]);
     }
+    TRY(gtap("conv_in", dh));
     TRY(conv_in_bwd(e, dh, u.conv_in, c.in_channels, V.xin_c, dx_out, dxdt));
     e.free(dh);
     return 0;

@@ -345,8 +345,22 @@ int gyre_unet_vjp_finish_range(gyre_unet* h, void* stream, const void* d_eps_nch
 
 /* Parity tests only: the next forward copies the named intermediate activation (f32, NCHW) into out.  Names follow
  * the oracle's taps: "down<i>" (end of down level i, after its downsampler), "mid", "up<i>" (end of up level i, after
- * its upsampler).  Taps are cleared by that forward. */
+ * its upsampler), and the NODES by their state-dict prefix: "conv_in", every "<block>.resnets.<j>", every
+ * "<block>.attentions.<j>" (the Transformer2D's output, after proj_out and its residual), every "<block>.downsamplers.0" /
+ * "<block>.upsamplers.0".  A name this UNet does not have is GYRE_ERR_INVALID here, a buffer too small for the tensor is
+ * GYRE_ERR_INVALID in the forward.  The next forward is a gyre_unet_forward* call or the activation-keeping pass of
+ * gyre_unet_vjp / gyre_unet_vjp_begin; taps are cleared by it.
+ * A tapped gyre_unet_forward* call loses two fusions, whatever the names: proj_out runs as its own launch instead of inside the
+ * last FF2 (one rounding more per Transformer2D), and the halves of a CFG pair do not share their prefix
+ * (gyre_unet_hint_cfg_pairs is ignored).  The activation-keeping pass has neither fusion and runs the same launches tapped or not. */
 int gyre_unet_debug_tap(gyre_unet* h, const char* name, float* out_nchw_f32, size_t out_bytes);
+/* Same for the reverse sweep: the next one (gyre_unet_vjp_finish, gyre_unet_vjp_finish_range or the sweep of gyre_unet_vjp) copies
+ * the COMPLETE gradient of the named node's output into out - for a tensor that is also a skip connection the sum of the up
+ * path's and the down path's contributions, i.e. what the adjoint of the node that produced it receives; for "conv_in" what the
+ * adjoint of conv_in receives.  Node names only (no level names).  With a sample range the buffer holds nb samples.  The sweep
+ * runs the same launches tapped or not.  Gradient taps are cleared by that sweep; a gyre_unet_forward* call, which drops a
+ * pending forward state, clears them too. */
+int gyre_unet_debug_grad_tap(gyre_unet* h, const char* name, float* out_nchw_f32, size_t out_bytes);
 
 /* Same, plus an optional additive term for the time embedding: temb_add[B, 4*block_out_channels[0]] (f32, dev) is
  * added to time_embedding(t) before it feeds the ResNet blocks.  This is how SDXL's `text_time` added conditioning

@@ -214,7 +214,10 @@ def unet_forward(sd: SD, cfg: UNetRefConfig, latents: Tensor, t: Tensor, encoder
                  down_res: Optional[Sequence[Tensor]] = None, mid_res: Optional[Tensor] = None,
                  adapter_states: Optional[Sequence[Tensor]] = None) -> Tensor:
     """eps = unet(latents[NCHW], t[int64 N], ctx[N,S,D]).  ``taps`` (optional dict)
-    receives named intermediate activations for block-level parity tests.
+    receives named intermediate activations for block-level parity tests: "temb", the levels "down<i>" / "mid" / "up<i>",
+    and the nodes under their state-dict prefix - "conv_in", every resnet, every Transformer2D (its output, after proj_out
+    and the residual) and every resampling conv ("<block>.downsamplers.0" / "<block>.upsamplers.0").  The tensors are the
+    ones of the graph: a gradient reference calls retain_grad() on them before it differentiates.
     down_res / mid_res: ControlNet residuals with the semantics of the reference's in-tree patcher
     (gyre/pipeline/controlnet/unet_patcher.py:30-95): added to the skip connections as the UP path consumes them
     (`res_sample + extra`) and to the mid block's output; the down path and the mid block see the plain activations.
@@ -233,22 +236,28 @@ def unet_forward(sd: SD, cfg: UNetRefConfig, latents: Tensor, t: Tensor, encoder
     if taps is not None:
         taps["temb"] = temb
 
-    h = _conv(latents, sd, "conv_in")
+    def node(name: str, y: Tensor) -> Tensor:
+        if taps is not None:
+            taps[name] = y
+        return y
+
+    h = node("conv_in", _conv(latents, sd, "conv_in"))
     skips: List[Tensor] = [h]
     nlev = len(boc)
     for i in range(nlev):
         for j in range(cfg.layers_per_block):
-            h = resnet_block(h, temb, sd, f"down_blocks.{i}.resnets.{j}", g, eps)
+            h = node(f"down_blocks.{i}.resnets.{j}", resnet_block(h, temb, sd, f"down_blocks.{i}.resnets.{j}", g, eps))
             if cfg.attn_levels[i]:
                 h = transformer_2d(h, encoder_hidden_states, sd, f"down_blocks.{i}.attentions.{j}",
                                    cfg.num_heads[i], g, cfg.transformer_depth[i], cfg.use_linear_projection, tome_r)
+                node(f"down_blocks.{i}.attentions.{j}", h)
             skips.append(h)
         adapt_before = adapter_states is not None and (cfg.attn_levels[i] or i == nlev - 1)
         if adapt_before:                         # in place in the reference: the stored skip connection changes with it
             h = h + adapter_states[i]
             skips[-1] = h
         if i < nlev - 1:
-            h = _conv(h, sd, f"down_blocks.{i}.downsamplers.0.conv", stride=2, padding=1)
+            h = node(f"down_blocks.{i}.downsamplers.0", _conv(h, sd, f"down_blocks.{i}.downsamplers.0.conv", stride=2, padding=1))
             skips.append(h)
         if adapter_states is not None and not adapt_before:
             h = h + adapter_states[i]
@@ -256,10 +265,10 @@ def unet_forward(sd: SD, cfg: UNetRefConfig, latents: Tensor, t: Tensor, encoder
         if taps is not None:
             taps[f"down{i}"] = h
 
-    h = resnet_block(h, temb, sd, "mid_block.resnets.0", g, eps)
-    h = transformer_2d(h, encoder_hidden_states, sd, "mid_block.attentions.0", cfg.num_heads[-1], g,
-                       cfg.transformer_depth[-1], cfg.use_linear_projection, tome_r)
-    h = resnet_block(h, temb, sd, "mid_block.resnets.1", g, eps)
+    h = node("mid_block.resnets.0", resnet_block(h, temb, sd, "mid_block.resnets.0", g, eps))
+    h = node("mid_block.attentions.0", transformer_2d(h, encoder_hidden_states, sd, "mid_block.attentions.0", cfg.num_heads[-1], g,
+                                                      cfg.transformer_depth[-1], cfg.use_linear_projection, tome_r))
+    h = node("mid_block.resnets.1", resnet_block(h, temb, sd, "mid_block.resnets.1", g, eps))
     if taps is not None:
         taps["mid"] = h
     if down_res is not None:
@@ -273,14 +282,15 @@ def unet_forward(sd: SD, cfg: UNetRefConfig, latents: Tensor, t: Tensor, encoder
         lvl = nlev - 1 - i
         for j in range(cfg.layers_per_block + 1):
             h = torch.cat([h, skips.pop()], dim=1)
-            h = resnet_block(h, temb, sd, f"up_blocks.{i}.resnets.{j}", g, eps)
+            h = node(f"up_blocks.{i}.resnets.{j}", resnet_block(h, temb, sd, f"up_blocks.{i}.resnets.{j}", g, eps))
             if cfg.attn_levels[lvl]:
                 h = transformer_2d(h, encoder_hidden_states, sd, f"up_blocks.{i}.attentions.{j}",
                                    cfg.num_heads[lvl], g, cfg.transformer_depth[lvl], cfg.use_linear_projection, tome_r)
+                node(f"up_blocks.{i}.attentions.{j}", h)
         if i < nlev - 1:
             # diffusers resizes to the next skip connection's size (forward_upsample_size) - 2x unless a level is odd
             h = F.interpolate(h, size=skips[-1].shape[-2:], mode="nearest")
-            h = _conv(h, sd, f"up_blocks.{i}.upsamplers.0.conv")
+            h = node(f"up_blocks.{i}.upsamplers.0", _conv(h, sd, f"up_blocks.{i}.upsamplers.0.conv"))
         if taps is not None:
             taps[f"up{i}"] = h
 
