@@ -112,6 +112,13 @@ class GemmTestArgs(C.Structure):
                [("sc_A", C.c_void_p), ("sc_A2", C.c_void_p)] + [(n, C.c_int32) for n in ("sc_K", "sc_C1", "sc_lda", "sc_lda2")]
 
 
+class UpsampleConvTestArgs(C.Structure):
+    """gyre_upsample_conv_test_args (include/gyre_hip.h): an upsampler conv in the four-parity 2x2 form, for tests and tuning."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "Hi", "Wi", "Cin", "N", "splits", "colstat_unit")] + \
+               [(n, C.c_void_p) for n in ("x", "w", "bias", "out", "colstat_out", "scratch")] + [("scratch_bytes", C.c_size_t)] + \
+               [("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class LoraPair(C.Structure):
     """gyre_lora_pair (include/gyre_hip.h): one up / down factor pair of a LoRA, device pointers."""
     _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("dtype", C.c_int), ("rank", C.c_int), ("scale", C.c_float)]
@@ -227,6 +234,8 @@ _SIGS = {
     "gyre_op_gemm_test": (_i, [_vp, C.POINTER(GemmTestArgs)]),
     "gyre_debug_gemm_plan": (_i, [C.POINTER(GemmTestArgs), C.POINTER(C.c_int32)]),
     "gyre_debug_gemm_tiles": (_i, [C.POINTER(C.c_int32), _i]),
+    "gyre_debug_ups4_plan": (_i, [_i] * 9 + [C.POINTER(C.c_int32)]),
+    "gyre_op_upsample_conv_test": (_i, [_vp, C.POINTER(UpsampleConvTestArgs)]),
     "gyre_set_batch_invariant": (_i, [_i]),
     "gyre_get_batch_invariant": (_i, []),
     "gyre_op_groupnorm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _sz, _vp]),

@@ -75,6 +75,8 @@ enum : int {
     GEMM_DBG_NO_W_BLOCK       = 0x4000000,   // bit 26: row-major weights everywhere (no blocked weight copies)
     GEMM_DBG_TWO_STAGE_CONV   = 0x8000000,   // bit 27: the two-stage K loop for the 128x160 / 256x128 tiles' 3x3 convolutions
     GEMM_DBG_NO_POUT_FOLD     = 0x10000000,  // bit 28: a Transformer2D's proj_out stays its own launch instead of riding inside the last FF2
+    GEMM_DBG_NO_UPS4          = 0x20000000,  // bit 29: the upsampler convs keep nine taps (no four-parity 2x2 form, GemmParams::ups4)
+    GEMM_DBG_UPS4_ALL         = 0x40000000,  // bit 30: the four-parity form wherever the kernel supports it: config 24 whatever the tile count
 };
 int launch_groupnorm_stats(hipStream_t st, const GnParams& p);   // partial sums + finalize -> scale_shift
 int launch_groupnorm_apply(hipStream_t st, const GnParams& p);   // y = act(a*x+b)
@@ -289,7 +291,23 @@ struct GemmParams {
     // conv: circular instead of zero padding along x (bit 0) / y (bit 1) - the reference's request option "tiling"
     // (unified_pipeline.py:1671-1712 patches every Conv2d's own padding to F.pad(mode="circular")); 4-wave tile configs only
     int wrap = 0;
+    // nearest-2x upsample + 3x3 / stride 1 / pad 1 convolution as FOUR 2x2 convolutions on the SOURCE image, one per output parity
+    // (a, b) = (Y & 1, X & 1): after the upsample the nine taps of an output pixel read only 2x2 distinct source pixels, window origin
+    // (i - 1 + a, j - 1 + b) for the output pixel (2i + a, 2j + b), and the upsampled image's zero border is the source's.  K = 4 Cin
+    // (taps t' = 2 ty + tx, chunk outer / tap inner like the nine-tap walk), M = B Ho Wo with Ho = 2 Hi, Wo = 2 Wi as before; the
+    // kernel's tile rows are (parity, 256 rows of that parity's B Hi Wi source pixels) and every store goes to the output row of its
+    // pixel, so out, residual, rowbias and the split-K slabs keep their natural row order.  W_blk holds the composed weights
+    // (launch_compose_ups4): [4 N][4 Cin] in blocked order, rows parity * N + n; the kernel reads W_blk alone (callers set W to the same buffer: the
+    // planner and the launch checks look at it for NULL and alignment only).  Pipelined 256x320 tile only
+    // (GemmPlan::cfg == 24), one source, Cin % 64 == 0; column statistics: Hi Wi % 256 == 0, row block (sample, parity, local tile).
+    // Set by Exec::conv3 and gyre_op_upsample_conv_test alone.
+    int ups4 = 0;
 };
+// the composed weights of GemmParams::ups4 from W [N][9 Cin] (tap-major K): per parity (a, b) and 2x2 tap (ty, tx) the fp32 sum of the
+// nine-tap weights whose upsampled pixel lands on that source pixel - rows ky in {0} | {1, 2} for a = 0, {0, 1} | {2} for a = 1,
+// columns alike - ky ascending outer, kx ascending inner, one rounding to the storage type.  out: 16 N Cin elements, blocked order.
+int launch_compose_ups4(hipStream_t st, const bf16_t* W, int N, int Cin, bf16_t* out);
+bool gemm4s_supports(const GemmParams& p, int cfg);     // (kernels_gemm4s.hip) the pipelined tile configs' domain
 // out[n][0:K1] = a[n][0:K1], out[n][K1:K1+K2] = b[n][0:K2] (bf16 rows; K1, K2 multiples of 8): the folded conv + shortcut weight
 int launch_concat_rows(hipStream_t st, const bf16_t* a, int K1, const bf16_t* b, int K2, int N, bf16_t* out);
 // W'[n][k] = bf16(W[n][k] * gamma[k]); colsum[n] = sum_k W'[n][k]; bias_out[n] = sum_k beta[k] * W[n][k] + (bias ? bias[n] : 0)

@@ -1373,13 +1373,15 @@ static long ar_grid_min() {
 static int pick_cfg(const GemmParams& p, int* splits_out) {
     *splits_out = 1;
     const bool trans = p.out_mode == OUT_BF16_T;
-    auto tiles = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
+    // (ups4: four stacked problems of M / 4 rows, a parity's last tile may be ragged - the tile count the launch will have)
+    auto mtiles = [&](int bm) { return p.ups4 ? 4L * ((p.M / 4 + bm - 1) / bm) : (long)((p.M + bm - 1) / bm); };
+    auto tiles = [&](int bm, int bn) { return mtiles(bm) * ((p.N + bn - 1) / bn); };
     auto tiles_of = [&](int id) { const GemmTile* t = gemm_tile(id); return tiles(t->bm, t->bn); };
     // wave-quantisation efficiency on 256 CUs with `slots` resident workgroups per CU
     auto eff = [&](long t, int slots) { long cap = 256L * slots; long waves = (t + cap - 1) / cap; return (double)t / (double)(waves * cap); };
     // padding efficiency along N and along M (a 256-row tile on 128 rows does half its work on padding)
     auto neff = [&](int bn) { long nt = (p.N + bn - 1) / bn; return (double)p.N / (double)(nt * bn); };
-    auto meff = [&](int bm) { long mt = (p.M + bm - 1) / bm; return (double)p.M / (double)(mt * bm); };
+    auto meff = [&](int bm) { long mt = mtiles(bm); return (double)p.M / (double)(mt * bm); };
     double best = -1; int cfg = 3;
     auto consider = [&](int id, double speed, int slots) {
         const GemmTile* t = gemm_tile(id);
@@ -1392,6 +1394,9 @@ static int pick_cfg(const GemmParams& p, int* splits_out) {
     consider(2, 0.50, 2);
     // circular padding exists in the 4-wave register-staged gather only (a niche request option: correctness over speed)
     const bool wrap_only4 = p.mode == GEMM_CONV3 && p.wrap != 0;
+    // the four-parity upsampler form lives in the pipelined 256x320 tile alone: the caller (Exec::conv3) takes it only where the rules
+    // below answer 24 for the K = 4 Cin problem and keeps nine taps otherwise.  Tuning bit 30: 24 wherever the kernel supports it
+    if (p.ups4 && (p.debug & GEMM_DBG_UPS4_ALL) && gemm4s_supports(p, 24)) return 24;
     // A-resident kernel (kernels_gemm_ar.hip): K = 320 / 640 linear problems with enough rows to cover the chip keep their
     // activations in registers and stream only the weights (tuning bit 21: off)
     // Taken where the N sweep is long enough to amortise the slab load (GEGLU FF1: N = 8 C, 216 -> 129 us at 64x64, 163 -> 124
@@ -1590,6 +1595,8 @@ GemmPlan gemm_plan(const GemmParams& p0) {
         if (!one_split) rows = cs_red_colblock(p.N, unit) <= 2048 ? cs_red_rows(p.rows_per_sample) : 0;
         else if (t->bn % unit == 0 && (t->kind != GEMM_K_4S || p.mode == GEMM_CONV3) && !(pl.cfg == 8 && (p.debug & GEMM_DBG_NO_CS_128x160)))
             rows = t->cs_rows;
+        // (ups4, unsplit: the kernel's row block is 256 SOURCE pixels of one parity - whole blocks per sample and parity)
+        if (rows && p.ups4 && one_split && (pl.cfg != 24 || ((long)p.Hi * p.Wi) % rows)) rows = 0;
         if (rows && p.rows_per_sample % rows == 0) pl.colstat_rows = rows;
     }
     return pl;
@@ -1632,6 +1639,38 @@ int launch_w_block(hipStream_t st, const bf16_t* W, int N, int K, bf16_t* out) {
     GYRE_LAUNCH_CHECK();
     return 0;
 }
+// Composed weights of the four-parity upsampler form (GemmParams::ups4): one thread per 8 channels of (parity, n, 2x2 tap).
+// Row taps of parity a: ty = 0 sums ky in {0} (a = 0) or {0, 1} (a = 1), ty = 1 sums {1, 2} or {2}; columns alike with b.
+// fp32, ky ascending outer / kx ascending inner, one rounding; written straight into the blocked order of the [4 N][4 Cin] matrix.
+__global__ __launch_bounds__(256) void k_compose_ups4(const bf16_t* __restrict__ W, int N, int Cin, bf16_t* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int cv = Cin >> 3;
+    if (t >= (size_t)16 * N * cv) return;
+    const int c = (int)(t % cv) * 8;
+    size_t q = t / cv;
+    const int tap = (int)(q & 3); q >>= 2;
+    const int n = (int)(q % N), par = (int)(q / N);
+    const int a = par >> 1, b = par & 1, ty = tap >> 1, tx = tap & 1;
+    const int ky0 = ty ? (a ? 2 : 1) : 0, ky1 = ty ? 2 : (a ? 1 : 0);
+    const int kx0 = tx ? (b ? 2 : 1) : 0, kx1 = tx ? 2 : (b ? 1 : 0);
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int ky = ky0; ky <= ky1; ++ky)
+        for (int kx = kx0; kx <= kx1; ++kx) {
+            float f[8];
+            unpack8(*(const uint4*)(W + ((size_t)n * 9 + ky * 3 + kx) * Cin + c), f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += f[e];
+        }
+    const int r = par * N + n, k = tap * Cin + c, K4 = 4 * Cin;
+    *(uint4*)(out + ((size_t)(r >> 3) * (K4 >> 6) + (k >> 6)) * 512 + (r & 7) * 64 + (k & 63)) = pack8(s);
+}
+int launch_compose_ups4(hipStream_t st, const bf16_t* W, int N, int Cin, bf16_t* out) {
+    if (Cin % 64 || N % 8 || N < 8 || Cin < 64) GYRE_FAIL(-1, "compose_ups4: Cin must be a multiple of 64 and N of 8");
+    const size_t total = (size_t)16 * N * (Cin / 8);
+    hipLaunchKernelGGL(k_compose_ups4, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, N, Cin, out);
+    GYRE_LAUNCH_CHECK();
+    return 0;
+}
 // tests / tuning: scratch where this thread's bare gyre_op_* calls block their weights on the fly
 static thread_local bf16_t* g_dbg_blk_ws = nullptr;
 static thread_local size_t g_dbg_blk_ws_bytes = 0;
@@ -1649,7 +1688,10 @@ int launch_gemm(hipStream_t st, const GemmParams& p0, const GemmPlan& plan) {
     if (p.K % 8) GYRE_FAIL(-1, "gemm: K must be a multiple of 8");
     if (p.C1 % 8) GYRE_FAIL(-1, "gemm: source split must be a multiple of 8");
     if (p.mode == GEMM_CONV3) {
-        if (p.Cin % 8 || p.K != 9 * p.Cin + p.sc_K) GYRE_FAIL(-1, "conv3x3: Cin must be a multiple of 8 and K == 9*Cin (+ the folded shortcut's channels)");
+        if (p.Cin % 8 || p.K != (p.ups4 ? 4 : 9) * p.Cin + p.sc_K)
+            GYRE_FAIL(-1, "conv3x3: Cin must be a multiple of 8 and K == 9*Cin (+ the folded shortcut's channels; four-parity upsampler form: 4*Cin)");
+        if (p.ups4 && (plan.cfg != 24 || !gemm4s_supports(p, 24)))
+            GYRE_FAIL(-6, "conv3x3: the four-parity upsampler form runs on the pipelined 256x320 tile only (exact 2x, one source, Cin % 64 == 0)");
         if (p.sc_K && (p.sc_K % BK || p.Cin % BK || !p.sc_A || p.stride != 1 || p.pad != 1 || p.ups || p.Hi != p.Ho || p.Wi != p.Wo || p.wrap ||
                        (p.sc_A2 && p.sc_A2 != p.sc_A && (p.sc_C1 <= 0 || p.sc_C1 >= p.sc_K || p.sc_C1 % BK))))
             GYRE_FAIL(-1, "conv3x3: a folded shortcut needs a stride-1 / pad-1 convolution and whole 64-channel steps on both sides");
@@ -1683,7 +1725,7 @@ int launch_gemm(hipStream_t st, const GemmParams& p0, const GemmPlan& plan) {
         if (!p.splitk_ws) { p.splitk_ws = g_dbg_ws; p.splitk_ws_bytes = g_dbg_ws_bytes; }
         if (!p.splitk_ws || p.splitk_ws_bytes < (size_t)splits * p.M * p.N * sizeof(float)) {
             splits = 1;   // no slab space: best single-split configuration instead
-            cfg = pick_cfg_nosplit(p);
+            cfg = p.ups4 ? 24 : pick_cfg_nosplit(p);
         }
     }
     const GemmTile* t = gemm_tile(cfg);

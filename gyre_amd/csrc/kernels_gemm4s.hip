@@ -70,13 +70,19 @@ __device__ __forceinline__ srd_t make_srd(const void* base, unsigned bytes) {
 // rstd * acc - rstd * mean * colsum + bias per element (linear mode, unsplit; instantiated for the 8-wave 256x320 tile only -
 // the weight-dominated GEGLU FF1 of the 16x16 level)
 // CS: column statistics of the output tile for the GroupNorm that consumes it (GemmParams::colstat_out; unsplit launches)
-template <int BM, int BN, int WM, int WN, int MODE, int ZFILL, bool LNF = false, bool CS = false>
+// U4: the four-parity 2x2 form of an upsampler conv (GemmParams::ups4): TAPS = 4 in the K walk, tile rows = (parity, 256 source
+// pixels), every store goes to the output row of its pixel.  A template parameter, not a scalar: the loop keeps its registers
+// !! The U4 epilogue re-reads Hi, Wi and M from offset 0 of the kernarg segment: `GemmParams p` must remain the FIRST kernel argument
+// (static_assert on the kernel's type in launch_cfg4s).
+template <int BM, int BN, int WM, int WN, int MODE, int ZFILL, bool LNF = false, bool CS = false, bool U4 = false>
 __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams p, int tiles_m, int tiles_n, int splits, int group_m) {
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
     constexpr int AP = BM / (8 * NW), BP = BN / (8 * NW);   // DMA pieces (8 rows x 128 B) per wave per stage: A rows, W rows
     constexpr int DTOT = AP + BP, DH0 = (DTOT + 1) / 2;     // pieces [0, DH0) form half 0 of a stage, [DH0, DTOT) half 1
     constexpr int STAGE = (BM + BN) * 128;
+    constexpr int TAPS = U4 ? 4 : 9, TW = U4 ? 2 : 3;      // taps of the conv K walk and of one window row
+    static_assert(!U4 || (MODE == GEMM_CONV3 && ZFILL == 0 && !LNF), "the four-parity form is a convolution");
     static_assert((NW == 4 || NW == 8) && TM % 32 == 0 && TN % 32 == 0 && BM % (8 * NW) == 0 && BN % (8 * NW) == 0 &&
                   MI * NI * 16 <= (NW == 4 ? 256 : 160) && (NI == 4 || NI == 5), "tile shape");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -88,14 +94,19 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
     // weight-dominated problems (deep UNet levels): tm fastest, the workgroups of an XCD stream the same weight slice;
     // otherwise groups of `group_m` tile rows, column-major inside a group, so that the ~32 tiles an XCD runs at a time
     // form a compact block of the output (A rows x W rows both shared in that L2)
-    if ((long)p.M < (MODE == GEMM_CONV3 ? 9L : 1L) * p.N) { tn = bid / tiles_m; tm = bid - tn * tiles_m; }
+    if ((long)p.M < (MODE == GEMM_CONV3 ? (long)TAPS : 1L) * p.N) { tn = bid / tiles_m; tm = bid - tn * tiles_m; }
     else {
         const int per = group_m * tiles_n;
         const int g = bid / per, r = bid - g * per;
         const int rows = min(group_m, tiles_m - g * group_m);
         tn = r / rows; tm = g * group_m + (r - tn * rows);
     }
-    const int m0 = tm * BM, n0 = tn * BN;
+    // U4: tile row tm = (parity, local tile) over the Mr = M / 4 source pixels of one parity; par = 2 a + b
+    int par = 0, tml = tm;
+    if (U4) { const int tpp = tiles_m >> 2; par = tm / tpp; tml = tm - par * tpp; }
+    const int Mr = U4 ? p.M >> 2 : p.M;
+    const int m0 = tml * BM, n0 = tn * BN;
+    [[maybe_unused]] int m0p = U4 ? m0 | par : 0;         // U4: parity and tile row in one register across the loop (see the epilogue)
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = w / WN, wn = w - wm * WN;
@@ -122,12 +133,14 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
         vo_w[i] = p.W_blk ? (unsigned)(n >> 3) * (unsigned)(p.K >> 6) * 1024u + (unsigned)(n & 7) * 128u + kvs * 16u
                           : (unsigned)n * (unsigned)p.K * 2u + kvs * 16u;
     }
-    const char* w_tile = p.W_blk ? (const char*)(p.W_blk + (size_t)(n0 >> 3) * (p.K >> 6) * 512) : (const char*)(p.W + (size_t)n0 * p.K);
+    const int n0w = U4 ? par * p.N + n0 : n0;            // first weight row of the tile (U4: the parity's block of N rows)
+    const char* w_tile = p.W_blk ? (const char*)(p.W_blk + (size_t)(n0w >> 3) * (p.K >> 6) * 512) : (const char*)(p.W + (size_t)n0w * p.K);
     const bool wblk = p.W_blk != nullptr;
     // activations
     unsigned vo_a[AP];                   // linear: byte offset of (row, k-slot) from the tile's first row
     int a_sbp[AP], a_y0[AP], a_x0[AP];   // conv: sample base pixel relative to the tile's first sample, window origin
-    const int hw_o = MODE == GEMM_CONV3 ? p.Ho * p.Wo : 1;
+    const int hw_o = MODE == GEMM_CONV3 ? (U4 ? p.Hi * p.Wi : p.Ho * p.Wo) : 1;    // rows per sample of the tile-row space
+    const int w_o = U4 ? p.Wi : p.Wo;
     const int ns0 = m0 / hw_o;           // first sample this tile touches (conv): sources are addressed relative to it
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
@@ -137,10 +150,11 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
             vo_a[i] = rl * (unsigned)p.lda * 2u + kvs * 16u;
         } else {
             const int n = row / hw_o, rem = row - n * hw_o;
-            const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
+            const int oy = rem / w_o, ox = rem - oy * w_o;
             a_sbp[i] = (n - ns0) * p.Hi * p.Wi;
-            a_y0[i] = row < p.M ? oy * p.stride - p.pad : 0x40000000;   // rows past M: every tap fails the bounds test
-            a_x0[i] = ox * p.stride - p.pad;
+            // (U4: window origin (i - 1 + a, j - 1 + b) on the source image)
+            a_y0[i] = row < Mr ? (U4 ? oy - 1 + (par >> 1) : oy * p.stride - p.pad) : 0x40000000;   // rows past M: every tap fails the bounds test
+            a_x0[i] = U4 ? ox - 1 + (par & 1) : ox * p.stride - p.pad;
         }
     }
     const char* a_tile = (const char*)(p.A + (size_t)m0 * p.lda);
@@ -150,15 +164,15 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
     // before the next step is described, so the first source is dead by then; the split is looked at per K step, not per K slice
     // (a split-K boundary falls anywhere).  One source: a_split is never reached.
     int a_split = (MODE == GEMM_LINEAR && p.A2 != p.A) ? p.C1 : 0x7fffffff;
-    const int Hlim = p.ups ? (p.Hup ? p.Hup : 2 * p.Hi) : p.Hi, Wlim = p.ups ? (p.Wup ? p.Wup : 2 * p.Wi) : p.Wi;
-    const int ups = p.ups ? 1 : 0;
+    const int Hlim = (p.ups && !U4) ? (p.Hup ? p.Hup : 2 * p.Hi) : p.Hi, Wlim = (p.ups && !U4) ? (p.Wup ? p.Wup : 2 * p.Wi) : p.Wi;
+    const int ups = (p.ups && !U4) ? 1 : 0;
     // conv sources, based at the tile's first sample; a tile spans a handful of samples, so 32-bit offsets suffice
     const size_t spix = (size_t)ns0 * p.Hi * p.Wi;
     const char* cA = (const char*)(p.A + spix * p.lda);
     const char* cA2 = (const char*)(p.A2 + spix * p.lda2);
     srd_t srdA{}, srdA2{};
     if (MODE == GEMM_CONV3 && ZFILL == 0) {
-        const size_t left = (size_t)(p.M / hw_o - ns0) * p.Hi * p.Wi;      // pixels from the tile's first sample to the end
+        const size_t left = (size_t)(Mr / hw_o - ns0) * p.Hi * p.Wi;      // pixels from the tile's first sample to the end
         const size_t b1 = left * p.lda * 2, b2 = left * p.lda2 * 2;
         srdA = make_srd(cA, (unsigned)(b1 < 0x7ffffff0ull ? b1 : 0x7ffffff0ull));
         srdA2 = make_srd(cA2, (unsigned)(b2 < 0x7ffffff0ull ? b2 : 0x7ffffff0ull));
@@ -167,7 +181,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
     // steps.  The conv sources are dead from the first shortcut step on, so that step REPLACES them (bases, buffer descriptors, strides,
     // split) instead of carrying a second set through the loop - the kernel sits at 82 of ~100 scalar registers, and a "s" asm
     // operand that no longer fits is silently handed over in vector registers.  step_src is called with non-decreasing kc.
-    const int nk_conv = MODE == GEMM_CONV3 ? 9 * (p.Cin / BK) : 0;
+    const int nk_conv = MODE == GEMM_CONV3 ? TAPS * (p.Cin / BK) : 0;
     int src_C1 = p.C1;
     unsigned src_ld = (unsigned)p.lda * 2u, src_ld2 = (unsigned)p.lda2 * 2u;
     bool on_shortcut = false;
@@ -201,7 +215,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
                     cA2 = (const char*)(p.sc_A2 + spix * p.sc_lda2);
                     src_C1 = p.sc_C1; src_ld = (unsigned)p.sc_lda * 2u; src_ld2 = (unsigned)p.sc_lda2 * 2u;
                     if (ZFILL == 0) {
-                        const size_t left = (size_t)(p.M / hw_o - ns0) * p.Hi * p.Wi;
+                        const size_t left = (size_t)(Mr / hw_o - ns0) * p.Hi * p.Wi;
                         const size_t b1 = left * p.sc_lda * 2, b2 = left * p.sc_lda2 * 2;
                         srdA = make_srd(cA, (unsigned)(b1 < 0x7ffffff0ull ? b1 : 0x7ffffff0ull));
                         srdA2 = make_srd(cA2, (unsigned)(b2 < 0x7ffffff0ull ? b2 : 0x7ffffff0ull));
@@ -209,10 +223,10 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
                 }
                 c0 = (kc - nk_conv) * BK;
                 s.ky = p.pad; s.kx = p.pad;
-                kw = 9 * p.Cin + c0;
+                kw = TAPS * p.Cin + c0;
             } else {
-                const int chunk = kc / 9, tap = kc - chunk * 9;
-                s.ky = tap / 3; s.kx = tap - s.ky * 3;
+                const int chunk = kc / TAPS, tap = kc - chunk * TAPS;
+                s.ky = tap / TW; s.kx = tap - s.ky * TW;
                 c0 = chunk * BK;
                 kw = tap * p.Cin + c0;
             }
@@ -353,21 +367,47 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
     __builtin_amdgcn_s_barrier();
 
     const int hi = lane >> 5, l31 = lane & 31;
-    const int m_base = m0 + wm * TM, n_base = n0 + wn * TN;
+    // U4: the parity crossed the loop in the low bits of the tile's first row (one scalar register, not three: the loop has none to
+    // spare); everything else the epilogue needs about the tile is derived from the two again
+    int m0e = m0, pare = 0;
+    if constexpr (U4) {
+        asm volatile("" : "+s"(m0p));
+        m0e = m0p & ~3; pare = m0p & 3;
+    }
+    const int m_base = m0e + wm * TM, n_base = n0 + wn * TN;
+    // ... and the image size is read from the kernel arguments AGAIN behind the loop (the compiler loads every field of `p` once, at
+    // the top, and would carry these through the loop too)
+    int e_Hi = 0, e_Wi = 0, e_Mr = Mr;
+    if constexpr (U4) {
+        auto* ka = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        // `p` MUST stay the kernel's first argument (offset 0 of the kernarg segment): the launcher asserts the signature
+        const auto* pk = (const __attribute__((address_space(4))) GemmParams*)ka;
+        e_Hi = pk->Hi; e_Wi = pk->Wi; e_Mr = pk->M >> 2;
+    }
+    // output row of tile-row m (< Mr).  U4: source pixel (n, i, j) of parity (a, b) -> n (2 Hi)(2 Wi) + (2 i + a) 2 Wi + 2 j + b
+    auto out_row = [&](int m) {
+        if (!U4) return m;
+        const int hw = e_Hi * e_Wi;
+        const int n = m / hw, rem = m - n * hw;
+        const int i = rem / e_Wi, j = rem - i * e_Wi;
+        return n * 4 * hw + (2 * i + (pare >> 1)) * 2 * e_Wi + 2 * j + (pare & 1);
+    };
     if (!LNF && !CS && splits > 1) {
         // fp32 partial slab of this K slice; bias / residual / rounding happen once in k_splitk_reduce
         float* slab = p.splitk_ws + (size_t)split * p.M * p.N;
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int m = m_base + i * 32 + l31;
-            if (m >= p.M) continue;
+            if (m >= e_Mr) continue;
+            const int mo = out_row(m);          // (U4: the slabs are in output-row order, the reduction kernels do not know the form)
 #pragma unroll
             for (int j = 0; j < NI; ++j)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int n = n_base + j * 32 + 8 * g + 4 * hi;
                     if (n < p.N)
-                        *(float4*)(slab + (size_t)m * p.N + n) =
+                        *(float4*)(slab + (size_t)mo * p.N + n) =
                             make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
                 }
         }
@@ -411,7 +451,8 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 const int m = m_base + i * 32 + l31;
-                const float* rbias = (p.rowbias && m < p.M) ? p.rowbias + (size_t)(m / p.rows_per_sample) * p.ld_rowbias : nullptr;
+                const int mo = m < e_Mr ? out_row(m) : -1;           // this lane's output row; the read-back fetches row r's from lane r
+                const float* rbias = (p.rowbias && m < e_Mr) ? p.rowbias + (size_t)(mo / p.rows_per_sample) * p.ld_rowbias : nullptr;
 #pragma unroll
                 for (int j = j0; j < j1; ++j)
 #pragma unroll
@@ -424,9 +465,9 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
                         }
                         *(float4*)(slabc + l31 * ROWC + (j - j0) * 32 + 8 * g + 4 * hi) = o;
                     }
-                for (int row = r0; row < 32; row += R) {
-                    const int mm = m_base + i * 32 + row;
-                    if (mm < p.M && nn < p.N) {
+                for (int row = r0; row < 32; row += R) {            // (uniform trip count: R divides 32)
+                    const int mm = U4 ? __shfl(mo, row) : m_base + i * 32 + row;
+                    if ((U4 ? mm >= 0 : mm < p.M) && nn < p.N) {
                         const float4 a = *(const float4*)(slabc + row * ROWC + c8 * 8);
                         const float4 b = *(const float4*)(slabc + row * ROWC + c8 * 8 + 4);
                         float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -474,7 +515,10 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
             if (n < p.N) {
                 float su = 0.f, sq = 0.f;
                 for (int c = 0; c < unit; ++c) { const float2 v = chan[u * unit + c]; su += v.x; sq += v.y; }
-                ((float2*)p.colstat_out)[(size_t)tm * (p.N / unit) + n / unit] = make_float2(su, sq);
+                // U4 (Hi Wi % BM == 0: a tile lies in one sample): row block (sample, parity, local tile) - a sample's blocks stay one run
+                int blk = tm;
+                if (U4) { const int tle = m0e / BM, tps = e_Hi * e_Wi / BM, ns = tle / tps; blk = ns * 4 * tps + pare * tps + (tle - ns * tps); }
+                ((float2*)p.colstat_out)[(size_t)blk * (p.N / unit) + n / unit] = make_float2(su, sq);
             }
         }
         return;
@@ -490,7 +534,8 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         const int m = m_base + i * 32 + l31;
-        const float* rbias = (p.rowbias && m < p.M) ? p.rowbias + (size_t)(m / p.rows_per_sample) * p.ld_rowbias : nullptr;
+        const int mo = m < e_Mr ? out_row(m) : -1;           // this lane's output row; the read-back fetches row r's from lane r
+        const float* rbias = (p.rowbias && m < e_Mr) ? p.rowbias + (size_t)(mo / p.rows_per_sample) * p.ld_rowbias : nullptr;
         // folded LayerNorm: this lane's accumulators of slab i all belong to row m
         float lrstd = 1.f, lrmu = 0.f;
         if constexpr (LNF) {
@@ -556,10 +601,10 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void k_gemm4s(GemmParams
             // read the slab back row-wise: 8 consecutive channels per lane -> one 16-byte store (residual added in fp32 first)
             const int vpr = (j1 - j0) * (gg ? 2 : 4);                               // 16-byte output vectors per row
             const int n_pass = (gg ? n_base / 2 + j0 * 16 : n_base + j0 * 32);      // first output column of this pass
-            for (int v = lane; v < 32 * vpr; v += 64) {
+            for (int v = lane; v < 32 * vpr; v += 64) {                  // (uniform trip count: 32 vpr is a multiple of 64)
                 const int row = v / vpr, c8 = v - row * vpr;
-                const int mm = m_base + i * 32 + row, nn = n_pass + c8 * 8;
-                if (mm < p.M && nn < n_out) {
+                const int mm = U4 ? __shfl(mo, row) : m_base + i * 32 + row, nn = n_pass + c8 * 8;
+                if ((U4 ? mm >= 0 : mm < p.M) && nn < n_out) {
                     const float4 a = *(const float4*)(slab + row * ROWF + c8 * 8);
                     const float4 b = *(const float4*)(slab + row * ROWF + c8 * 8 + 4);
                     float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -595,11 +640,15 @@ bool gemm4s_supports(const GemmParams& p, int cfg) {
         // keep refusing it, like the folded shortcut), whole 64-channel steps on both sides of the split, 16-byte rows
         if (p.A2 && p.A2 != p.A && (cfg != 24 || p.C1 <= 0 || p.C1 >= p.K || p.C1 % BK || p.lda2 % 8 || ((size_t)p.A2 & 15))) return false;
     }
-    else if (p.Cin % BK || c1 % BK || p.K != 9 * p.Cin + p.sc_K || (p.sc_K && (p.sc_K % BK || cfg != 24))) return false;
+    else if (p.Cin % BK || c1 % BK || p.K != (p.ups4 ? 4 : 9) * p.Cin + p.sc_K || (p.sc_K && (p.sc_K % BK || cfg != 24))) return false;
+    // four-parity upsampler form: the 8-wave 256x320 tile only, the exact 2x image of one source, stride 1, zero padding 1, no folded shortcut
+    if (p.ups4 && (p.mode != GEMM_CONV3 || cfg != 24 || p.sc_K || (p.A2 && p.A2 != p.A) || p.stride != 1 || p.pad != 1 || p.wrap ||
+                   p.Ho != 2 * p.Hi || p.Wo != 2 * p.Wi || p.Hi <= 0 || p.Wi <= 0 || p.M % (4 * p.Hi * p.Wi) || p.ln_colsum || p.geglu))
+        return false;
     if (p.mode == GEMM_CONV3) {
-        // a tile's rows span at most 256 / (Ho*Wo) + 2 samples; sources are addressed relative to the first of them with
-        // 24-bit pixel indices and 31-bit byte offsets
-        const size_t span = ((size_t)256 / ((size_t)p.Ho * p.Wo) + 2) * p.Hi * p.Wi;
+        // a tile's rows span at most 256 / (Ho*Wo) + 2 samples (ups4: of Hi*Wi rows each); sources are addressed relative to the first of
+        // them with 24-bit pixel indices and 31-bit byte offsets
+        const size_t span = ((size_t)256 / (p.ups4 ? (size_t)p.Hi * p.Wi : (size_t)p.Ho * p.Wo) + 2) * p.Hi * p.Wi;
         const size_t ld = p.lda > p.lda2 ? p.lda : p.lda2;
         if (span >= (1u << 24) || ld * 2 >= (1u << 24) || span * ld * 2 >= 0x7ff00000ull) return false;
     }
@@ -609,10 +658,12 @@ bool gemm4s_supports(const GemmParams& p, int cfg) {
 
 template <int BM, int BN, int WM, int WN>
 static int launch_cfg4s(hipStream_t st, const GemmParams& p, int kcls_base, int splits) {
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    // ups4: four stacked problems of M / 4 rows each, tile row = (parity, local tile); a parity's last tile may be ragged
+    const int tiles_m = p.ups4 ? 4 * ((p.M / 4 + BM - 1) / BM) : (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
     const int nk_all = (p.K + BK - 1) / BK;
     if (splits > nk_all) splits = nk_all;
     while (splits > 1 && (splits - 1) * ((nk_all + splits - 1) / splits) >= nk_all) --splits;   // no empty K slice
+    if ((long)tiles_m * tiles_n * splits > 0x7fffffffL) GYRE_FAIL(-6, "gemm: grid too large");
     const int grid = tiles_m * tiles_n * splits;
     // LDS: two operand stages; the epilogue's four 32-row fp32 slabs reuse them
     constexpr int NW = WM * WN, NI = BN / WN / 32, JP = NW == 8 ? (NI + 1) / 2 : NI;
@@ -637,7 +688,31 @@ static int launch_cfg4s(hipStream_t st, const GemmParams& p, int kcls_base, int 
             (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, p, tiles_m, tiles_n, splits, group_m);             \
     } while (0)
-    if (p.mode == GEMM_LINEAR && p.ln_colsum) {
+    if (p.ups4) {
+        if constexpr (BM == 256 && BN == 320 && NW == 8) {
+            if (!p.W_blk) GYRE_FAIL(-6, "gemm: the four-parity upsampler form reads the composed weights in blocked order (GemmParams::W_blk)");
+            // the U4 epilogue reads `p` back from offset 0 of the kernarg segment
+            static_assert(std::is_same<decltype(&k_gemm4s<BM, BN, WM, WN, GEMM_CONV3, 0, false, false, true>), void (*)(GemmParams, int, int, int, int)>::value &&
+                          std::is_same<decltype(&k_gemm4s<BM, BN, WM, WN, GEMM_CONV3, 0, false, true, true>), void (*)(GemmParams, int, int, int, int)>::value,
+                          "GemmParams must be the first argument of k_gemm4s");
+            if (p.colstat_out && splits == 1) {
+                if ((p.Hi * p.Wi) % BM) GYRE_FAIL(-6, "gemm: the four-parity form emits column statistics for Hi * Wi % 256 == 0 only");
+                auto kern = k_gemm4s<BM, BN, WM, WN, GEMM_CONV3, 0, false, true, true>;
+                static std::atomic<unsigned long long> attr_done{0};
+                if (gyre_lds_attr_needed(attr_done))
+                    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, p, tiles_m, tiles_n, splits, group_m);
+            } else {
+                auto kern = k_gemm4s<BM, BN, WM, WN, GEMM_CONV3, 0, false, false, true>;
+                static std::atomic<unsigned long long> attr_done{0};
+                if (gyre_lds_attr_needed(attr_done))
+                    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, p, tiles_m, tiles_n, splits, group_m);
+            }
+        } else {
+            GYRE_FAIL(-6, "gemm: the four-parity upsampler form exists for the 8-wave 256x320 pipelined tile only");
+        }
+    } else if (p.mode == GEMM_LINEAR && p.ln_colsum) {
         if constexpr (BM == 256 && BN == 320 && NW == 8) {
             auto kern = k_gemm4s<BM, BN, WM, WN, GEMM_LINEAR, 0, true>;
             static std::atomic<unsigned long long> attr_done{0};

@@ -842,6 +842,53 @@ int gyre_debug_gemm_plan(const gyre_gemm_test_args* a, int32_t* out) {
     out[8] = pl.per_sample_w ? 1 : 0; out[9] = pl.shortcut_fold ? 1 : 0; out[10] = nst; out[11] = uni;
     return 0;
 }
+// The nine-tap upsampler conv Exec::conv3 would describe for these sizes (no pointers), for the shape query and the test operator
+static int ups4_test_problem(GemmParams& p, int B, int Hi, int Wi, int Cin, int N, int Hup, int Wup) {
+    if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || N <= 0 || B > 4096 || Hi > 2048 || Wi > 2048 || Cin > 65536 || N > (1 << 20) || Cin % 8 || N % 8)
+        GYRE_FAIL(GYRE_ERR_INVALID, "ups4: sizes must be positive, Cin and N multiples of 8");
+    if ((Hup != 0 && Hup != 2 * Hi && Hup != 2 * Hi - 1) || (Wup != 0 && Wup != 2 * Wi && Wup != 2 * Wi - 1))
+        GYRE_FAIL(GYRE_ERR_INVALID, "ups4: the upsample target must be 2x or 2x-1 of the input");
+    const int Ho = Hup ? Hup : 2 * Hi, Wo = Wup ? Wup : 2 * Wi;
+    if ((long)B * Ho * Wo > (1 << 24)) GYRE_FAIL(GYRE_ERR_INVALID, "ups4: too many output pixels");
+    p.mode = GEMM_CONV3; p.lda = Cin; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.stride = 1; p.pad = 1; p.ups = 1;
+    p.Hup = Ho; p.Wup = Wo; p.K = 9 * Cin; p.N = N; p.M = B * Ho * Wo; p.rows_per_sample = Ho * Wo; p.samples = B;
+    p.ldc = N; p.out_mode = OUT_BF16;
+    return 0;
+}
+int gyre_debug_ups4_plan(int B, int Hi, int Wi, int Cin, int N, int Hup, int Wup, int tiling, int colstat_unit, int32_t* out) {
+    if (!out || tiling < 0 || tiling > 3 || colstat_unit < 0) GYRE_FAIL(GYRE_ERR_INVALID, "ups4_plan: bad argument");
+    GemmParams p, p4;
+    GemmPlan pl;
+    TRY(ups4_test_problem(p, B, Hi, Wi, Cin, N, Hup, Wup));
+    const bool take = conv3_ups4_rule(p, tiling, B, colstat_unit, &p4, &pl);
+    out[0] = take ? 1 : 0; out[1] = take ? pl.cfg : 0; out[2] = take ? pl.splits : 0; out[3] = take ? pl.colstat_rows : 0;
+    return 0;
+}
+int gyre_op_upsample_conv_test(void* st, const gyre_upsample_conv_test_args* a) {
+    if (!a || !a->x || !a->w || !a->out || !a->scratch) GYRE_FAIL(GYRE_ERR_INVALID, "upsample_conv_test: null argument");
+    if (a->splits < 0 || a->splits > 64 || a->colstat_unit < 0 || (a->colstat_out && a->colstat_unit <= 0))
+        GYRE_FAIL(GYRE_ERR_INVALID, "upsample_conv_test: bad splits / colstat_unit");
+    if (((size_t)a->x & 15) || ((size_t)a->w & 15) || ((size_t)a->out & 15) || ((size_t)a->scratch & 15) || ((size_t)a->bias & 15) ||
+        ((size_t)a->colstat_out & 7) || ((size_t)a->ws & 15))
+        GYRE_FAIL(GYRE_ERR_INVALID, "upsample_conv_test: pointers need 16-byte alignment");
+    GemmParams p, p4;
+    GemmPlan pl;
+    TRY(ups4_test_problem(p, a->B, a->Hi, a->Wi, a->Cin, a->N, 0, 0));
+    if (a->splits > 1) p.force_cfg = 24 | (a->splits << 8);            // forced K slices (no column statistics then, as with every forced config)
+    p.A = (const bf16_t*)a->x; p.W = (const bf16_t*)a->w; p.bias = a->bias; p.out = a->out;
+    if (!conv3_ups4_rule(p, 0, a->B, a->colstat_out ? a->colstat_unit : 0, &p4, &pl))
+        GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "upsample_conv_test: the four-parity form is not taken for this shape under the calling thread's planner state (gyre_debug_ups4_plan)");
+    if (a->scratch_bytes < (size_t)16 * a->N * a->Cin * 2) GYRE_FAIL(GYRE_ERR_WORKSPACE, "upsample_conv_test: scratch below 16 N Cin elements");
+    if (pl.splits > 1 && (!a->ws || a->ws_bytes < pl.ws_bytes)) GYRE_FAIL(GYRE_ERR_WORKSPACE, "upsample_conv_test: the plan runs in K slices and needs its slab space in ws");
+    if (a->colstat_out) {
+        if (pl.colstat_rows <= 0) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "upsample_conv_test: no column statistics for this shape / plan");
+        p4.colstat_unit = a->colstat_unit; p4.colstat_out = a->colstat_out;
+    }
+    TRY(launch_compose_ups4((hipStream_t)st, p.W, a->N, a->Cin, (bf16_t*)a->scratch));
+    p4.W = (const bf16_t*)a->scratch; p4.W_blk = p4.W;
+    p4.splitk_ws = (float*)a->ws; p4.splitk_ws_bytes = a->ws ? a->ws_bytes : 0;
+    return launch_gemm((hipStream_t)st, p4, pl);
+}
 /* (id, bm, bn, kernel family) of every GEMM tile configuration (at most cap ints are written); returns the number of configurations */
 int gyre_debug_gemm_tiles(int32_t* out, int cap) { return gemm_tile_table(out, out ? cap : 0); }
 int gyre_op_ln_linear(void* st, const void* x, int M, int K, const float* gamma, const float* beta, float eps, const void* w,

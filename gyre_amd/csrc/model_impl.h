@@ -112,7 +112,8 @@ struct Store {
     // Derived copies of weights, made on first use and refreshed by their user when any weight was set since (per-request LoRA
     // re-uploads).  One cache for every kind, keyed by (kind, the row-major matrix the copy was made from); the user computes the
     // size, fills the buffer and decides what a failed allocation means.  Memory per SD1.5 UNet handle and device-slot replica
-    // (DESIGN.md 3): DC_BLOCKED ~1.6 GB (~0.15 GB per VAE handle), DC_TRANSPOSED +1.7 GB, DC_SHORTCUT +0.4 GB, DC_PROJ_OUT 124 MB.
+    // (DESIGN.md 3): DC_BLOCKED ~1.6 GB (~0.15 GB per VAE handle), DC_TRANSPOSED +1.7 GB, DC_SHORTCUT +0.4 GB, DC_PROJ_OUT 124 MB,
+    // DC_UPS4 118 MB ((2 x 29.5 + 7.4) MB of upsampler weights x 16 / 9).
     enum Kind {
         DC_TRANSPOSED,   // W^T / rotated conv weights of the input-gradient pass (model_vjp.hip)
         DC_LN_FOLD,      // gamma-folded weights | column sums | bias after a LayerNorm (GemmParams::ln_colsum)
@@ -120,6 +121,7 @@ struct Store {
         DC_BLOCKED,      // blocked order of the LDS-DMA tile kernels (GemmParams::W_blk), every routed weight with K > 1024
         DC_SHORTCUT,     // conv2 rows | 1x1 shortcut rows, and the sum of the two biases (GemmParams::sc_*)
         DC_PROJ_OUT,     // proj_out composed with the last FF2: Wc [C][5C] = [Wp W2 | Wp], bc = Wp b2 + bp (Exec::proj_out_folded)
+        DC_UPS4,         // an upsampler conv's four 2x2 parity matrices [4 N][4 Cin], blocked order (GemmParams::ups4, launch_compose_ups4)
         DC_WIN_BIAS,     // a window attention's relative-position table expanded to [heads][64 x 64] in its kernel's order (launch_win_bias)
         DC_RDB_CHUNKED   // K-chunk order of the dense-block convolution kernel (launch_rdb_wpack, model_rrdb.hip); tag = NT
     };
@@ -144,6 +146,11 @@ struct Store {
         *fresh = en.version == weights_version && en.tag == tag;
         en.version = weights_version; en.tag = tag;
         return en.p;
+    }
+    // the caller could not fill the buffer derived() handed it (its launch failed): the entry is stale again, the next user refills it
+    void derived_unfilled(Kind kind, const void* src) {
+        auto it = derived_.find(DKey{kind, src});
+        if (it != derived_.end() && it->second.p) it->second.version = 0;
     }
     // did the allocation of (kind, src) fail under the current weights_version?  (a user to whom the copy is an optimisation only
     // may then not ask again before a weight is set)
@@ -377,6 +384,29 @@ struct MhaSave { Tn ao, qk, km, vm, idx; int idx_B = 0, idx_b0 = 0; };      // i
 struct ResSave { Tn h1; };                                   // conv1 output (input of the second GroupNorm)
 struct TBlockSave { Tn h0, n1, h1, n2, h2, n3; MhaSave a1, a2; };   // block input, LN outputs, residual stream after each attention
 struct TransSave { std::vector<TBlockSave> blocks; Tn hlast; };     // hlast: residual stream entering proj_out
+// Does the upsampler conv `p9` (nine taps, as Exec::conv3 describes it) take the four-parity 2x2 form (GemmParams::ups4)?  One rule for
+// the runtime and for the shape query (gyre_debug_ups4_plan):
+//   the exact 2x image (the 2H-1 crop of forward_upsample_size keeps nine taps), pad 1, stride 1, one source, no folded shortcut, no
+//   circular padding, Cin % 64 == 0, and the planner hands the K = 4 Cin problem the pipelined 256x320 tile (its usual rules: >= 20 K
+//   steps and >= 160 tiles, or the split-K form from K >= 5000; tuning bit 30: wherever the kernel supports the shape).
+//   Off under batch-invariant planning, like the shortcut fold: the composed weights round differently from nine taps and the planner's
+//   answer depends on the batch.  Tuning bit 29: off.
+// *p4 = the problem in that form (weights not yet set), *pl = its plan with column statistics asked for `cs_unit`.
+static inline bool conv3_ups4_rule(const GemmParams& p9, int tiling, int batch, int cs_unit, GemmParams* p4, GemmPlan* pl) {
+    if (!p9.ups || p9.mode != GEMM_CONV3 || p9.stride != 1 || p9.pad != 1 || tiling || p9.wrap || p9.A2 || p9.sc_K) return false;
+    if (p9.Hi <= 0 || p9.Wi <= 0 || p9.Ho != 2 * p9.Hi || p9.Wo != 2 * p9.Wi || p9.Cin % 64 || p9.lda % 8 || p9.N % 8) return false;
+    if (gemm_get_batch_invariant() > 0 || (gemm_planner_state() & GEMM_DBG_NO_UPS4)) return false;
+    GemmParams q = p9;
+    q.ups4 = 1; q.K = 4 * q.Cin;
+    if (!q.samples) q.samples = batch;
+    GemmParams qs = q;
+    qs.colstat_unit = cs_unit; qs.colstat_out = nullptr;
+    *pl = gemm_plan(qs);
+    if (pl->cfg != 24 || !gemm4s_supports(q, 24)) return false;
+    *p4 = q;
+    return true;
+}
+
 struct Exec {
     Arena arena;
     hipStream_t st = nullptr;
@@ -555,8 +585,48 @@ struct Exec {
                 p.W = fw; p.bias = fb;
             }
         }
+        GemmParams p4; GemmPlan pl4;
+        if (!sc_x && store && conv3_ups4_rule(p, tiling, batch, cs_unit, &p4, &pl4)) return conv3_ups4(p, p4, w, y);
         TRY(attach_colstats(p, y, Ho * Wo));       // every conv output of the UNet feeds a GroupNorm
         return run_gemm(p);
+    }
+    // The upsampler conv `p` (nine taps over the 2x image) as four 2x2 parity convs on composed weights (GemmParams::ups4): 4/9 of the
+    // MACs, same M, N and output.  The composed weights are constant across evaluations and requests - one Store::DC_UPS4 entry per
+    // weight, refreshed when a weight is set.  The dry pass and the real call size the same plan (p4's statistics buffer and slabs);
+    // a call that finds no memory for the composed weights runs the nine taps for that weight version, without producer statistics
+    // and - where its own plan wanted more slab space than p4's - unsplit (launch_gemm's fallback): slower, never an error.
+    int conv3_ups4(GemmParams& p9, GemmParams& p4, const ConvW& w, Tn& y) {
+        p4.out = y.p;
+        TRY(attach_colstats(p4, y, p4.Ho * p4.Wo));
+        const GemmPlan pl = gemm_plan(p4);
+        Tn ws;
+        if (pl.ws_bytes) TRY(alloc_raw(ws, pl.ws_bytes));
+        int rc = 0;
+        if (!dry()) {
+            bf16_t* cw = nullptr;
+            if (!store->derived_failed(Store::DC_UPS4, w.w)) {
+                bool fresh = false;
+                cw = (bf16_t*)store->derived(Store::DC_UPS4, w.w, (size_t)16 * p4.N * p4.Cin * 2, &fresh);
+                if (cw && !fresh) {
+                    rc = launch_compose_ups4(st, w.w, p4.N, p4.Cin, cw);
+                    if (rc) store->derived_unfilled(Store::DC_UPS4, w.w);        // (marked current by derived(): not with an unfilled buffer)
+                }
+            }
+            if (cw && !rc) {
+                p4.W = cw; p4.W_blk = cw;
+                p4.splitk_ws = (float*)ws.p; p4.splitk_ws_bytes = pl.ws_bytes;
+                rc = launch_gemm(st, p4, pl);
+            } else if (!rc) {
+                y.cs_chunks = 0;                     // (the statistics buffer stays reserved; the consumer runs its own pass)
+                p9.samples = batch;
+                const GemmPlan pl9 = gemm_plan(p9);
+                rc = prep_blk(p9, pl9);
+                p9.splitk_ws = (float*)ws.p; p9.splitk_ws_bytes = pl.ws_bytes;
+                if (!rc) rc = launch_gemm(st, p9, pl9);
+            }
+        }
+        free(ws);
+        return rc;
     }
     void fill_shortcut(GemmParams& p, const Tn& sx, const Tn* sskip) const {
         p.sc_A = sx.p; p.sc_lda = sx.C; p.sc_C1 = sx.C; p.sc_K = sx.C;

@@ -542,6 +542,8 @@ int gyre_debug_xattn_stamps(void* dev_buf);
  * stays its own launch instead of riding inside conv2 as extra K steps of the pipelined tile (round 6).
  * Round 7: bit28 = a Transformer2D's proj_out stays its own launch instead of riding inside the FF2 of its last block as extra K
  * steps on composed weights.
+ * Round 12: bit29 = the UNet upsampler convs keep nine taps (no four-parity 2x2 form on composed weights), bit30 = that form wherever
+ * the kernel supports the shape, whatever the planner's tile-count rule (tile config 24 for that conv; tests and tuning on small shapes).
  * Epilogue ablations (garbage): bit3 = no GELU, bit4 = no stores.
  * These switches are PER CALLING THREAD (thread-local, like gyre_set_batch_invariant): they never change what another thread's
  * handle computes. */
@@ -588,6 +590,27 @@ int gyre_op_gemm_test(void* stream, const gyre_gemm_test_args* a);
  * tile configs the LDS ring depth (else 0), for convolutions on the 4- and 8-wave configs whether the K loop takes the uniform-tap
  * form (else 0; the other kernels have no tap forms).  out[9] needs the sc_* fields of the folded shortcut. */
 int gyre_debug_gemm_plan(const gyre_gemm_test_args* a, int32_t* out);
+/* Shape query, no device: would the model runtime run the upsampler (nearest 2x of the NHWC image [B][Hi][Wi][Cin], then a 3x3 / pad 1
+ * convolution into N channels) as four 2x2 parity convolutions on composed weights (k_gemm4s)?  Hup / Wup: size of the
+ * upsampled image (0 = 2 Hi x 2 Wi; the 2 Hi - 1 crop keeps nine taps), tiling: the request's circular-padding bits, colstat_unit: the
+ * channel unit of the GroupNorm statistics asked of the launch (0: none).  Answers for the calling thread's planner state (tuning bits
+ * 29 / 30 of gyre_debug_gemm_ablation, batch-invariant mode, forced config).  out[4] = taken (0 / 1), tile config, K slices,
+ * column-statistics rows (0: the consumer runs its own statistics pass). */
+int gyre_debug_ups4_plan(int B, int Hi, int Wi, int Cin, int N, int Hup, int Wup, int tiling, int colstat_unit, int32_t* out);
+/* Tests / tuning only: that upsampler in the four-parity form, one call.  x NHWC [B][Hi][Wi][Cin] storage, w [N][3][3][Cin] storage
+ * (gyre_op_repack_conv_weight), bias [N] fp32 or NULL, out [B][2 Hi][2 Wi][N] storage.  scratch: 16 N Cin storage elements, receives
+ * the composed weights (four [N][4 Cin] matrices, blocked order) on every call.  splits <= 1: the planner's form for the calling
+ * thread's switches; splits >= 2: that many K slices forced (ws: splits x B 2Hi 2Wi N floats; no column statistics).
+ * colstat_out: [B 4 Hi Wi / rows][N / colstat_unit][2] floats (rows: gyre_debug_ups4_plan) or NULL.  GYRE_ERR_UNSUPPORTED where the
+ * form is not taken (gyre_debug_ups4_plan) - never a nine-tap launch instead. */
+typedef struct gyre_upsample_conv_test_args {
+    int32_t B, Hi, Wi, Cin, N, splits, colstat_unit;
+    const void* x; const void* w; const float* bias;
+    void* out; float* colstat_out;
+    void* scratch; size_t scratch_bytes;
+    void* ws; size_t ws_bytes;
+} gyre_upsample_conv_test_args;
+int gyre_op_upsample_conv_test(void* stream, const gyre_upsample_conv_test_args* a);
 /* The tile-config table: out[4 i ..] = id, rows, columns, kernel family (0 register-staged 4-wave, 1 LDS-DMA 8-wave, 2 pipelined,
  * 3 A-resident, 4 small-problem) of the i-th configuration; at most cap ints are written.  Returns the number of configurations. */
 int gyre_debug_gemm_tiles(int32_t* out, int cap);

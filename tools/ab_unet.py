@@ -47,8 +47,8 @@ res = {f: ([], []) for f in flags}
 outs = {}
 for r in range(rounds):
     for f in flags:
-        L.gyre_debug_gemm_ablation(f & 0x1fffffff)           # (bit 28 = proj_out stays its own launch, round 7)
-        L.gyre_debug_force_attn_variant((f >> 29) & 7)       # bits 29-31: attention variant (7 = per-tile check in every tile)
+        L.gyre_debug_gemm_ablation(f & 0x7fffffff)           # bits 0-30: planner switches (29 / 30 = the four-parity upsampler form, round 12)
+        L.gyre_debug_force_attn_variant((f >> 32) & 7)       # bits 32-34: attention variant (7 = per-tile check in every tile)
         res[f][0].append(timeit(lambda: net(x, t, encoder_hidden_states=ctx).sample, 5))
         res[f][1].append(timeit(lambda: vae.decode(z).sample, 2))
         if r == 0:
