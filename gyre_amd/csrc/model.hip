@@ -266,17 +266,22 @@ int gyre_unet_select_context(gyre_unet* h, int slot) {
     return 0;
 }
 int gyre_unet_debug_tap(gyre_unet* h, const char* name, float* out_nchw_f32, size_t out_bytes) {
-    if (!h || !name || !out_nchw_f32) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    if (!h->tap_channels.count(name)) GYRE_FAIL(GYRE_ERR_INVALID, std::string("debug tap: this UNet has no tensor named ") + name);
-    h->taps[name] = {out_nchw_f32, out_bytes};
-    return 0;
+    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    return h->tap_set(h->taps, true, "debug tap: this UNet has no tensor named ", name, out_nchw_f32, out_bytes);
 }
 int gyre_unet_debug_grad_tap(gyre_unet* h, const char* name, float* out_nchw_f32, size_t out_bytes) {
-    if (!h || !name || !out_nchw_f32) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    if (!h->tap_channels.count(name) || !gyre_unet::tap_is_node(name))
-        GYRE_FAIL(GYRE_ERR_INVALID, std::string("gradient tap: this UNet has no node named ") + name);
-    h->gtaps[name] = {out_nchw_f32, out_bytes};
-    return 0;
+    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    return h->tap_set(h->gtaps, name && gyre_unet::tap_is_node(name), "gradient tap: this UNet has no node named ", name, out_nchw_f32,
+                      out_bytes);
+}
+int gyre_vae_debug_tap(gyre_vae* h, const char* name, float* out_nchw_f32, size_t out_bytes) {
+    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    return h->tap_set(h->taps, true, "debug tap: this VAE has no node named ", name, out_nchw_f32, out_bytes);
+}
+int gyre_vae_debug_grad_tap(gyre_vae* h, const char* name, float* out_nchw_f32, size_t out_bytes) {
+    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    return h->tap_set(h->gtaps, name && gyre_vae::tap_is_decoder_node(name), "gradient tap: this VAE's decoder has no node named ", name,
+                      out_nchw_f32, out_bytes);
 }
 int gyre_unet_forward_ex(gyre_unet* h, void* st, const void* x, int xdt, const int64_t* t, const void* ctx, int cdt, int B,
                          int H, int W, int S, void* ws, size_t wsb, void* out, int odt, const float* temb_add) {
@@ -399,6 +404,8 @@ size_t gyre_vae_decode_vjp_workspace_bytes(gyre_vae* h, int B, int hl, int wl) {
 }
 int gyre_vae_decode_vjp(gyre_vae* h, void* st, const void* z, int zdt, int B, int hl, int wl, const void* d_img, int ddt, void* ws,
                         size_t wsb, void* img_out, int odt, void* dz_out, int dzdt) {
+    // gradient taps belong to this call, also when it is refused below
+    struct DropTaps { gyre_vae* h; ~DropTaps() { if (h) h->gtaps.clear(); } } drop{h};
     if (!h || !z || !d_img || !ws || !img_out || !dz_out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     if (h->ex.tiling) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "the input-gradient sweep has no circular (tiling) convolutions");
     for (int d : {zdt, ddt, odt, dzdt}) if (d < 0 || d > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");

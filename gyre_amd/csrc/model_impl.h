@@ -1365,7 +1365,32 @@ struct UNetVjpState {
     Tn h, cx, tp;
 };
 
-struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_out and conv_out
+// Debug taps of a model handle (parity tests; gyre_unet_debug_tap / gyre_vae_debug_tap and their _grad_ forms): the names a handle
+// knows with the channel count of each tensor, the taps set for the next forward and for the next reverse sweep, and the copy.
+struct DebugTaps {
+    typedef std::map<std::string, std::pair<float*, size_t>> Set;   // name -> (device f32 NCHW buffer, capacity in bytes)
+    Set taps;                                        // consumed by the next forward
+    Set gtaps;                                       // the complete gradient of a node's output: consumed by the next reverse sweep
+    std::map<std::string, int> tap_channels;         // every name a tap may carry -> channels of that tensor
+    // the body of gyre_*_debug_tap / gyre_*_debug_grad_tap (`known`: the handle has the name, and it may carry this kind of tap)
+    int tap_set(Set& into, bool known, const char* what, const char* name, float* out_nchw_f32, size_t out_bytes) {
+        if (!name || !out_nchw_f32) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+        if (!known || !tap_channels.count(name)) GYRE_FAIL(GYRE_ERR_INVALID, std::string(what) + name);
+        into[name] = {out_nchw_f32, out_bytes};
+        return 0;
+    }
+    // copy t (NHWC, storage type) into the buffer `from` holds under `name`, if any: f32 NCHW, t.B samples
+    int tap_copy(const Set& from, hipStream_t st, const std::string& name, const Tn& t) const {
+        auto it = from.find(name);
+        if (it == from.end()) return 0;
+        const int channels = tap_channels.at(name);
+        const size_t need = (size_t)t.B * channels * t.H * t.W * sizeof(float);
+        if (it->second.second < need) GYRE_FAIL(GYRE_ERR_INVALID, "tap buffer too small for " + name);
+        return launch_nhwc_to_nchw_f32(st, t.p, t.B, channels, t.H * t.W, t.C, it->second.first);
+    }
+};
+
+struct gyre_unet : UNetTrunk, DebugTaps {        // the trunk, then the up path, conv_norm_out and conv_out
     gyre_unet_cfg cfg;
     Store store;
     Exec ex;
@@ -1378,11 +1403,7 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
     std::vector<Level> up;
     float *ong, *onb;
     ConvW conv_out;
-    // debug taps (parity tests): name -> (device f32 NCHW buffer, capacity in bytes); consumed by the next forward
-    std::map<std::string, std::pair<float*, size_t>> taps;
-    // ... and gradient taps: the complete gradient of a node's output, consumed by the next reverse sweep (model_vjp.hip)
-    std::map<std::string, std::pair<float*, size_t>> gtaps;
-    std::map<std::string, int> tap_channels;         // every name a tap may carry -> channels of that tensor (reg_tap_names)
+    // debug taps (DebugTaps): `taps` are consumed by the next forward, `gtaps` by the next reverse sweep (model_vjp.hip)
     static bool tap_is_node(const std::string& name) { return name == "conv_in" || name.find('.') != std::string::npos; }
     // Names: the levels ("down<i>", "mid", "up<i>": the tensor at the end of a level) and the nodes - the state-dict prefixes of
     // conv_in, every resnet, every Transformer2D (its output: after proj_out and the residual) and every resampling conv.
@@ -1409,15 +1430,6 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
         }
         level("mid_block", 2, false, nullptr, c.block_out_channels[n - 1]);
         tap_channels["mid_block.attentions.0"] = tap_channels["mid"] = c.block_out_channels[n - 1];
-    }
-    // copy t (NHWC, storage type) into the buffer `from` holds under `name`, if any: f32 NCHW, t.B samples
-    int tap_copy(const std::map<std::string, std::pair<float*, size_t>>& from, hipStream_t st, const std::string& name, const Tn& t) {
-        auto it = from.find(name);
-        if (it == from.end()) return 0;
-        const int channels = tap_channels.at(name);
-        const size_t need = (size_t)t.B * channels * t.H * t.W * sizeof(float);
-        if (it->second.second < need) GYRE_FAIL(GYRE_ERR_INVALID, "tap buffer too small for " + name);
-        return launch_nhwc_to_nchw_f32(st, t.p, t.B, channels, t.H * t.W, t.C, it->second.first);
     }
     // text-context cache (cross-attention K / V^T per layer, and the bf16 copy of the context)
     // GYRE_CTX_SLOTS independent entries: a hires-fix / graft tree and CFGUNet_Sequential alternate between contexts on
@@ -1686,10 +1698,32 @@ struct gyre_unet : UNetTrunk {        // the trunk, then the up path, conv_norm_
 // ------------------------------------------------------------------------------------------
 // VAE
 // ------------------------------------------------------------------------------------------
-struct gyre_vae {
+struct gyre_vae : DebugTaps {
     gyre_vae_cfg cfg;
     Store store;
     Exec ex;
+    // debug taps (DebugTaps): nodes by state-dict prefix.  `taps` belong to the next encode or decode, `gtaps` (decoder nodes only)
+    // to the next decode VJP (model_vjp.hip); either call drops its set when it returns.
+    static bool tap_is_decoder_node(const std::string& name) { return name == "post_quant_conv" || name.compare(0, 8, "decoder.") == 0; }
+    void reg_tap_names() {
+        const gyre_vae_cfg& c = cfg;
+        const int n = c.n_levels, top = c.block_out_channels[n - 1];
+        tap_channels.clear();
+        for (const char* half : {"encoder", "decoder"}) {
+            const std::string h = half;
+            const bool enc = h == "encoder";
+            tap_channels[h + ".conv_in"] = enc ? c.block_out_channels[0] : top;
+            for (const char* m : {".mid_block.resnets.0", ".mid_block.attentions.0", ".mid_block.resnets.1"}) tap_channels[h + m] = top;
+            for (int i = 0; i < n; ++i) {
+                const int ch = c.block_out_channels[enc ? i : n - 1 - i];
+                const std::string p = h + (enc ? ".down_blocks." : ".up_blocks.") + std::to_string(i);
+                for (int j = 0; j < c.layers_per_block + (enc ? 0 : 1); ++j) tap_channels[p + ".resnets." + std::to_string(j)] = ch;
+                if (i < n - 1) tap_channels[p + (enc ? ".downsamplers.0" : ".upsamplers.0")] = ch;
+            }
+        }
+        tap_channels["encoder.conv_out"] = 2 * c.latent_channels;
+        tap_channels["post_quant_conv"] = c.latent_channels;
+    }
     struct Blk { std::vector<ResW> res; ConvW resample; bool has_resample = false; };
     // encoder
     ConvW e_in, e_out; std::vector<Blk> e_down; ResW e_mid0, e_mid1; AttnW e_attn; float *e_ag, *e_ab, *e_ng, *e_nb;
@@ -1719,6 +1753,7 @@ struct gyre_vae {
                 GYRE_FAIL(GYRE_ERR_INVALID, "block_out_channels must be multiples of norm_num_groups and 8");
         ex.groups = c.norm_num_groups;
         ex.store = &store;
+        reg_tap_names();
         int dummy = 0;
         const int z = c.latent_channels;
         // ---- encoder ----
@@ -1786,13 +1821,30 @@ struct gyre_vae {
         e.free(a);
         return 0;
     }
-    int mid(Exec& e, Tn& h, const ResW& r0, const AttnW& aw, const float* g, const float* b, const ResW& r1) {
+    // ft: the forward taps of this call (empty: none), half: "encoder" / "decoder"
+    int mid(Exec& e, Tn& h, const ResW& r0, const AttnW& aw, const float* g, const float* b, const ResW& r1, const Set& ft, const char* half) {
         Tn a, b2, c2;
+        auto tap = [&](const char* node, const Tn& t) -> int {
+            return ft.empty() ? 0 : tap_copy(ft, e.st, std::string(half) + ".mid_block." + node, t);
+        };
         TRY(e.resnet(h, nullptr, r0, nullptr, 0, 1e-6f, a)); e.free(h);
+        TRY(tap("resnets.0", a));
         TRY(vattn(e, a, aw, g, b, b2)); e.free(a);
+        TRY(tap("attentions.0", b2));
         TRY(e.resnet(b2, nullptr, r1, nullptr, 0, 1e-6f, c2)); e.free(b2);
+        TRY(tap("resnets.1", c2));
         h = c2;
         return 0;
+    }
+    // the taps a non-dry encode / decode serves: taken out of the handle, so that they are gone when the call returns, however it ends
+    Set take_taps(bool dry) {
+        Set ft;
+        if (!dry) ft.swap(taps);
+        return ft;
+    }
+    // node names are put together for a tapped call only
+    int tap_node(const Set& ft, hipStream_t st, const char* blocks, int i, const char* kind, int j, const Tn& t) const {
+        return ft.empty() ? 0 : tap_copy(ft, st, std::string(blocks) + std::to_string(i) + kind + std::to_string(j), t);
     }
     int run_encode(bool dry, hipStream_t st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb,
                    void* out, int odt) {
@@ -1801,22 +1853,28 @@ struct gyre_vae {
         if ((H % (1 << (n - 1))) || (W % (1 << (n - 1)))) GYRE_FAIL(GYRE_ERR_INVALID, "vae.encode: H, W must be multiples of 8");
         ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
         Exec& e = ex;
+        const Set ft = take_taps(dry);
         Tn x, h;
         TRY(e.alloc(x, B, H, W, pad8(cfg.in_channels)));
         if (!dry) TRY(launch_nchw_to_nhwc(st, img, idt, B, cfg.in_channels, H * W, x.C, x.p));
         TRY(e.conv3(x, e_in, 1, 1, 0, nullptr, 0, nullptr, h)); e.free(x);
+        if (!ft.empty()) TRY(tap_copy(ft, st, "encoder.conv_in", h));
         for (int i = 0; i < n; ++i) {
+            int j = 0;
             for (auto& rw : e_down[i].res) {
                 Tn r; TRY(e.resnet(h, nullptr, rw, nullptr, 0, 1e-6f, r)); e.free(h); h = r;
+                TRY(tap_node(ft, st, "encoder.down_blocks.", i, ".resnets.", j++, h));
             }
             if (e_down[i].has_resample) {  // pad (0,1,0,1) + stride-2 conv, pad 0
                 Tn d; TRY(e.conv3(h, e_down[i].resample, 2, 0, 0, nullptr, 0, nullptr, d)); e.free(h); h = d;
+                TRY(tap_node(ft, st, "encoder.down_blocks.", i, ".downsamplers.", 0, h));
             }
         }
-        TRY(mid(e, h, e_mid0, e_attn, e_ag, e_ab, e_mid1));
+        TRY(mid(e, h, e_mid0, e_attn, e_ag, e_ab, e_mid1, ft, "encoder"));
         Tn a, m;
         TRY(e.groupnorm(h, nullptr, e_ng, e_nb, 1e-6f, 1, a)); e.free(h);
         TRY(e.conv3(a, e_out, 1, 1, 0, nullptr, 0, nullptr, m)); e.free(a);
+        if (!ft.empty()) TRY(tap_copy(ft, st, "encoder.conv_out", m));
         if (!dry) {
             GemmParams p;
             p.A = m.p; p.lda = m.C; p.mode = GEMM_LINEAR; p.W = quant_w; p.K = m.C; p.N = 2 * cfg.latent_channels;
@@ -1833,20 +1891,26 @@ struct gyre_vae {
         if (B < 1 || h_ < 1 || w_ < 1) GYRE_FAIL(GYRE_ERR_INVALID, "vae.decode: empty input");
         ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
         Exec& e = ex;
+        const Set ft = take_taps(dry);
         Tn x, q, h;
         const int zc = pad8(cfg.latent_channels);
         TRY(e.alloc(x, B, h_, w_, zc));
         if (!dry) TRY(launch_nchw_to_nhwc(st, z, idt, B, cfg.latent_channels, h_ * w_, zc, x.p));
         TRY(e.alloc(q, B, h_, w_, zc));
         TRY(e.linear(x.p, zc, nullptr, 0, 0, x.rows(), zc, pq_w, zc, pq_b, nullptr, 0, 0, q.p, zc)); e.free(x);
+        if (!ft.empty()) TRY(tap_copy(ft, st, "post_quant_conv", q));
         TRY(e.conv3(q, d_in, 1, 1, 0, nullptr, 0, nullptr, h)); e.free(q);
-        TRY(mid(e, h, d_mid0, d_attn, d_ag, d_ab, d_mid1));
+        if (!ft.empty()) TRY(tap_copy(ft, st, "decoder.conv_in", h));
+        TRY(mid(e, h, d_mid0, d_attn, d_ag, d_ab, d_mid1, ft, "decoder"));
         for (int i = 0; i < n; ++i) {
+            int j = 0;
             for (auto& rw : d_up[i].res) {
                 Tn r; TRY(e.resnet(h, nullptr, rw, nullptr, 0, 1e-6f, r)); e.free(h); h = r;
+                TRY(tap_node(ft, st, "decoder.up_blocks.", i, ".resnets.", j++, h));
             }
             if (d_up[i].has_resample) {
                 Tn u; TRY(e.conv3(h, d_up[i].resample, 1, 1, 1, nullptr, 0, nullptr, u)); e.free(h); h = u;
+                TRY(tap_node(ft, st, "decoder.up_blocks.", i, ".upsamplers.", 0, h));
             }
         }
         Tn a;

@@ -604,8 +604,15 @@ int gyre_vae_run_decode_vjp(gyre_vae& v, bool dry, hipStream_t st, const void* z
     Exec& e = v.ex;
     e.arena.reset((char*)ws, wsb, dry); e.st = st; e.batch = B; e.cs_unit = 0;
     const int zc = pad8(c.latent_channels);
-    struct RNode { const ResW* rw; Tn x, out; ResSave rs; };
-    struct UNode { const ConvW* cw; Tn x, out; };
+    // gradient taps (gyre_vae_debug_grad_tap) belong to this call, however it ends; they only add copies of gradients the sweep holds
+    DebugTaps::Set gtaps;
+    if (!dry) gtaps.swap(v.gtaps);
+    const bool gt = !gtaps.empty();
+    auto gtap = [&](const std::string& name, const Tn& g) -> int {     // g: the COMPLETE gradient of the output of node `name`
+        return gt ? v.tap_copy(gtaps, st, name, g) : 0;
+    };
+    struct RNode { const ResW* rw; Tn x, out; ResSave rs; std::string name; };
+    struct UNode { const ConvW* cw; Tn x, out; std::string name; };
     Tn x, q, h0;
     TRY(e.alloc(x, B, h_, w_, zc));
     if (!dry) TRY(launch_nchw_to_nhwc(st, z, zdt, B, c.latent_channels, h_ * w_, zc, x.p));
@@ -624,9 +631,12 @@ int gyre_vae_run_decode_vjp(gyre_vae& v, bool dry, hipStream_t st, const void* z
     std::vector<std::pair<int, size_t>> order;   // (0 = resnet, 1 = upsample), index
     std::vector<RNode> rn; std::vector<UNode> un;
     for (int i = 0; i < n; ++i) {
+        const std::string blk = gt ? "decoder.up_blocks." + std::to_string(i) : std::string();   // (names for a tapped call only)
+        int j = 0;
         for (auto& rw : v.d_up[i].res) {
             rn.push_back(RNode{&rw});
             RNode& nd = rn.back();
+            if (gt) nd.name = blk + ".resnets." + std::to_string(j++);
             nd.x = h;
             TRY(e.resnet(nd.x, nullptr, rw, nullptr, 0, 1e-6f, nd.out, &nd.rs));
             h = nd.out;
@@ -635,6 +645,7 @@ int gyre_vae_run_decode_vjp(gyre_vae& v, bool dry, hipStream_t st, const void* z
         if (v.d_up[i].has_resample) {
             un.push_back(UNode{&v.d_up[i].resample});
             UNode& nd = un.back();
+            if (gt) nd.name = blk + ".upsamplers.0";
             nd.x = h;
             TRY(e.conv3(nd.x, *nd.cw, 1, 1, 1, nullptr, 0, nullptr, nd.out));
             h = nd.out;
@@ -661,23 +672,30 @@ int gyre_vae_run_decode_vjp(gyre_vae& v, bool dry, hipStream_t st, const void* z
         if (order[k].first == 1) {
             UNode& nd = un[order[k].second];
             Tn g;
+            TRY(gtap(nd.name, dh));
             TRY(conv3_bwd(e, dh, *nd.cw, nd.x.C, 1, 1, 1, nd.x.H, nd.x.W, nullptr, g));
             e.free(dh); dh = g;
         } else {
+            TRY(gtap(rn[order[k].second].name, dh));
             TRY(res_bwd(rn[order[k].second], dh));
         }
     }
+    TRY(gtap("decoder.mid_block.resnets.1", dh));
     TRY(res_bwd(m1, dh));
+    TRY(gtap("decoder.mid_block.attentions.0", dh));
     {   // attention block: out = x + attn(GN(x))
         Tn dn, g;
         TRY(mha_bwd(e, an, false, nullptr, 0, 0, v.d_attn, asv, dh, dn));
         TRY(groupnorm_bwd(e, m0.out, nullptr, v.d_ag, v.d_ab, 1e-6f, 0, dn, &dh, g, nullptr));
         e.free(dn); e.free(dh); dh = g;
     }
+    TRY(gtap("decoder.mid_block.resnets.0", dh));
     TRY(res_bwd(m0, dh));
+    TRY(gtap("decoder.conv_in", dh));
     Tn dq;
     TRY(conv3_bwd(e, dh, v.d_in, zc, 1, 1, 0, h_, w_, nullptr, dq));
     e.free(dh);
+    TRY(gtap("post_quant_conv", dq));
     // post_quant_conv (1x1) adjoint straight to the caller's NCHW buffer
     Tn wt; const bf16_t* wtp;
     TRY(weight_t_linear(e, v.pq_w, zc, zc, wt, &wtp));

@@ -361,6 +361,21 @@ int gyre_unet_debug_tap(gyre_unet* h, const char* name, float* out_nchw_f32, siz
  * runs the same launches tapped or not.  Gradient taps are cleared by that sweep; a gyre_unet_forward* call, which drops a
  * pending forward state, clears them too. */
 int gyre_unet_debug_grad_tap(gyre_unet* h, const char* name, float* out_nchw_f32, size_t out_bytes);
+/* The same two taps on a VAE handle (one implementation: the name table and the copy are shared with the UNet's).  Forward NODES by
+ * their state-dict prefix: "encoder.conv_in", "encoder.down_blocks.<i>.resnets.<j>", "encoder.down_blocks.<i>.downsamplers.0",
+ * "encoder.mid_block.resnets.0" / ".attentions.0" (the attention block's output, after proj_attn and its residual) / ".resnets.1",
+ * "encoder.conv_out" (what quant_conv reads); "post_quant_conv", "decoder.conv_in", "decoder.mid_block.*",
+ * "decoder.up_blocks.<i>.resnets.<j>", "decoder.up_blocks.<i>.upsamplers.0".  There are no level names.
+ * Forward taps belong to the NEXT gyre_vae_encode or gyre_vae_decode call, whichever comes first: it writes the taps of its own
+ * half and drops all of them when it returns, so an encoder name set before a decode (or a decoder name before an encode) is
+ * accepted here, never written and gone afterwards.  gyre_vae_decode_vjp serves no forward tap and leaves them pending.
+ * Gradient taps exist for the decoder's nodes only ("post_quant_conv" and "decoder.*"; an encoder name is GYRE_ERR_INVALID here):
+ * the next gyre_vae_decode_vjp copies the COMPLETE gradient of the node's output, as its sweep holds it, and drops every gradient
+ * tap when it returns - also when it refuses the call (a tiling request is GYRE_ERR_UNSUPPORTED) and has written none.
+ * A buffer too small for the tensor is GYRE_ERR_INVALID in the call that would write it.  Nothing in the VAE is fused differently
+ * for a tap: a tapped call runs the launches of an untapped one plus one copy per tap, and writes the same output bits. */
+int gyre_vae_debug_tap(gyre_vae* h, const char* name, float* out_nchw_f32, size_t out_bytes);
+int gyre_vae_debug_grad_tap(gyre_vae* h, const char* name, float* out_nchw_f32, size_t out_bytes);
 
 /* Same, plus an optional additive term for the time embedding: temb_add[B, 4*block_out_channels[0]] (f32, dev) is
  * added to time_embedding(t) before it feeds the ResNet blocks.  This is how SDXL's `text_time` added conditioning

@@ -316,26 +316,39 @@ def _vae_attn(x: Tensor, sd: SD, p: str, groups: int) -> Tensor:
     return x + a.reshape(B, H, W, C).permute(0, 3, 1, 2)
 
 
-def _vae_mid(h: Tensor, sd: SD, p: str, groups: int) -> Tensor:
-    h = resnet_block(h, None, sd, p + ".resnets.0", groups, 1e-6)
-    h = _vae_attn(h, sd, p + ".attentions.0", groups)
-    return resnet_block(h, None, sd, p + ".resnets.1", groups, 1e-6)
+def _tapper(taps: Optional[dict]):
+    def node(name: str, y: Tensor) -> Tensor:
+        if taps is not None:
+            taps[name] = y
+        return y
+    return node
 
 
-def vae_encode_moments(sd: SD, cfg: VAERefConfig, image: Tensor) -> Tensor:
-    """image [B,3,H,W] in -1..1 -> moments [B,2*z,H/8,W/8] (mean | logvar)."""
+def _vae_mid(h: Tensor, sd: SD, p: str, groups: int, node=_tapper(None)) -> Tensor:
+    h = node(p + ".resnets.0", resnet_block(h, None, sd, p + ".resnets.0", groups, 1e-6))
+    h = node(p + ".attentions.0", _vae_attn(h, sd, p + ".attentions.0", groups))
+    return node(p + ".resnets.1", resnet_block(h, None, sd, p + ".resnets.1", groups, 1e-6))
+
+
+def vae_encode_moments(sd: SD, cfg: VAERefConfig, image: Tensor, taps: Optional[dict] = None) -> Tensor:
+    """image [B,3,H,W] in -1..1 -> moments [B,2*z,H/8,W/8] (mean | logvar).  ``taps`` (optional dict) receives the NODES under
+    their state-dict prefix - "encoder.conv_in", every resnet, every downsampler conv, the mid block's two resnets and its attention
+    block (after proj_attn and the residual), "encoder.conv_out" - the names of gyre_vae_debug_tap."""
     g = cfg.norm_num_groups
     boc = cfg.block_out_channels
-    h = _conv(image, sd, "encoder.conv_in")
+    node = _tapper(taps)
+    h = node("encoder.conv_in", _conv(image, sd, "encoder.conv_in"))
     for i in range(len(boc)):
         for j in range(cfg.layers_per_block):
-            h = resnet_block(h, None, sd, f"encoder.down_blocks.{i}.resnets.{j}", g, 1e-6)
+            p = f"encoder.down_blocks.{i}.resnets.{j}"
+            h = node(p, resnet_block(h, None, sd, p, g, 1e-6))
         if i < len(boc) - 1:
             h = F.pad(h, (0, 1, 0, 1))  # asymmetric pad, stride-2 conv pad 0 [3P Downsample2D]
-            h = _conv(h, sd, f"encoder.down_blocks.{i}.downsamplers.0.conv", stride=2, padding=0)
-    h = _vae_mid(h, sd, "encoder.mid_block", g)
+            p = f"encoder.down_blocks.{i}.downsamplers.0"
+            h = node(p, _conv(h, sd, p + ".conv", stride=2, padding=0))
+    h = _vae_mid(h, sd, "encoder.mid_block", g, node)
     h = F.silu(_gn(h, sd, "encoder.conv_norm_out", g, 1e-6))
-    h = _conv(h, sd, "encoder.conv_out")
+    h = node("encoder.conv_out", _conv(h, sd, "encoder.conv_out"))
     return _conv(h, sd, "quant_conv", padding=0)
 
 
@@ -348,18 +361,23 @@ def vae_posterior_sample(moments: Tensor, generator: Optional[torch.Generator]) 
     return mean + std * noise.to(mean.device)
 
 
-def vae_decode(sd: SD, cfg: VAERefConfig, z: Tensor) -> Tensor:
-    """latents [B,4,h,w] (already divided by the scaling factor) -> image [B,3,8h,8w]."""
+def vae_decode(sd: SD, cfg: VAERefConfig, z: Tensor, taps: Optional[dict] = None) -> Tensor:
+    """latents [B,4,h,w] (already divided by the scaling factor) -> image [B,3,8h,8w].  ``taps``: as in vae_encode_moments -
+    "post_quant_conv", "decoder.conv_in", the mid block's nodes, every up resnet and every upsampler conv; the tensors are the ones of
+    the graph, so a gradient reference calls retain_grad() on them before it differentiates."""
     g = cfg.norm_num_groups
     boc = list(reversed(cfg.block_out_channels))
-    h = _conv(z, sd, "post_quant_conv", padding=0)
-    h = _conv(h, sd, "decoder.conv_in")
-    h = _vae_mid(h, sd, "decoder.mid_block", g)
+    node = _tapper(taps)
+    h = node("post_quant_conv", _conv(z, sd, "post_quant_conv", padding=0))
+    h = node("decoder.conv_in", _conv(h, sd, "decoder.conv_in"))
+    h = _vae_mid(h, sd, "decoder.mid_block", g, node)
     for i in range(len(boc)):
         for j in range(cfg.layers_per_block + 1):
-            h = resnet_block(h, None, sd, f"decoder.up_blocks.{i}.resnets.{j}", g, 1e-6)
+            p = f"decoder.up_blocks.{i}.resnets.{j}"
+            h = node(p, resnet_block(h, None, sd, p, g, 1e-6))
         if i < len(boc) - 1:
             h = F.interpolate(h, scale_factor=2.0, mode="nearest")
-            h = _conv(h, sd, f"decoder.up_blocks.{i}.upsamplers.0.conv")
+            p = f"decoder.up_blocks.{i}.upsamplers.0"
+            h = node(p, _conv(h, sd, p + ".conv"))
     h = F.silu(_gn(h, sd, "decoder.conv_norm_out", g, 1e-6))
     return _conv(h, sd, "decoder.conv_out")
