@@ -1,6 +1,6 @@
-"""End-to-end upscaler run on random-init weights: a 4-channel image through GyreUpscalerPipeline over the native RRDBNet or SwinIR.
+"""End-to-end upscaler run on random-init weights: a 4-channel image through GyreUpscalerPipeline over the native RRDBNet, SwinIR or HAT.
 
-    python examples/upscale.py [--network esrgan|swinir|swinir-l] [--size 512] [--blocks 23] [--dtype f16] [--out upscaled.png]
+    python examples/upscale.py [--network esrgan|swinir|swinir-l|hat|hat-l] [--size 512] [--blocks 23] [--dtype f16] [--out upscaled.png]
 
 Synthetic weights make no picture worth looking at; the run shows the call sequence an engine makes (loader-shaped model, pipeline
 call, 9 stacked tiles for 512 x 512) and prints its time."""
@@ -13,10 +13,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from gyre_amd import config as gcfg, weights
-from gyre_amd.upscaler import GyreHipRRDBNet, GyreHipSwinIR, GyreUpscalerPipeline
+from gyre_amd.upscaler import GyreHipHAT, GyreHipRRDBNet, GyreHipSwinIR, GyreUpscalerPipeline
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--network", choices=("esrgan", "swinir", "swinir-l"), default="esrgan")
+ap.add_argument("--network", choices=("esrgan", "swinir", "swinir-l", "hat", "hat-l"), default="esrgan")
 ap.add_argument("--size", type=int, default=512)
 ap.add_argument("--blocks", type=int, default=23, help="RRDBs of the esrgan network")
 ap.add_argument("--dtype", choices=("bf16", "f16"), default="f16")
@@ -27,6 +27,11 @@ if a.network == "esrgan":
     cfg = gcfg.rrdb_config(num_block=a.blocks)
     net = GyreHipRRDBNet(cfg)
     net.load_state_dict(weights.synthetic_state_dict(weights.rrdb_param_shapes(cfg)))
+elif a.network in ("hat", "hat-l"):
+    cfg = gcfg.hat_config(**gcfg.HAT_DEFAULTS[a.network])
+    net = GyreHipHAT(cfg)
+    shapes = {k: v for k, v in weights.hat_param_shapes(cfg).items() if not weights.hat_is_buffer(k)}
+    net.load_state_dict(weights.synthetic_state_dict(shapes), strict=False)      # (the buffers keep their zeros: they are never read)
 else:
     cfg = gcfg.swinir_config(**gcfg.SWINIR_DEFAULTS[a.network])
     net = GyreHipSwinIR(cfg)

@@ -89,6 +89,14 @@ class SwinIRCfg(C.Structure):
                 ("img_range", C.c_float), ("resi_3conv", C.c_int32)]
 
 
+class HATCfg(C.Structure):
+    """gyre_hat_cfg (include/gyre_hip.h)."""
+    _fields_ = [("in_chans", C.c_int32), ("embed_dim", C.c_int32), ("num_layers", C.c_int32), ("depths", C.c_int32 * 16),
+                ("num_heads", C.c_int32 * 16), ("window_size", C.c_int32), ("mlp_hidden", C.c_int32), ("upscale", C.c_int32),
+                ("img_range", C.c_float), ("compress_ratio", C.c_int32), ("squeeze_factor", C.c_int32), ("conv_scale", C.c_float),
+                ("overlap_ratio", C.c_float)]
+
+
 class RdbEpilogue(C.Structure):
     """gyre_rdb_epilogue (include/gyre_hip.h): v = alpha (acc + bias); leaky-relu(0.2) if act; + beta1 r1; + beta2 r2."""
     _fields_ = [("bias", C.c_void_p), ("alpha", C.c_float), ("act", C.c_int32), ("r1", C.c_void_p), ("ldr1", C.c_int32),
@@ -206,6 +214,14 @@ _SIGS = {
     "gyre_swinir_finalize": (_i, [_vp, _vp]),
     "gyre_swinir_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "gyre_swinir_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
+    "gyre_hat_create": (_i, [C.POINTER(HATCfg), _i, C.POINTER(_vp)]),
+    "gyre_hat_destroy": (None, [_vp]),
+    "gyre_hat_num_params": (_i, [_vp]),
+    "gyre_hat_param_key": (C.c_char_p, [_vp, _i]),
+    "gyre_hat_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
+    "gyre_hat_finalize": (_i, [_vp, _vp]),
+    "gyre_hat_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "gyre_hat_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
     "gyre_ctrl_create": (_i, [C.POINTER(CtrlCfg), _i, C.POINTER(_vp)]),
     "gyre_ctrl_destroy": (None, [_vp]),
     "gyre_ctrl_num_params": (_i, [_vp]),
@@ -300,6 +316,12 @@ _SIGS = {
     "gyre_op_swin_act": (_i, [_vp, _vp, _sz, _i, _f]),
     "gyre_op_swin_entry": (_i, [_vp, _vp, _i, _i, _sz, _vp, _f, _vp]),
     "gyre_op_swin_exit": (_i, [_vp, _vp, _i, _i, _sz, _vp, _f, _vp, _i]),
+    "gyre_op_hat_attn": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i]),
+    "gyre_op_chan_pool_workspace": (_sz, [_i, _sz, _i]),
+    "gyre_op_chan_pool": (_i, [_vp, _vp, _i, _i, _sz, _i, _vp, _vp]),
+    "gyre_op_chan_gate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i]),
+    "gyre_op_scale_add": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _sz, _i]),
+    "gyre_op_pixel_shuffle2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_ctrl_emit": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _i]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)

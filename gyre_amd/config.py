@@ -287,3 +287,78 @@ def tiny_swinir(**kw) -> SwinIRConfig:
     """Two RSTBs of two blocks (plain and shifted windows, both residual levels) at embed 60 / 2 heads, x4, built for 16 x 16 images."""
     return swinir_config(**{**dict(upscale=4, img_size=16, window_size=8, depths=[2, 2], embed_dim=60, num_heads=[2, 2], mlp_ratio=2,
                                    upsampler="nearest+conv", resi_connection="1conv"), **kw})
+
+
+class HATConfig(dict):
+    """Configuration of a HAT upscaler - the keyword arguments of the reference's ``HAT`` constructor
+    (gyre/pipeline/upscalers/models/hat_arch.py:743-769): a mapping that also reads as attributes."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+# the reference's default configurations (gyre/pipeline/upscalers/upscaler_loader.py DEFAULT_CONFIGS "hat" / "hat-l")
+HAT_DEFAULTS = {
+    "hat": dict(upscale=4, in_chans=3, img_size=64, window_size=16, compress_ratio=3, squeeze_factor=30, conv_scale=0.01,
+                overlap_ratio=0.5, img_range=1.0, depths=[6, 6, 6, 6, 6, 6], embed_dim=180, num_heads=[6, 6, 6, 6, 6, 6], mlp_ratio=2,
+                upsampler="pixelshuffle", resi_connection="1conv"),
+    "hat-l": dict(upscale=4, in_chans=3, img_size=64, window_size=16, compress_ratio=3, squeeze_factor=30, conv_scale=0.01,
+                  overlap_ratio=0.5, img_range=1.0, depths=[6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6], embed_dim=180,
+                  num_heads=[6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6], mlp_ratio=2, upsampler="pixelshuffle", resi_connection="1conv")}
+
+# HAT.__init__'s own defaults: what a key the caller leaves out means
+_HAT_CTOR = dict(img_size=64, patch_size=1, in_chans=3, embed_dim=96, depths=(6, 6, 6, 6), num_heads=(6, 6, 6, 6), window_size=7,
+                 compress_ratio=3, squeeze_factor=30, conv_scale=0.01, overlap_ratio=0.5, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
+                 drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.1, norm_layer=None, ape=False, patch_norm=True,
+                 use_checkpoint=False, upscale=2, img_range=1.0, upsampler="", resi_connection="1conv")
+
+
+def hat_config(**kw) -> HATConfig:
+    """The constructor's defaults under ``kw``, refused (NotImplementedError) outside what the native path builds: window 16,
+    overlap_ratio 0.5, compress_ratio 3, squeeze_factor 30, embed_dim = 30 * heads with one head count (at most 8) for all layers, an
+    MLP width that is a multiple of 8, "pixelshuffle" with upscale 2 or 4, "1conv", ape=False, patch_norm=True, qkv_bias=True,
+    in_chans=3.  A key that is not a constructor argument is refused too - the reference swallows it in ``**kwargs``; here a folder of
+    another model family fails at its configuration instead of at load_state_dict."""
+    unknown = sorted(set(kw) - set(_HAT_CTOR))
+    if unknown:
+        raise NotImplementedError(f"HAT: {unknown} are not arguments of the HAT constructor (a configuration of another model family?)")
+    cfg = HATConfig(**{**_HAT_CTOR, **kw})
+    cfg["depths"], cfg["num_heads"] = [int(d) for d in cfg["depths"]], [int(h) for h in cfg["num_heads"]]
+
+    def refuse(why):
+        raise NotImplementedError(f"HAT: {why} is outside the native path")
+
+    if cfg["window_size"] != 16:
+        refuse(f"window_size {cfg['window_size']} (16 is built)")
+    if cfg["overlap_ratio"] != 0.5 or cfg["compress_ratio"] != 3 or cfg["squeeze_factor"] != 30:
+        refuse("an overlap_ratio other than 0.5, a compress_ratio other than 3 or a squeeze_factor other than 30")
+    if cfg["patch_size"] != 1 or cfg["in_chans"] != 3:
+        refuse("patch_size other than 1 or in_chans other than 3")
+    if cfg["upsampler"] != "pixelshuffle" or cfg["upscale"] not in (2, 4):
+        refuse(f"upsampler {cfg['upsampler']!r} at upscale {cfg['upscale']} (pixelshuffle at 2 or 4 is built)")
+    if cfg["resi_connection"] != "1conv":
+        refuse(f"resi_connection {cfg['resi_connection']!r}")
+    if cfg["ape"] or not cfg["patch_norm"] or not cfg["qkv_bias"] or cfg["qk_scale"] is not None:
+        refuse("ape=True, patch_norm=False, qkv_bias=False or a qk_scale")
+    if cfg["norm_layer"] is not None and cfg["norm_layer"] is not __import__("torch").nn.LayerNorm:
+        refuse("a norm_layer other than LayerNorm")
+    heads, depths = cfg["num_heads"], cfg["depths"]
+    if not depths or len(depths) != len(heads) or len(depths) > 16 or min(depths) < 1:
+        refuse(f"depths {depths} with num_heads {heads} (1 to 16 layers, one head count per layer)")
+    if len(set(heads)) != 1 or not 1 <= heads[0] <= 8 or cfg["embed_dim"] != 30 * heads[0]:
+        refuse(f"embed_dim {cfg['embed_dim']} with num_heads {heads} (embed_dim = 30 * heads, the same 1 to 8 heads in every layer)")
+    hidden = int(cfg["embed_dim"] * cfg["mlp_ratio"])
+    if hidden < 8 or hidden % 8:
+        refuse(f"an MLP width of {hidden} (multiples of 8 are built)")
+    if not float(cfg["img_range"]) > 0:
+        raise ValueError("HAT: img_range must be positive")
+    return cfg
+
+
+def tiny_hat(**kw) -> HATConfig:
+    """Two RHAGs of two HABs (plain and shifted windows) and their OCABs at embed 60 / 2 heads, x4."""
+    return hat_config(**{**dict(upscale=4, window_size=16, depths=[2, 2], embed_dim=60, num_heads=[2, 2], mlp_ratio=2,
+                                upsampler="pixelshuffle", resi_connection="1conv"), **kw})

@@ -201,6 +201,29 @@ int launch_swin_act(hipStream_t st, bf16_t* x, size_t n, int mode, float slope);
 int launch_swin_entry(hipStream_t st, const void* x, int dtype, int B, size_t HW, const float* mean3, float range, bf16_t* y);
 int launch_swin_exit(hipStream_t st, const bf16_t* x, int ldx, int B, size_t HW, const float* mean3, float range, void* y, int dtype);
 
+// ---- HAT upscaler kernels (kernels_hat.hip) --------------------------------------
+// Window attention over 16 x 16 windows, head dim 30 stored as 32, the qkv / o layouts of launch_win_attn (arithmetic: header of
+// kernels_hat.hip).  table: the relative-position table itself, fp32 [961][heads] (SA) or [1521][heads] (OCA); nothing is expanded.
+//   HAT_ATTN_SA   256 queries x 256 keys of one window under shift 0 or 8 (always honoured, also on one window per side)
+//   HAT_ATTN_OCA  256 queries x the 24 x 24 keys around the window, zero k / v outside the image; shift must be 0
+// GYRE_ERR_UNSUPPORTED / GYRE_ERR_INVALID outside the domain, nothing written.
+enum { HAT_ATTN_SA = 0, HAT_ATTN_OCA = 1 };
+int hat_attn_check(const bf16_t* qkv, int ld_qkv, const bf16_t* o, int ld_o, const float* table, int mode, int B, int H, int W, int heads,
+                   int shift);
+int launch_hat_attn(hipStream_t st, const bf16_t* qkv, int ld_qkv, bf16_t* o, int ld_o, const float* table, int mode, int B, int H, int W,
+                    int heads, int shift);
+// pool[b][c] = mean over HW of x[b][.][c], c < C <= 256, fp32, in a fixed two-stage order (64-row chunks, then the chunks in order):
+// a sample's result does not depend on B.  partial: chan_pool_partial_floats(B, HW, C) floats of scratch
+size_t chan_pool_partial_floats(int B, size_t HW, int C);
+int launch_chan_pool(hipStream_t st, const bf16_t* x, int ld, int B, size_t HW, int C, float* partial, float* pool);
+// s[b][c] = scale * sigmoid(w2[c] . relu(w1 pool[b] + b1) + b2[c]) for c < C, 0 for C <= c < ld_s; w1 [Cs][C], w2 [C][Cs] fp32, Cs <= 8
+int launch_chan_gate(hipStream_t st, const float* pool, int B, int C, int Cs, const float* w1, const float* b1, const float* w2,
+                     const float* b2, float scale, float* s, int ld_s);
+// y[b][p][c] += c2[b][p][c] * s[b][c] over c < Cn (a multiple of 8, <= ld_s), one fma and one rounding per element
+int launch_scale_add(hipStream_t st, bf16_t* y, int ldy, const bf16_t* c2, int ldc, const float* s, int ld_s, int B, size_t HW, int Cn);
+// PixelShuffle(2) on NHWC: out[b][2 y + i][2 x + j][c] = x[b][y][x][4 c + 2 i + j], c < Co (a multiple of 8); bit copies
+int launch_pixel_shuffle2(hipStream_t st, const bf16_t* x, int ld_x, int B, int H, int W, int Co, bf16_t* out, int ld_out);
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

@@ -1,4 +1,4 @@
-"""The ESRGAN and SwinIR families of upscaler engines on the native path: model shells, loader and pipeline.
+"""The ESRGAN, SwinIR and HAT families of upscaler engines on the native path: model shells, loader and pipeline.
 
 The reference serves ``task: upscaler`` engines (gyre/config/engines/upscaler.yaml) through three pieces whose behaviour is
 restated here:
@@ -11,8 +11,9 @@ restated here:
 The model is BasicSR's ``RRDBNet`` (``esrgan``, ``esrgan_old``, ``realesrgan``, ``realesrgan_6B``) or the reference's ``RRDBNet_Plus``
 (``esrgan_plus``); its parameters carry BasicSR's state-dict names and all compute happens in the HIP library (gyre_rrdb_forward) -
 there is no PyTorch fallback.  The second family is the reference's vendored ``SwinIR`` (``swinir``, ``swinir_l``;
-gyre/pipeline/upscalers/models/network_swinir.py) in its "nearest+conv" form, on gyre_swinir_forward.  HAT is a separate model family and
-is not built, nor are SwinIR's pixel-shuffle and denoising forms.
+gyre/pipeline/upscalers/models/network_swinir.py) in its "nearest+conv" form, on gyre_swinir_forward; SwinIR's pixel-shuffle and
+denoising forms are not built.  The third is the reference's vendored ``HAT`` (``hat``, ``hat_l``; .../models/hat_arch.py) in its
+"pixelshuffle" / "1conv" form at window 16, on gyre_hat_forward.
 
 One native liberty: the tiles of a request go through the module as stacked batches (up to 16 tiles each, so the 9 tiles of a
 512 x 512 request are ONE call) and are then blended in the reference's order.  The module is batch-independent (a sample's result does not depend on the batch it runs in), so the result is the same; a
@@ -31,9 +32,10 @@ import numpy as np
 import torch
 
 from . import _lib, images
-from .config import RRDB_DEFAULTS, SWINIR_DEFAULTS, RRDBConfig, SwinIRConfig, rrdb_config, swinir_config
+from .config import (HAT_DEFAULTS, RRDB_DEFAULTS, SWINIR_DEFAULTS, HATConfig, RRDBConfig, SwinIRConfig, hat_config, rrdb_config,
+                     swinir_config)
 from .modules import _NativeModule, _build_tree
-from .weights import rrdb_param_shapes, swinir_is_buffer, swinir_param_shapes
+from .weights import hat_is_buffer, hat_param_shapes, rrdb_param_shapes, swinir_is_buffer, swinir_param_shapes
 
 PATHS = {"auto": 0, "generic": 1, "fused": 2}
 _UNSHUFFLE = {4: 1, 2: 2, 1: 4}          # model scale -> pixel-unshuffle factor in front of conv_first
@@ -200,12 +202,83 @@ class GyreHipSwinIR(_NativeModule):
         return out[:, :, :H * c.upscale, :W * c.upscale] if ph or pw else out
 
 
+class GyreHipHAT(_NativeModule):
+    """Drop-in for the reference's ``HAT`` with upsampler "pixelshuffle": ``forward(x) -> tensor``, NCHW in and out.  The state dict
+    carries the reference's names, its two global buffers included (``relative_position_index_SA`` / ``_OCA``), so a real checkpoint
+    loads strictly; the buffers' values are never read - the kernel computes both indices and the mask from the window position.
+    Like the reference, the model has no padding: H and W must be multiples of the window size 16 (``tile()`` cuts multiples of 32)."""
+
+    _kind = "hat"
+
+    def __init__(self, config: Optional[dict] = None, **kw):
+        super().__init__()
+        cfg = dict(config or {})
+        cfg.update(kw)
+        self.config: HATConfig = hat_config(**cfg)
+        self._scale = self.config.upscale
+        self._window_size = self.config.window_size
+        shapes = hat_param_shapes(self.config)
+        _build_tree(self, {k: v for k, v in shapes.items() if not hat_is_buffer(k)})
+        for key, shape in shapes.items():
+            if hat_is_buffer(key):
+                self.register_buffer(key, torch.zeros(shape, dtype=torch.long))
+
+    def _shapes(self):
+        return hat_param_shapes(self.config)
+
+    def _c_cfg(self):
+        c, cfg = self.config, _lib.HATCfg()
+        cfg.in_chans, cfg.embed_dim, cfg.num_layers = c.in_chans, c.embed_dim, len(c.depths)
+        for i, (d, h) in enumerate(zip(c.depths, c.num_heads)):
+            cfg.depths[i], cfg.num_heads[i] = d, h
+        cfg.window_size, cfg.mlp_hidden, cfg.upscale = c.window_size, int(c.embed_dim * c.mlp_ratio), c.upscale
+        cfg.img_range, cfg.compress_ratio, cfg.squeeze_factor = float(c.img_range), c.compress_ratio, c.squeeze_factor
+        cfg.conv_scale, cfg.overlap_ratio = float(c.conv_scale), float(c.overlap_ratio)
+        return cfg
+
+    def out_shape(self, shape):
+        B, _, H, W = shape
+        return (B, self.config.in_chans, H * self.config.upscale, W * self.config.upscale)
+
+    def workspace_bytes(self, B: int, H: int, W: int, device) -> int:
+        h = self._sync(torch.device(device))
+        with torch.cuda.device(device):
+            return int(self._L().gyre_hat_workspace_bytes(C.c_void_p(h), B, H, W))
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        c = self.config
+        if x.ndim != 4 or x.shape[1] != c.in_chans:
+            raise ValueError(f"expected an image [B,{c.in_chans},H,W], got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        if H < 16 or W < 16 or H % 16 or W % 16:
+            raise ValueError(f"HAT takes images whose height and width are multiples of the window size 16, got {H} x {W}")
+        dev = x.device
+        h = self._sync(dev)
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            x = x.to(torch.float32)
+        x = x.contiguous()
+        _lib.require_gpu_tensor(x, "image")
+        L = self._L()
+        with torch.cuda.device(dev):
+            need = L.gyre_hat_workspace_bytes(C.c_void_p(h), B, H, W)
+            if need == 0:
+                _lib.check(-1, L)
+            ws = self._workspace(need, dev)
+            wp = (ws.data_ptr() + 255) & ~255
+            out = torch.empty(self.out_shape(x.shape), dtype=self.dtype, device=dev)
+            _lib.check(L.gyre_hat_forward(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()),
+                                          _lib.dtype_code(x), B, H, W, C.c_void_p(wp), need, C.c_void_p(out.data_ptr()),
+                                          _lib.dtype_code(out)), L)
+        return out
+
+
 # ---- loader ----------------------------------------------------------------------------------------------------------------------------
 CONFIG_PATTERN = ["*.yaml"]
 MODELS_PATTERN = ["*.safetensors", "*.pt", "*.pth"]
 # default configuration per name, the values the reference uses for the family (the published inference settings of ESRGAN and
-# Real-ESRGAN, and of SwinIR's real-world x4 models); HAT names are refused
-DEFAULT_CONFIGS = {k: dict(v) for k, v in {**RRDB_DEFAULTS, **SWINIR_DEFAULTS}.items()}
+# Real-ESRGAN, of SwinIR's real-world x4 models and of HAT / HAT-L x4)
+DEFAULT_CONFIGS = {k: dict(v) for k, v in {**RRDB_DEFAULTS, **SWINIR_DEFAULTS, **HAT_DEFAULTS}.items()}
 
 # Old-format ESRGAN checkpoints (the original xinntao/ESRGAN release) name the same tensors by their position in an nn.Sequential:
 # the trunk convolutions sit at fixed indices, the RRDBs under model.1.sub.{i}, the convolution that closes the trunk right behind
@@ -287,7 +360,7 @@ def _merged_config(folder, network, config, allow_patterns, ignore_patterns) -> 
 
 
 class GyreHipUpscalerLoader:
-    """The reference ``UpscalerLoader``'s surface for the ESRGAN and SwinIR families: ``load`` and one classmethod per engine ``class:`` name
+    """The reference ``UpscalerLoader``'s surface for the ESRGAN, SwinIR and HAT families: ``load`` and one classmethod per engine ``class:`` name
     (ENTRY_POINTS below).  The model's ``_scale`` and ``_window_size`` - what the pipeline reads - come from the model itself."""
 
     convert_old_esrgan = staticmethod(convert_old_esrgan)
@@ -295,14 +368,15 @@ class GyreHipUpscalerLoader:
     @classmethod
     def load(cls, path, torch_dtype="auto", low_cpu_mem_usage=False, allow_patterns=None, ignore_patterns=None,
              network="esrgan", converter=None, **config):
-        if network == "hat":
-            raise NotImplementedError(f"upscaler network {network!r} is a separate model family outside the native path")
-        if network not in ("esrgan", "esrgan-plus", "swinir"):
+        if network not in ("esrgan", "esrgan-plus", "swinir", "hat"):
             raise ValueError(f"Unknown upscaler network kind {network}")
         if converter not in (None, "esrgan-old"):
             raise ValueError(f"Unknown converter {converter}")
         merged = _merged_config(path, network, config, allow_patterns, ignore_patterns)
-        model = GyreHipSwinIR(**merged) if network == "swinir" else GyreHipRRDBNet(plus=network == "esrgan-plus", **merged)
+        if network == "hat":
+            model = GyreHipHAT(**merged)
+        else:
+            model = GyreHipSwinIR(**merged) if network == "swinir" else GyreHipRRDBNet(plus=network == "esrgan-plus", **merged)
         weights_file = _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
         tensors = _read_state_dict(weights_file)
         tensors = tensors.get("params_ema", tensors)               # Real-ESRGAN training files keep the EMA weights under this key
@@ -313,15 +387,14 @@ class GyreHipUpscalerLoader:
         return (model if torch_dtype == "auto" else model.to(torch_dtype)).eval()
 
 
-# engine ``class:`` name -> the arguments of load() it fixes.  The HAT names exist so that an engines.yaml that selects them gets
-# load()'s NotImplementedError instead of an AttributeError.
+# engine ``class:`` name -> the arguments of load() it fixes
 ENTRY_POINTS = {"esrgan": dict(network="esrgan"),
                 "esrgan_old": dict(network="esrgan", converter="esrgan-old"),
                 "esrgan_plus": dict(network="esrgan-plus", converter="esrgan-old"),
                 "realesrgan": dict(network="esrgan"),
                 "realesrgan_6B": dict(network="esrgan", config="esrgan-6B"),
                 "swinir": dict(network="swinir"), "swinir_l": dict(network="swinir", config="swinir-l"),
-                "hat": dict(network="hat"), "hat_l": dict(network="hat")}
+                "hat": dict(network="hat"), "hat_l": dict(network="hat", config="hat-l")}
 
 
 def _entry_point(fixed):

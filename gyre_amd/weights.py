@@ -371,3 +371,69 @@ def swinir_param_shapes(cfg) -> Shapes:
 
 def swinir_is_buffer(key: str) -> bool:
     return key.endswith(SWINIR_BUFFERS)
+
+
+HAT_BUFFERS = ("relative_position_index_SA", "relative_position_index_OCA")      # state-dict entries that are buffers: loaded, never read
+
+
+def hat_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``HAT`` (gyre/pipeline/upscalers/models/hat_arch.py) with upsampler
+    "pixelshuffle" and "1conv", in state_dict() order, its two global index buffers (HAT_BUFFERS) first; cfg: a mapping as
+    gyre_amd.config.tiny_hat returns."""
+    s: Shapes = OrderedDict()
+    C, heads, upscale = cfg["embed_dim"], cfg["num_heads"], cfg["upscale"]
+    hidden = int(C * cfg["mlp_ratio"])
+    mid, sq = C // cfg["compress_ratio"], C // cfg["squeeze_factor"]
+
+    def conv(p, o, i, k=3):
+        s[p + ".weight"] = (o, i, k, k)
+        s[p + ".bias"] = (o,)
+
+    def lin(p, o, i):
+        s[p + ".weight"] = (o, i)
+        s[p + ".bias"] = (o,)
+
+    def norm(p):
+        s[p + ".weight"] = (C,)
+        s[p + ".bias"] = (C,)
+
+    def mlp(p):
+        norm(p + ".norm2")
+        lin(p + ".mlp.fc1", hidden, C)
+        lin(p + ".mlp.fc2", C, hidden)
+
+    s["relative_position_index_SA"] = (256, 256)
+    s["relative_position_index_OCA"] = (256, 576)
+    conv("conv_first", C, cfg["in_chans"])
+    norm("patch_embed.norm")
+    for i, depth in enumerate(cfg["depths"]):
+        for j in range(depth):
+            p = f"layers.{i}.residual_group.blocks.{j}"
+            norm(p + ".norm1")
+            s[p + ".attn.relative_position_bias_table"] = (961, heads[i])
+            lin(p + ".attn.qkv", 3 * C, C)
+            lin(p + ".attn.proj", C, C)
+            conv(p + ".conv_block.cab.0", mid, C)
+            conv(p + ".conv_block.cab.2", C, mid)
+            conv(p + ".conv_block.cab.3.attention.1", sq, C, 1)
+            conv(p + ".conv_block.cab.3.attention.3", C, sq, 1)
+            mlp(p)
+        p = f"layers.{i}.residual_group.overlap_attn"
+        s[p + ".relative_position_bias_table"] = (1521, heads[i])
+        norm(p + ".norm1")
+        lin(p + ".qkv", 3 * C, C)
+        lin(p + ".proj", C, C)
+        mlp(p)
+        conv(f"layers.{i}.conv", C, C)
+    norm("norm")
+    conv("conv_after_body", C, C)
+    conv("conv_before_upsample.0", 64, C)
+    conv("upsample.0", 256, 64)
+    if upscale == 4:
+        conv("upsample.2", 256, 64)
+    conv("conv_last", cfg["in_chans"], 64)
+    return s
+
+
+def hat_is_buffer(key: str) -> bool:
+    return key in HAT_BUFFERS

@@ -169,8 +169,28 @@ typedef struct {
     int32_t resi_3conv;              /* 0 = "1conv", 1 = "3conv" */
 } gyre_swinir_cfg;
 
+/* HAT upscaler (the reference's gyre/pipeline/upscalers/models/hat_arch.py, upsampler "pixelshuffle", resi_connection "1conv").  Built:
+ * window 16, overlap_ratio 0.5, compress_ratio 3, squeeze_factor 30, embed_dim = 30 * heads with the same head count (<= 8) in every
+ * layer, mlp_hidden % 8 == 0, upscale 2 or 4, in_chans 3. */
+typedef struct {
+    int32_t in_chans;                /* 3 */
+    int32_t embed_dim;               /* 180 */
+    int32_t num_layers;              /* RHAGs: 6 (hat) / 12 (hat-l) (<= 16) */
+    int32_t depths[16];              /* HABs per RHAG: 6 */
+    int32_t num_heads[16];           /* 6 */
+    int32_t window_size;             /* 16 (the only one built) */
+    int32_t mlp_hidden;              /* int(embed_dim * mlp_ratio): 360 */
+    int32_t upscale;                 /* 4 or 2 */
+    float img_range;                 /* 1.0 */
+    int32_t compress_ratio;          /* 3 */
+    int32_t squeeze_factor;          /* 30 */
+    float conv_scale;                /* 0.01 */
+    float overlap_ratio;             /* 0.5 */
+} gyre_hat_cfg;
+
 typedef struct gyre_unet gyre_unet;
 typedef struct gyre_swinir gyre_swinir;
+typedef struct gyre_hat gyre_hat;
 typedef struct gyre_vae gyre_vae;
 typedef struct gyre_t2i gyre_t2i;
 typedef struct gyre_ctrl gyre_ctrl;
@@ -455,6 +475,26 @@ size_t gyre_swinir_workspace_bytes(gyre_swinir* h, int B, int H, int W);
  * side.  A sample's result does not depend on the batch it runs in. */
 int gyre_swinir_forward(gyre_swinir* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                         void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
+
+/* ---- HAT upscaler ----------------------------------------------------------- */
+/* Weight keys are the reference's state-dict names: conv_first, patch_embed.norm, layers.{i}.residual_group.blocks.{j}.{norm1,
+ * attn.relative_position_bias_table, attn.qkv, attn.proj, conv_block.cab.0, conv_block.cab.2, conv_block.cab.3.attention.1,
+ * conv_block.cab.3.attention.3, norm2, mlp.fc1, mlp.fc2}, layers.{i}.residual_group.overlap_attn.{norm1, qkv,
+ * relative_position_bias_table, proj, norm2, mlp.fc1, mlp.fc2}, layers.{i}.conv, norm, conv_after_body, conv_before_upsample.0,
+ * upsample.0, upsample.2 (x4 only), conv_last.  Same weight store, workspace and dry-run sizing rules as the other handles.  A
+ * configuration outside the built list (gyre_hat_cfg): GYRE_ERR_UNSUPPORTED at create. */
+int gyre_hat_create(const gyre_hat_cfg* cfg, int device, gyre_hat** out);
+void gyre_hat_destroy(gyre_hat* h);
+int gyre_hat_num_params(const gyre_hat* h);
+const char* gyre_hat_param_key(const gyre_hat* h, int i);
+int gyre_hat_set_weight(gyre_hat* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_hat_finalize(gyre_hat* h, void* stream);
+size_t gyre_hat_workspace_bytes(gyre_hat* h, int B, int H, int W);
+/* out[B, 3, H * upscale, W * upscale] = HAT(image[B, 3, H, W]).  H and W must be positive multiples of 16 (GYRE_ERR_INVALID otherwise:
+ * the reference has no padding either).  HABs with an odd index use the shift 8, also on an image of one window per side.  A sample's
+ * result does not depend on the batch it runs in. */
+int gyre_hat_forward(gyre_hat* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                     void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -877,6 +917,22 @@ int gyre_op_ln_live(void* stream, const void* x, int ldx, size_t M, int C, const
 int gyre_op_swin_act(void* stream, void* x, size_t n, int mode, float slope);
 int gyre_op_swin_entry(void* stream, const void* x, int dtype, int B, size_t HW, const float* mean3, float range, void* y);
 int gyre_op_swin_exit(void* stream, const void* x, int ldx, int B, size_t HW, const float* mean3, float range, void* y, int dtype);
+/* The kernels of the HAT upscaler (kernels_hat.hip).  hat_attn: attention over 16 x 16 windows, head dim 30 stored as 32, qkv / o laid
+ * out as for win_attn; table = the relative-position table itself, fp32 [961][heads] (mode 0, self-attention: 256 keys of the window
+ * under shift 0 or 8, mask from the window position) or [1521][heads] (mode 1, overlapping cross-attention: the 24 x 24 keys around the
+ * window, zero k / v outside the image, the reference's index modulo 1521; shift must be 0).  H and W multiples of 16, 1 to 8 heads.
+ * chan_pool: pool[b][c] = mean over HW of x[b][.][c] (c < C <= 256) in a fixed order; partial = gyre_op_chan_pool_workspace bytes.
+ * chan_gate: s[b][c] = scale * sigmoid(w2[c] . relu(w1 pool[b] + b1) + b2[c]), zeros in [C, ld_s); w1 [Cs][C], w2 [C][Cs], Cs <= 8.
+ * scale_add: y[b][p][c] += c2[b][p][c] * s[b][c] for c < Cn (a multiple of 8).  pixel_shuffle2: out[b][2 y + i][2 x + j][c] =
+ * x[b][y][x][4 c + 2 i + j] for c < Co (a multiple of 8), NHWC, exact.  GYRE_ERR_UNSUPPORTED / GYRE_ERR_INVALID outside the domain. */
+int gyre_op_hat_attn(void* stream, const void* qkv, int ld_qkv, void* o, int ld_o, const float* table, int mode, int B, int H, int W,
+                     int heads, int shift);
+size_t gyre_op_chan_pool_workspace(int B, size_t HW, int C);
+int gyre_op_chan_pool(void* stream, const void* x, int ld, int B, size_t HW, int C, float* partial, float* pool);
+int gyre_op_chan_gate(void* stream, const float* pool, int B, int C, int Cs, const float* w1, const float* b1, const float* w2,
+                      const float* b2, float scale, float* s, int ld_s);
+int gyre_op_scale_add(void* stream, void* y, int ldy, const void* c2, int ldc, const float* s, int ld_s, int B, size_t HW, int Cn);
+int gyre_op_pixel_shuffle2(void* stream, const void* x, int ld_x, int B, int H, int W, int Co, void* out, int ld_out);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
