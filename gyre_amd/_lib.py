@@ -197,31 +197,7 @@ _SIGS = {
     "gyre_t2i_finalize": (_i, [_vp, _vp]),
     "gyre_t2i_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "gyre_t2i_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(_vp), _i, _i]),
-    "gyre_rrdb_create": (_i, [C.POINTER(RRDBCfg), _i, C.POINTER(_vp)]),
-    "gyre_rrdb_destroy": (None, [_vp]),
-    "gyre_rrdb_num_params": (_i, [_vp]),
-    "gyre_rrdb_param_key": (C.c_char_p, [_vp, _i]),
-    "gyre_rrdb_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
-    "gyre_rrdb_finalize": (_i, [_vp, _vp]),
-    "gyre_rrdb_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
-    "gyre_rrdb_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
     "gyre_rrdb_set_path": (_i, [_vp, _i]),
-    "gyre_swinir_create": (_i, [C.POINTER(SwinIRCfg), _i, C.POINTER(_vp)]),
-    "gyre_swinir_destroy": (None, [_vp]),
-    "gyre_swinir_num_params": (_i, [_vp]),
-    "gyre_swinir_param_key": (C.c_char_p, [_vp, _i]),
-    "gyre_swinir_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
-    "gyre_swinir_finalize": (_i, [_vp, _vp]),
-    "gyre_swinir_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
-    "gyre_swinir_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
-    "gyre_hat_create": (_i, [C.POINTER(HATCfg), _i, C.POINTER(_vp)]),
-    "gyre_hat_destroy": (None, [_vp]),
-    "gyre_hat_num_params": (_i, [_vp]),
-    "gyre_hat_param_key": (C.c_char_p, [_vp, _i]),
-    "gyre_hat_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
-    "gyre_hat_finalize": (_i, [_vp, _vp]),
-    "gyre_hat_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
-    "gyre_hat_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
     "gyre_ctrl_create": (_i, [C.POINTER(CtrlCfg), _i, C.POINTER(_vp)]),
     "gyre_ctrl_destroy": (None, [_vp]),
     "gyre_ctrl_num_params": (_i, [_vp]),
@@ -324,6 +300,16 @@ _SIGS = {
     "gyre_op_pixel_shuffle2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_ctrl_emit": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _i]),
 }
+# the handle surface of the three upscaler families: image in, image out
+for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg)):
+    _SIGS.update({f"gyre_{_kind}_create": (_i, [C.POINTER(_cfg), _i, C.POINTER(_vp)]),
+                  f"gyre_{_kind}_destroy": (None, [_vp]),
+                  f"gyre_{_kind}_num_params": (_i, [_vp]),
+                  f"gyre_{_kind}_param_key": (C.c_char_p, [_vp, _i]),
+                  f"gyre_{_kind}_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
+                  f"gyre_{_kind}_finalize": (_i, [_vp, _vp]),
+                  f"gyre_{_kind}_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+                  f"gyre_{_kind}_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i])})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 _libs: dict = {}

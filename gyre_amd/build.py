@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgyre_hip.so")
 LIB_F16 = os.path.join(HERE, "libgyre_hip_f16.so")
 SOURCES = ["kernels_elem.hip", "kernels_gemm.hip", "kernels_gemm4s.hip", "kernels_gemm_ar.hip", "kernels_gemm_sm.hip", "kernels_conv_out.hip", "kernels_attn.hip", "kernels_xattn.hip", "kernels_tome.hip", "kernels_bwd.hip", "kernels_t2i.hip", "kernels_ctrl.hip", "kernels_lora.hip", "kernels_lyco.hip", "kernels_rdb.hip", "kernels_swin.hip", "kernels_hat.hip", "model.hip", "model_vjp.hip", "model_t2i.hip", "model_ctrl.hip", "model_rrdb.hip", "model_swinir.hip", "model_hat.hip"]
-HEADERS = ["common.h", "kernels.h", "gemm_shared.h", "model_impl.h", os.path.join("..", "..", "include", "gyre_hip.h")]
+HEADERS = ["common.h", "kernels.h", "gemm_shared.h", "model_impl.h", "model_upscaler.h", os.path.join("..", "..", "include", "gyre_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5",
          "-Wno-unused-result", "-fno-gpu-rdc",
          # the fully unrolled MFMA epilogues (up to 40 fragments per wave) exceed clang's default pragma-unroll

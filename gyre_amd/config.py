@@ -153,15 +153,19 @@ def tiny_controlnet(**kw) -> ControlNetConfig:
                                       conditioning_embedding_out_channels=(16, 32, 48, 64)), **kw})
 
 
-class T2IConfig(dict):
-    """Configuration of a T2I adapter: a mapping that also reads as attributes - the reference asks both ``"cin" in
-    model.config`` and ``model.config.cin`` (unified_pipeline.py:869)."""
+class _AttrDict(dict):
+    """A mapping that also reads as attributes."""
 
     def __getattr__(self, name):
         try:
             return self[name]
         except KeyError:
             raise AttributeError(name) from None
+
+
+class T2IConfig(_AttrDict):
+    """Configuration of a T2I adapter: a mapping that also reads as attributes - the reference asks both ``"cin" in
+    model.config`` and ``model.config.cin`` (unified_pipeline.py:869)."""
 
 
 # the reference's per-type defaults (t2i_adapter/models.py:82-89, 187-191)
@@ -182,15 +186,9 @@ def tiny_t2i(kind: str = "main", **kw) -> T2IConfig:
     return t2i_config(kind, **{"channels": (32, 64, 128, 128), **kw})
 
 
-class RRDBConfig(dict):
+class RRDBConfig(_AttrDict):
     """Configuration of an RRDBNet upscaler (BasicSR ``RRDBNet(num_in_ch, num_out_ch, scale, num_feat, num_block, num_grow_ch)``
     plus ``plus`` for the reference's ESRGAN+ blocks): a mapping that also reads as attributes."""
-
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError:
-            raise AttributeError(name) from None
 
 
 # the reference's default configurations (gyre/pipeline/upscalers/upscaler_loader.py:22-40)
@@ -215,15 +213,9 @@ def tiny_rrdb(**kw) -> RRDBConfig:
     return rrdb_config(**{"num_block": 2, **kw})
 
 
-class SwinIRConfig(dict):
+class SwinIRConfig(_AttrDict):
     """Configuration of a SwinIR upscaler - the keyword arguments of the reference's ``SwinIR`` constructor
     (gyre/pipeline/upscalers/models/network_swinir.py:651-657): a mapping that also reads as attributes."""
-
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError:
-            raise AttributeError(name) from None
 
 
 # the reference's default configurations (gyre/pipeline/upscalers/upscaler_loader.py:43-69)
@@ -239,33 +231,26 @@ _SWINIR_CTOR = dict(img_size=64, patch_size=1, in_chans=3, embed_dim=96, depths=
                     ape=False, patch_norm=True, use_checkpoint=False, upscale=2, img_range=1.0, upsampler="", resi_connection="1conv")
 
 
-def swinir_config(**kw) -> SwinIRConfig:
-    """The constructor's defaults under ``kw``, refused (NotImplementedError) outside what the native path builds: window 8,
-    embed_dim = 30 * heads with one head count (at most 8) for all layers, an MLP width that is a multiple of 8, "nearest+conv" with
-    upscale 2 or 4, "1conv" / "3conv", ape=False, patch_norm=True, qkv_bias=True, in_chans=3.  A key that is not a constructor
-    argument is refused too - the reference swallows it in ``**kwargs``; here a folder of another model family fails at its
-    configuration instead of at load_state_dict."""
-    unknown = sorted(set(kw) - set(_SWINIR_CTOR))
+def _window_transformer_config(cls, family, ctor, window, kw, before_patch, before_flags):
+    """What swinir_config and hat_config share: the constructor's defaults under ``kw`` (a key that is no constructor argument is
+    refused), then the refusals in the order the two families always made them - the window, the family's ``before_patch(cfg,
+    refuse)``, patch_size / in_chans, the family's ``before_flags(cfg, refuse)`` (upsampler and residual connection), and what the
+    trunk of both needs: ape / patch_norm / qkv_bias / qk_scale, the norm layer, depths and heads, the MLP width, img_range."""
+    unknown = sorted(set(kw) - set(ctor))
     if unknown:
-        raise NotImplementedError(f"SwinIR: {unknown} are not arguments of the SwinIR constructor (a configuration of another model family?)")
-    cfg = SwinIRConfig(**{**_SWINIR_CTOR, **kw})
+        raise NotImplementedError(f"{family}: {unknown} are not arguments of the {family} constructor (a configuration of another model family?)")
+    cfg = cls(**{**ctor, **kw})
     cfg["depths"], cfg["num_heads"] = [int(d) for d in cfg["depths"]], [int(h) for h in cfg["num_heads"]]
 
     def refuse(why):
-        raise NotImplementedError(f"SwinIR: {why} is outside the native path")
+        raise NotImplementedError(f"{family}: {why} is outside the native path")
 
-    size = cfg["img_size"]
-    size = (size, size) if isinstance(size, int) else tuple(size)
-    if cfg["window_size"] != 8:
-        refuse(f"window_size {cfg['window_size']} (8 is built)")
-    if min(size) <= 8 or size[0] % 8 or size[1] % 8:
-        refuse(f"img_size {cfg['img_size']} (multiples of the window above it are built)")
+    if cfg["window_size"] != window:
+        refuse(f"window_size {cfg['window_size']} ({window} is built)")
+    before_patch(cfg, refuse)
     if cfg["patch_size"] != 1 or cfg["in_chans"] != 3:
         refuse("patch_size other than 1 or in_chans other than 3")
-    if cfg["upsampler"] != "nearest+conv" or cfg["upscale"] not in (2, 4):
-        refuse(f"upsampler {cfg['upsampler']!r} at upscale {cfg['upscale']} (nearest+conv at 2 or 4 is built; pixelshuffle, pixelshuffledirect and the denoising form are not)")
-    if cfg["resi_connection"] not in ("1conv", "3conv"):
-        refuse(f"resi_connection {cfg['resi_connection']!r}")
+    before_flags(cfg, refuse)
     if cfg["ape"] or not cfg["patch_norm"] or not cfg["qkv_bias"] or cfg["qk_scale"] is not None:
         refuse("ape=True, patch_norm=False, qkv_bias=False or a qk_scale")
     if cfg["norm_layer"] is not None and cfg["norm_layer"] is not __import__("torch").nn.LayerNorm:
@@ -279,8 +264,29 @@ def swinir_config(**kw) -> SwinIRConfig:
     if hidden < 8 or hidden % 8:
         refuse(f"an MLP width of {hidden} (multiples of 8 are built)")
     if not float(cfg["img_range"]) > 0:
-        raise ValueError("SwinIR: img_range must be positive")
+        raise ValueError(f"{family}: img_range must be positive")
     return cfg
+
+
+def swinir_config(**kw) -> SwinIRConfig:
+    """The constructor's defaults under ``kw``, refused (NotImplementedError) outside what the native path builds: window 8,
+    embed_dim = 30 * heads with one head count (at most 8) for all layers, an MLP width that is a multiple of 8, "nearest+conv" with
+    upscale 2 or 4, "1conv" / "3conv", ape=False, patch_norm=True, qkv_bias=True, in_chans=3.  A key that is not a constructor
+    argument is refused too - the reference swallows it in ``**kwargs``; here a folder of another model family fails at its
+    configuration instead of at load_state_dict."""
+    def img_size(cfg, refuse):
+        size = cfg["img_size"]
+        size = (size, size) if isinstance(size, int) else tuple(size)
+        if min(size) <= 8 or size[0] % 8 or size[1] % 8:
+            refuse(f"img_size {cfg['img_size']} (multiples of the window above it are built)")
+
+    def upsampler(cfg, refuse):
+        if cfg["upsampler"] != "nearest+conv" or cfg["upscale"] not in (2, 4):
+            refuse(f"upsampler {cfg['upsampler']!r} at upscale {cfg['upscale']} (nearest+conv at 2 or 4 is built; pixelshuffle, pixelshuffledirect and the denoising form are not)")
+        if cfg["resi_connection"] not in ("1conv", "3conv"):
+            refuse(f"resi_connection {cfg['resi_connection']!r}")
+
+    return _window_transformer_config(SwinIRConfig, "SwinIR", _SWINIR_CTOR, 8, kw, img_size, upsampler)
 
 
 def tiny_swinir(**kw) -> SwinIRConfig:
@@ -289,15 +295,9 @@ def tiny_swinir(**kw) -> SwinIRConfig:
                                    upsampler="nearest+conv", resi_connection="1conv"), **kw})
 
 
-class HATConfig(dict):
+class HATConfig(_AttrDict):
     """Configuration of a HAT upscaler - the keyword arguments of the reference's ``HAT`` constructor
     (gyre/pipeline/upscalers/models/hat_arch.py:743-769): a mapping that also reads as attributes."""
-
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError:
-            raise AttributeError(name) from None
 
 
 # the reference's default configurations (gyre/pipeline/upscalers/upscaler_loader.py DEFAULT_CONFIGS "hat" / "hat-l")
@@ -322,40 +322,17 @@ def hat_config(**kw) -> HATConfig:
     MLP width that is a multiple of 8, "pixelshuffle" with upscale 2 or 4, "1conv", ape=False, patch_norm=True, qkv_bias=True,
     in_chans=3.  A key that is not a constructor argument is refused too - the reference swallows it in ``**kwargs``; here a folder of
     another model family fails at its configuration instead of at load_state_dict."""
-    unknown = sorted(set(kw) - set(_HAT_CTOR))
-    if unknown:
-        raise NotImplementedError(f"HAT: {unknown} are not arguments of the HAT constructor (a configuration of another model family?)")
-    cfg = HATConfig(**{**_HAT_CTOR, **kw})
-    cfg["depths"], cfg["num_heads"] = [int(d) for d in cfg["depths"]], [int(h) for h in cfg["num_heads"]]
+    def ratios(cfg, refuse):
+        if cfg["overlap_ratio"] != 0.5 or cfg["compress_ratio"] != 3 or cfg["squeeze_factor"] != 30:
+            refuse("an overlap_ratio other than 0.5, a compress_ratio other than 3 or a squeeze_factor other than 30")
 
-    def refuse(why):
-        raise NotImplementedError(f"HAT: {why} is outside the native path")
+    def upsampler(cfg, refuse):
+        if cfg["upsampler"] != "pixelshuffle" or cfg["upscale"] not in (2, 4):
+            refuse(f"upsampler {cfg['upsampler']!r} at upscale {cfg['upscale']} (pixelshuffle at 2 or 4 is built)")
+        if cfg["resi_connection"] != "1conv":
+            refuse(f"resi_connection {cfg['resi_connection']!r}")
 
-    if cfg["window_size"] != 16:
-        refuse(f"window_size {cfg['window_size']} (16 is built)")
-    if cfg["overlap_ratio"] != 0.5 or cfg["compress_ratio"] != 3 or cfg["squeeze_factor"] != 30:
-        refuse("an overlap_ratio other than 0.5, a compress_ratio other than 3 or a squeeze_factor other than 30")
-    if cfg["patch_size"] != 1 or cfg["in_chans"] != 3:
-        refuse("patch_size other than 1 or in_chans other than 3")
-    if cfg["upsampler"] != "pixelshuffle" or cfg["upscale"] not in (2, 4):
-        refuse(f"upsampler {cfg['upsampler']!r} at upscale {cfg['upscale']} (pixelshuffle at 2 or 4 is built)")
-    if cfg["resi_connection"] != "1conv":
-        refuse(f"resi_connection {cfg['resi_connection']!r}")
-    if cfg["ape"] or not cfg["patch_norm"] or not cfg["qkv_bias"] or cfg["qk_scale"] is not None:
-        refuse("ape=True, patch_norm=False, qkv_bias=False or a qk_scale")
-    if cfg["norm_layer"] is not None and cfg["norm_layer"] is not __import__("torch").nn.LayerNorm:
-        refuse("a norm_layer other than LayerNorm")
-    heads, depths = cfg["num_heads"], cfg["depths"]
-    if not depths or len(depths) != len(heads) or len(depths) > 16 or min(depths) < 1:
-        refuse(f"depths {depths} with num_heads {heads} (1 to 16 layers, one head count per layer)")
-    if len(set(heads)) != 1 or not 1 <= heads[0] <= 8 or cfg["embed_dim"] != 30 * heads[0]:
-        refuse(f"embed_dim {cfg['embed_dim']} with num_heads {heads} (embed_dim = 30 * heads, the same 1 to 8 heads in every layer)")
-    hidden = int(cfg["embed_dim"] * cfg["mlp_ratio"])
-    if hidden < 8 or hidden % 8:
-        refuse(f"an MLP width of {hidden} (multiples of 8 are built)")
-    if not float(cfg["img_range"]) > 0:
-        raise ValueError("HAT: img_range must be positive")
-    return cfg
+    return _window_transformer_config(HATConfig, "HAT", _HAT_CTOR, 16, kw, ratios, upsampler)
 
 
 def tiny_hat(**kw) -> HATConfig:

@@ -1,5 +1,5 @@
 // Model runtime internals shared by model.hip (forward graphs + C ABI), model_vjp.hip (input-gradient graphs), model_ctrl.hip,
-// model_t2i.hip and model_rrdb.hip: workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
+// model_t2i.hip and, through model_upscaler.h, the upscaler graphs (model_rrdb.hip, model_swinir.hip, model_hat.hip): workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
 #pragma once
 #include "../../include/gyre_hip.h"
 #include "kernels.h"
@@ -1921,7 +1921,8 @@ struct gyre_vae : DebugTaps {
 };
 
 // ------------------------------------------------------------------------------------------
-// C ABI bodies every handle type shares (gyre_{unet,vae,ctrl,t2i}_create / _num_params / _param_key / _finalize)
+// C ABI bodies the handle types share (gyre_{unet,vae,ctrl,t2i,rrdb,swinir,hat}_create / _num_params / _param_key / _finalize;
+// _set_weight where it does no more than this: t2i, rrdb, swinir, hat)
 // ------------------------------------------------------------------------------------------
 template <typename H, typename Cfg> static int handle_create(const Cfg* cfg, int device, H** out) {
     if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
@@ -1943,6 +1944,25 @@ template <typename H> static int handle_finalize(H* h) {
     TRY(h->store.finalize());
     h->finalized = true;
     return 0;
+}
+template <typename H> static int handle_set_weight(H* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
+    if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    h->finalized = false;
+    return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
+}
+// the two below: handles of the image-in / image-out shape (gyre_{rrdb,swinir,hat}), whose run(dry, stream, image, dtype, B, H, W,
+// workspace, bytes, out, dtype) sizes the workspace when dry
+template <typename H> static size_t handle_workspace_bytes(H* h, int B, int H_, int W) {
+    if (!h) return 0;
+    return h->run(true, nullptr, nullptr, 0, B, H_, W, nullptr, 0, nullptr, 0) ? 0 : h->ex.arena.peak;
+}
+template <typename H> static int handle_forward(H* h, const char* kind, void* st, const void* img, int idt, int B, int H_, int W, void* ws,
+                                                size_t wsb, void* out, int odt) {
+    if (!h || !img || !ws || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
+    if (!h->finalized) GYRE_FAIL(GYRE_ERR_INCOMPLETE, std::string("gyre_") + kind + "_finalize has not succeeded");
+    if (idt < 0 || idt > 2 || odt < 0 || odt > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
+    gyre_launch_counter() = 0;
+    return h->run(false, (hipStream_t)st, img, idt, B, H_, W, ws, wsb, out, odt);
 }
 
 // model_vjp.hip: forward + reverse sweep in one call (dry = size the workspace only)

@@ -16,11 +16,11 @@
 //   generic  launch_gemm (the planner's tile kernels) with bias only, then k_rdb_epilogue in place over the written slice
 //   fused    k_rdb_conv (kernels_rdb.hip): one launch, the epilogue applied to the fp32 accumulators, one rounding
 // auto takes the fused kernel for the shape groups of RDB_AUTO_MASK: where it measured faster (profiles/upscaler_time.json).
-#include "model_impl.h"
+// The weight record (UpConv) is the one of model_upscaler.h; the graph itself shares nothing with the window transformers.
+#include "model_upscaler.h"
 
 namespace {
-struct RConv { bf16_t* w = nullptr; float* b = nullptr; int cin = 0, cout = 0, rows = 0; bool on = false; };   // cin: padded input channels of the weight rows
-struct RDense { RConv c[5]; RConv c1x1; };
+struct RDense { UpConv c[5]; UpConv c1x1; };      // c1x1.w: the Plus block's 1x1, null without it
 
 // Shape groups of the net's 3x3 convolutions, the unit the choice between the two paths is made in (and measured in:
 // tools/upscaler_time.py turns them on one at a time through the tuning form of gyre_rrdb_set_path):
@@ -47,11 +47,11 @@ struct gyre_rrdb {
     bool finalized = false;
     int path = 0;                  // 0 auto, 1 generic, 2 fused, RDB_PATH_TUNING | group mask
     int r = 1, cin0 = 32;          // unshuffle factor and padded channels of the unshuffled image
-    RConv conv_first, conv_body, conv_up1, conv_up2, conv_hr, conv_last;
+    UpConv conv_first, conv_body, conv_up1, conv_up2, conv_hr, conv_last;
     std::vector<RDense> dense;     // 3 per RRDB
 
-    void reg(const std::string& key, int cout, int cin, int cin_pad, RConv& c) {
-        c.on = true; c.cin = cin_pad; c.cout = cout; c.rows = pad8(cout);
+    void reg(const std::string& key, int cout, int cin, int cin_pad, UpConv& c) {
+        c.cin = cin_pad; c.cout = cout; c.rows = pad8(cout);
         c.w = (bf16_t*)store.dmalloc((size_t)c.rows * 9 * cin_pad * 2, true);
         store.add(key + ".weight", {cout, cin, 3, 3}, PK_CONV3, c.w, c.rows, cin_pad);
         c.b = (float*)store.dmalloc((size_t)c.rows * 4, true);
@@ -74,7 +74,7 @@ struct gyre_rrdb {
                 RDense d;
                 for (int k = 0; k < 5; ++k) reg(p + ".conv" + std::to_string(k + 1), k == 4 ? 64 : 32, 64 + 32 * k, 64 + 32 * k, d.c[k]);
                 if (c.plus) {
-                    d.c1x1.on = true; d.c1x1.cin = 64; d.c1x1.cout = 32; d.c1x1.rows = 32;
+                    d.c1x1.cin = 64; d.c1x1.cout = 32; d.c1x1.rows = 32;
                     d.c1x1.w = store.mat(p + ".conv1x1", 32, 64, true, false, nullptr);
                 }
                 dense.push_back(d);
@@ -90,13 +90,13 @@ struct gyre_rrdb {
 
     // slice pointer; a dry run plans with aligned stand-ins of the same residue mod 256 (arena tensors are 256-byte aligned)
     bf16_t* at(const Tn& t, int c0) const { return ex.arena.dry ? (bf16_t*)(uintptr_t)(4096 + 2 * c0) : t.p + c0; }
-    bool fused(const RConv& c, int Cin, int ups) const {
+    bool fused(const UpConv& c, int Cin, int ups) const {
         if (path == 1 || path == 2) return path == 2;
         const int mask = path & RDB_PATH_TUNING ? path & 0x1f : RDB_AUTO_MASK;
         return (mask >> rdb_group(Cin, c.cout, ups)) & 1;
     }
     // out[pix][c0 .. c0 + cout) = epilogue(conv3x3(x[pix][0 .. Cin))), x NHWC [B][H][W] with pixel stride x.C
-    int conv(const Tn& x, int Cin, int ups, const RConv& c, Tn& out, int c0, RdbEpilogueArgs e) {
+    int conv(const Tn& x, int Cin, int ups, const UpConv& c, Tn& out, int c0, RdbEpilogueArgs e) {
         if (Cin != c.cin || Cin > x.C || c0 + c.rows > out.C) GYRE_FAIL(GYRE_ERR_INVALID, "rrdb: internal shape mismatch");
         const int Ho = ups ? 2 * x.H : x.H, Wo = ups ? 2 * x.W : x.W;
         if (out.H != Ho || out.W != Wo || out.B != x.B) GYRE_FAIL(GYRE_ERR_INVALID, "rrdb: internal size mismatch");
@@ -129,7 +129,7 @@ struct gyre_rrdb {
         for (int k = 0; k < 4; ++k) {
             RdbEpilogueArgs e = act_only();
             Tn tmp;
-            if (k == 1 && d.c1x1.on) {
+            if (k == 1 && d.c1x1.w) {
                 // Plus: x2 = lrelu(conv2(x | x1)) + conv1x1(x).  Fused: the 1x1 lands in the x2 slice and conv2 adds it in place (r1 aliases
                 // the output); generic: the GEMM would overwrite the slice first, so the 1x1 goes to a side tensor
                 const bool inplace = fused(d.c[1], 96, 0);
@@ -213,9 +213,7 @@ void gyre_rrdb_destroy(gyre_rrdb* h) { delete h; }
 int gyre_rrdb_num_params(const gyre_rrdb* h) { return handle_num_params(h); }
 const char* gyre_rrdb_param_key(const gyre_rrdb* h, int i) { return handle_param_key(h, i); }
 int gyre_rrdb_set_weight(gyre_rrdb* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    h->finalized = false;
-    return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
+    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
 }
 int gyre_rrdb_finalize(gyre_rrdb* h, void* st) { return handle_finalize(h); }
 int gyre_rrdb_set_path(gyre_rrdb* h, int path) {
@@ -225,16 +223,9 @@ int gyre_rrdb_set_path(gyre_rrdb* h, int path) {
     h->path = path;
     return 0;
 }
-size_t gyre_rrdb_workspace_bytes(gyre_rrdb* h, int B, int H, int W) {
-    if (!h) return 0;
-    return h->run(true, nullptr, nullptr, 0, B, H, W, nullptr, 0, nullptr, 0) ? 0 : h->ex.arena.peak;
-}
+size_t gyre_rrdb_workspace_bytes(gyre_rrdb* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
 int gyre_rrdb_forward(gyre_rrdb* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    if (!h || !img || !ws || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    if (!h->finalized) GYRE_FAIL(GYRE_ERR_INCOMPLETE, "gyre_rrdb_finalize has not succeeded");
-    if (idt < 0 || idt > 2 || odt < 0 || odt > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
-    gyre_launch_counter() = 0;
-    return h->run(false, (hipStream_t)st, img, idt, B, H, W, ws, wsb, out, odt);
+    return handle_forward(h, "rrdb", st, img, idt, B, H, W, ws, wsb, out, odt);
 }
 
 int gyre_op_rdb_tile(int* th, int* tw) {

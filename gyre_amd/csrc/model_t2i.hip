@@ -172,9 +172,7 @@ void gyre_t2i_destroy(gyre_t2i* h) { delete h; }
 int gyre_t2i_num_params(const gyre_t2i* h) { return handle_num_params(h); }
 const char* gyre_t2i_param_key(const gyre_t2i* h, int i) { return handle_param_key(h, i); }
 int gyre_t2i_set_weight(gyre_t2i* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    h->finalized = false;
-    return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
+    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
 }
 int gyre_t2i_finalize(gyre_t2i* h, void* st) { return handle_finalize(h); }
 size_t gyre_t2i_workspace_bytes(gyre_t2i* h, int B, int H, int W) {

@@ -32,8 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib, images
-from .config import (HAT_DEFAULTS, RRDB_DEFAULTS, SWINIR_DEFAULTS, HATConfig, RRDBConfig, SwinIRConfig, hat_config, rrdb_config,
-                     swinir_config)
+from .config import HAT_DEFAULTS, RRDB_DEFAULTS, SWINIR_DEFAULTS, hat_config, rrdb_config, swinir_config
 from .modules import _NativeModule, _build_tree
 from .weights import hat_is_buffer, hat_param_shapes, rrdb_param_shapes, swinir_is_buffer, swinir_param_shapes
 
@@ -41,24 +40,98 @@ PATHS = {"auto": 0, "generic": 1, "fused": 2}
 _UNSHUFFLE = {4: 1, 2: 2, 1: 4}          # model scale -> pixel-unshuffle factor in front of conv_first
 
 
-class GyreHipRRDBNet(_NativeModule):
-    """Drop-in for BasicSR's RRDBNet / the reference's RRDBNet_Plus (``plus=True``): ``forward(x) -> tensor``, NCHW in and out."""
+class _NativeUpscaler(_NativeModule):
+    """What the three upscaler shells share: the configuration merge, the parameter tree with the family's buffers, the workspace
+    query and the native call (gyre_{kind}_workspace_bytes / gyre_{kind}_forward).  A family names its configuration
+    (``_make_config``, ``_param_shapes``, the keys of its channel count and scale), its buffers (``_is_buffer``, ``_buffer_dtype``) and
+    its size rule (``_padding``), and builds its C configuration (``_c_cfg``)."""
 
-    _kind = "rrdb"
+    _make_config = _param_shapes = None
+    _in_key, _scale_key = "in_chans", "upscale"
+    _is_buffer = staticmethod(lambda key: False)
+    _buffer_dtype = staticmethod(lambda leaf: torch.long)
 
-    def __init__(self, config: Optional[dict] = None, plus: bool = False, **kw):
+    def __init__(self, config: Optional[dict] = None, **kw):
         super().__init__()
         cfg = dict(config or {})
         cfg.update(kw)
-        plus = bool(cfg.pop("plus", plus))
-        self.config: RRDBConfig = rrdb_config(plus=plus, **cfg)
-        self._scale = self.config.scale
-        self._window_size = 32
-        self._path = 0
-        _build_tree(self, rrdb_param_shapes(self.config))
+        self.config = type(self)._make_config(**cfg)
+        self._scale = self.config[self._scale_key]
+        self._window_size = self.config.get("window_size", 32)
+        shapes = self._shapes()
+        _build_tree(self, {k: v for k, v in shapes.items() if not self._is_buffer(k)})
+        for key, shape in shapes.items():
+            if self._is_buffer(key):
+                node = self
+                *path, leaf = key.split(".")
+                for part in path:
+                    node = node._modules[part]
+                node.register_buffer(leaf, torch.zeros(shape, dtype=self._buffer_dtype(leaf)))
 
     def _shapes(self):
-        return rrdb_param_shapes(self.config)
+        return type(self)._param_shapes(self.config)
+
+    def _prepare(self, h) -> None:
+        """Per-handle switches to apply before a native call."""
+
+    def _padding(self, H: int, W: int):
+        """The family's size rule: (rows, columns) to reflect-pad on the bottom / right before the call, cropped from the result;
+        a size it does not take is a ValueError."""
+        raise NotImplementedError
+
+    def _native(self, name: str):
+        return getattr(self._L(), f"gyre_{self._kind}_{name}")
+
+    def workspace_bytes(self, B: int, H: int, W: int, device) -> int:
+        h = self._sync(torch.device(device))
+        self._prepare(h)
+        with torch.cuda.device(device):
+            return int(self._native("workspace_bytes")(C.c_void_p(h), B, H, W))
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        cin = self.config[self._in_key]
+        if x.ndim != 4 or x.shape[1] != cin:
+            raise ValueError(f"expected an image [B,{cin},H,W], got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        ph, pw = self._padding(H, W)
+        dev = x.device
+        h = self._sync(dev)
+        self._prepare(h)
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            x = x.to(torch.float32)
+        if ph or pw:                                                     # check_image_size: reflect on the bottom / right
+            x = torch.nn.functional.pad(x, (0, pw, 0, ph), "reflect")
+        x = x.contiguous()
+        _lib.require_gpu_tensor(x, "image")
+        L = self._L()
+        Hp, Wp = H + ph, W + pw
+        with torch.cuda.device(dev):
+            need = self._native("workspace_bytes")(C.c_void_p(h), B, Hp, Wp)
+            if need == 0:
+                _lib.check(-1, L)
+            ws = self._workspace(need, dev)
+            wp = (ws.data_ptr() + 255) & ~255
+            out = torch.empty(self.out_shape(x.shape), dtype=self.dtype, device=dev)
+            _lib.check(self._native("forward")(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()),
+                                               _lib.dtype_code(x), B, Hp, Wp, C.c_void_p(wp), need, C.c_void_p(out.data_ptr()),
+                                               _lib.dtype_code(out)), L)
+        return out[:, :, :H * self._scale, :W * self._scale] if ph or pw else out
+
+
+class GyreHipRRDBNet(_NativeUpscaler):
+    """Drop-in for BasicSR's RRDBNet / the reference's RRDBNet_Plus (``plus=True``): ``forward(x) -> tensor``, NCHW in and out."""
+
+    _kind = "rrdb"
+    _make_config, _param_shapes = staticmethod(rrdb_config), staticmethod(rrdb_param_shapes)
+    _in_key, _scale_key = "num_in_ch", "scale"
+    _path = 0
+
+    def __init__(self, config: Optional[dict] = None, plus: bool = False, **kw):
+        cfg = dict(config or {})
+        cfg.update(kw)
+        cfg["plus"] = bool(cfg.pop("plus", plus))
+        super().__init__(cfg)
 
     def _c_cfg(self):
         c, cfg = self.config, _lib.RRDBCfg()
@@ -75,7 +148,7 @@ class GyreHipRRDBNet(_NativeModule):
         self._path = PATHS.get(path, path)
         self._path_applied = None
 
-    def _apply_path(self, h) -> None:
+    def _prepare(self, h) -> None:
         if getattr(self, "_path_applied", None) != (h, self._path):
             _lib.check(self._L().gyre_rrdb_set_path(C.c_void_p(h), self._path), self._L())
             self._path_applied = (h, self._path)
@@ -89,188 +162,72 @@ class GyreHipRRDBNet(_NativeModule):
         r = _UNSHUFFLE[self.config.scale]
         return (B, self.config.num_out_ch, H // r * 4, W // r * 4)
 
-    def workspace_bytes(self, B: int, H: int, W: int, device) -> int:
-        h = self._sync(torch.device(device))
-        self._apply_path(h)
-        with torch.cuda.device(device):
-            return int(self._L().gyre_rrdb_workspace_bytes(C.c_void_p(h), B, H, W))
-
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        c = self.config
-        if x.ndim != 4 or x.shape[1] != c.num_in_ch:
-            raise ValueError(f"expected an image [B,{c.num_in_ch},H,W], got {tuple(x.shape)}")
-        B, _, H, W = x.shape
-        r = _UNSHUFFLE[c.scale]
+    def _padding(self, H, W):
+        r = _UNSHUFFLE[self.config.scale]
         if H % r or W % r or H < r or W < r:
-            raise ValueError(f"image height and width must be multiples of {r} for scale {c.scale}, got {H} x {W}")
-        dev = x.device
-        h = self._sync(dev)
-        self._apply_path(h)
-        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            x = x.to(torch.float32)
-        x = x.contiguous()
-        _lib.require_gpu_tensor(x, "image")
-        L = self._L()
-        with torch.cuda.device(dev):
-            need = L.gyre_rrdb_workspace_bytes(C.c_void_p(h), B, H, W)
-            if need == 0:
-                _lib.check(-1, L)
-            ws = self._workspace(need, dev)
-            wp = (ws.data_ptr() + 255) & ~255
-            out = torch.empty(self.out_shape(x.shape), dtype=self.dtype, device=dev)
-            _lib.check(L.gyre_rrdb_forward(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()),
-                                           _lib.dtype_code(x), B, H, W, C.c_void_p(wp), need, C.c_void_p(out.data_ptr()),
-                                           _lib.dtype_code(out)), L)
-        return out
+            raise ValueError(f"image height and width must be multiples of {r} for scale {self.config.scale}, got {H} x {W}")
+        return 0, 0
 
 
-class GyreHipSwinIR(_NativeModule):
-    """Drop-in for the reference's ``SwinIR`` with upsampler "nearest+conv": ``forward(x) -> tensor``, NCHW in and out.  The state
-    dict carries the reference's names, its buffers included (``attn.relative_position_index``, the shifted blocks' ``attn_mask``), so
-    a real checkpoint loads strictly; the buffers' values are never read - the kernel computes index and mask from the window position."""
+class _WindowUpscaler(_NativeUpscaler):
+    """The two window transformers: the same output shape and the same head of the C configuration."""
 
-    _kind = "swinir"
-
-    def __init__(self, config: Optional[dict] = None, **kw):
-        super().__init__()
-        cfg = dict(config or {})
-        cfg.update(kw)
-        self.config: SwinIRConfig = swinir_config(**cfg)
-        self._scale = self.config.upscale
-        self._window_size = self.config.window_size
-        shapes = swinir_param_shapes(self.config)
-        _build_tree(self, {k: v for k, v in shapes.items() if not swinir_is_buffer(k)})
-        for key, shape in shapes.items():
-            if swinir_is_buffer(key):
-                node = self
-                *path, leaf = key.split(".")
-                for part in path:
-                    node = node._modules[part]
-                node.register_buffer(leaf, torch.zeros(shape, dtype=torch.long if leaf == "relative_position_index" else torch.float32))
-
-    def _shapes(self):
-        return swinir_param_shapes(self.config)
-
-    def _c_cfg(self):
-        c, cfg = self.config, _lib.SwinIRCfg()
+    def _c_trunk(self, cfg):
+        c = self.config
         cfg.in_chans, cfg.embed_dim, cfg.num_layers = c.in_chans, c.embed_dim, len(c.depths)
         for i, (d, h) in enumerate(zip(c.depths, c.num_heads)):
             cfg.depths[i], cfg.num_heads[i] = d, h
         cfg.window_size, cfg.mlp_hidden, cfg.upscale = c.window_size, int(c.embed_dim * c.mlp_ratio), c.upscale
-        cfg.img_range, cfg.resi_3conv = float(c.img_range), int(c.resi_connection == "3conv")
+        cfg.img_range = float(c.img_range)
         return cfg
 
     def out_shape(self, shape):
         B, _, H, W = shape
         return (B, self.config.in_chans, H * self.config.upscale, W * self.config.upscale)
 
-    def workspace_bytes(self, B: int, H: int, W: int, device) -> int:
-        h = self._sync(torch.device(device))
-        with torch.cuda.device(device):
-            return int(self._L().gyre_swinir_workspace_bytes(C.c_void_p(h), B, H, W))
 
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        c = self.config
-        if x.ndim != 4 or x.shape[1] != c.in_chans:
-            raise ValueError(f"expected an image [B,{c.in_chans},H,W], got {tuple(x.shape)}")
-        B, _, H, W = x.shape
+class GyreHipSwinIR(_WindowUpscaler):
+    """Drop-in for the reference's ``SwinIR`` with upsampler "nearest+conv": ``forward(x) -> tensor``, NCHW in and out.  The state
+    dict carries the reference's names, its buffers included (``attn.relative_position_index``, the shifted blocks' ``attn_mask``), so
+    a real checkpoint loads strictly; the buffers' values are never read - the kernel computes index and mask from the window position."""
+
+    _kind = "swinir"
+    _make_config, _param_shapes = staticmethod(swinir_config), staticmethod(swinir_param_shapes)
+    _is_buffer = staticmethod(swinir_is_buffer)
+    _buffer_dtype = staticmethod(lambda leaf: torch.long if leaf == "relative_position_index" else torch.float32)
+
+    def _c_cfg(self):
+        cfg = self._c_trunk(_lib.SwinIRCfg())
+        cfg.resi_3conv = int(self.config.resi_connection == "3conv")
+        return cfg
+
+    def _padding(self, H, W):
         ph, pw = -H % 8, -W % 8
         if ph >= H or pw >= W:                                           # (torch's reflect padding needs pad < size)
             raise ValueError(f"an image of {H} x {W} is too small to reflect-pad to a multiple of the window size 8")
-        dev = x.device
-        h = self._sync(dev)
-        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            x = x.to(torch.float32)
-        if ph or pw:                                                     # check_image_size: reflect on the bottom / right
-            x = torch.nn.functional.pad(x, (0, pw, 0, ph), "reflect")
-        x = x.contiguous()
-        _lib.require_gpu_tensor(x, "image")
-        L = self._L()
-        Hp, Wp = H + ph, W + pw
-        with torch.cuda.device(dev):
-            need = L.gyre_swinir_workspace_bytes(C.c_void_p(h), B, Hp, Wp)
-            if need == 0:
-                _lib.check(-1, L)
-            ws = self._workspace(need, dev)
-            wp = (ws.data_ptr() + 255) & ~255
-            out = torch.empty(self.out_shape(x.shape), dtype=self.dtype, device=dev)
-            _lib.check(L.gyre_swinir_forward(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()),
-                                             _lib.dtype_code(x), B, Hp, Wp, C.c_void_p(wp), need, C.c_void_p(out.data_ptr()),
-                                             _lib.dtype_code(out)), L)
-        return out[:, :, :H * c.upscale, :W * c.upscale] if ph or pw else out
+        return ph, pw
 
 
-class GyreHipHAT(_NativeModule):
+class GyreHipHAT(_WindowUpscaler):
     """Drop-in for the reference's ``HAT`` with upsampler "pixelshuffle": ``forward(x) -> tensor``, NCHW in and out.  The state dict
     carries the reference's names, its two global buffers included (``relative_position_index_SA`` / ``_OCA``), so a real checkpoint
     loads strictly; the buffers' values are never read - the kernel computes both indices and the mask from the window position.
     Like the reference, the model has no padding: H and W must be multiples of the window size 16 (``tile()`` cuts multiples of 32)."""
 
     _kind = "hat"
-
-    def __init__(self, config: Optional[dict] = None, **kw):
-        super().__init__()
-        cfg = dict(config or {})
-        cfg.update(kw)
-        self.config: HATConfig = hat_config(**cfg)
-        self._scale = self.config.upscale
-        self._window_size = self.config.window_size
-        shapes = hat_param_shapes(self.config)
-        _build_tree(self, {k: v for k, v in shapes.items() if not hat_is_buffer(k)})
-        for key, shape in shapes.items():
-            if hat_is_buffer(key):
-                self.register_buffer(key, torch.zeros(shape, dtype=torch.long))
-
-    def _shapes(self):
-        return hat_param_shapes(self.config)
+    _make_config, _param_shapes = staticmethod(hat_config), staticmethod(hat_param_shapes)
+    _is_buffer = staticmethod(hat_is_buffer)
 
     def _c_cfg(self):
-        c, cfg = self.config, _lib.HATCfg()
-        cfg.in_chans, cfg.embed_dim, cfg.num_layers = c.in_chans, c.embed_dim, len(c.depths)
-        for i, (d, h) in enumerate(zip(c.depths, c.num_heads)):
-            cfg.depths[i], cfg.num_heads[i] = d, h
-        cfg.window_size, cfg.mlp_hidden, cfg.upscale = c.window_size, int(c.embed_dim * c.mlp_ratio), c.upscale
-        cfg.img_range, cfg.compress_ratio, cfg.squeeze_factor = float(c.img_range), c.compress_ratio, c.squeeze_factor
+        c, cfg = self.config, self._c_trunk(_lib.HATCfg())
+        cfg.compress_ratio, cfg.squeeze_factor = c.compress_ratio, c.squeeze_factor
         cfg.conv_scale, cfg.overlap_ratio = float(c.conv_scale), float(c.overlap_ratio)
         return cfg
 
-    def out_shape(self, shape):
-        B, _, H, W = shape
-        return (B, self.config.in_chans, H * self.config.upscale, W * self.config.upscale)
-
-    def workspace_bytes(self, B: int, H: int, W: int, device) -> int:
-        h = self._sync(torch.device(device))
-        with torch.cuda.device(device):
-            return int(self._L().gyre_hat_workspace_bytes(C.c_void_p(h), B, H, W))
-
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        c = self.config
-        if x.ndim != 4 or x.shape[1] != c.in_chans:
-            raise ValueError(f"expected an image [B,{c.in_chans},H,W], got {tuple(x.shape)}")
-        B, _, H, W = x.shape
+    def _padding(self, H, W):
         if H < 16 or W < 16 or H % 16 or W % 16:
             raise ValueError(f"HAT takes images whose height and width are multiples of the window size 16, got {H} x {W}")
-        dev = x.device
-        h = self._sync(dev)
-        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            x = x.to(torch.float32)
-        x = x.contiguous()
-        _lib.require_gpu_tensor(x, "image")
-        L = self._L()
-        with torch.cuda.device(dev):
-            need = L.gyre_hat_workspace_bytes(C.c_void_p(h), B, H, W)
-            if need == 0:
-                _lib.check(-1, L)
-            ws = self._workspace(need, dev)
-            wp = (ws.data_ptr() + 255) & ~255
-            out = torch.empty(self.out_shape(x.shape), dtype=self.dtype, device=dev)
-            _lib.check(L.gyre_hat_forward(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()),
-                                          _lib.dtype_code(x), B, H, W, C.c_void_p(wp), need, C.c_void_p(out.data_ptr()),
-                                          _lib.dtype_code(out)), L)
-        return out
+        return 0, 0
 
 
 # ---- loader ----------------------------------------------------------------------------------------------------------------------------

@@ -308,6 +308,34 @@ def rrdb_param_shapes(cfg) -> Shapes:
     return s
 
 
+class _WindowShapes:
+    """The entries the SwinIR and HAT state dicts are made of, appended to ``s`` in call order: cfg gives the width and the MLP ratio."""
+
+    def __init__(self, s: Shapes, cfg):
+        self.s, self.C, self.hidden = s, cfg["embed_dim"], int(cfg["embed_dim"] * cfg["mlp_ratio"])
+
+    def conv(self, p, o, i, k=3):
+        self.s[p + ".weight"] = (o, i, k, k)
+        self.s[p + ".bias"] = (o,)
+
+    def lin(self, p, o, i):
+        self.s[p + ".weight"] = (o, i)
+        self.s[p + ".bias"] = (o,)
+
+    def norm(self, p):
+        self.s[p + ".weight"] = (self.C,)
+        self.s[p + ".bias"] = (self.C,)
+
+    def qkv_proj(self, p):
+        self.lin(p + ".qkv", 3 * self.C, self.C)
+        self.lin(p + ".proj", self.C, self.C)
+
+    def mlp(self, p):
+        self.norm(p + ".norm2")
+        self.lin(p + ".mlp.fc1", self.hidden, self.C)
+        self.lin(p + ".mlp.fc2", self.C, self.hidden)
+
+
 SWINIR_BUFFERS = ("attn.relative_position_index", "attn_mask")      # state-dict entries that are buffers: loaded, never read
 
 
@@ -317,55 +345,40 @@ def swinir_param_shapes(cfg) -> Shapes:
     ``relative_position_index`` and the ``attn_mask`` of the shifted (odd) blocks, built for cfg["img_size"]; cfg: a mapping as
     gyre_amd.config.tiny_swinir returns."""
     s: Shapes = OrderedDict()
+    b = _WindowShapes(s, cfg)
     C, heads, upscale = cfg["embed_dim"], cfg["num_heads"], cfg["upscale"]
-    hidden = int(C * cfg["mlp_ratio"])
     size = cfg["img_size"]
     size = (size, size) if isinstance(size, int) else tuple(size)
     three = cfg["resi_connection"] == "3conv"
 
-    def conv(p, o, i, k=3):
-        s[p + ".weight"] = (o, i, k, k)
-        s[p + ".bias"] = (o,)
-
-    def lin(p, o, i):
-        s[p + ".weight"] = (o, i)
-        s[p + ".bias"] = (o,)
-
-    def norm(p):
-        s[p + ".weight"] = (C,)
-        s[p + ".bias"] = (C,)
-
     def resi(p):
         if not three:
-            return conv(p, C, C)
-        conv(p + ".0", C // 4, C)
-        conv(p + ".2", C // 4, C // 4, 1)
-        conv(p + ".4", C, C // 4)
+            return b.conv(p, C, C)
+        b.conv(p + ".0", C // 4, C)
+        b.conv(p + ".2", C // 4, C // 4, 1)
+        b.conv(p + ".4", C, C // 4)
 
-    conv("conv_first", C, cfg["in_chans"])
-    norm("patch_embed.norm")
+    b.conv("conv_first", C, cfg["in_chans"])
+    b.norm("patch_embed.norm")
     for i, depth in enumerate(cfg["depths"]):
         for j in range(depth):
             p = f"layers.{i}.residual_group.blocks.{j}"
             if j % 2:
                 s[p + ".attn_mask"] = (size[0] // 8 * (size[1] // 8), 64, 64)
-            norm(p + ".norm1")
+            b.norm(p + ".norm1")
             s[p + ".attn.relative_position_bias_table"] = (225, heads[i])
             s[p + ".attn.relative_position_index"] = (64, 64)
-            lin(p + ".attn.qkv", 3 * C, C)
-            lin(p + ".attn.proj", C, C)
-            norm(p + ".norm2")
-            lin(p + ".mlp.fc1", hidden, C)
-            lin(p + ".mlp.fc2", C, hidden)
+            b.qkv_proj(p + ".attn")
+            b.mlp(p)
         resi(f"layers.{i}.conv")
-    norm("norm")
+    b.norm("norm")
     resi("conv_after_body")
-    conv("conv_before_upsample.0", 64, C)
-    conv("conv_up1", 64, 64)
+    b.conv("conv_before_upsample.0", 64, C)
+    b.conv("conv_up1", 64, 64)
     if upscale == 4:
-        conv("conv_up2", 64, 64)
-    conv("conv_hr", 64, 64)
-    conv("conv_last", cfg["in_chans"], 64)
+        b.conv("conv_up2", 64, 64)
+    b.conv("conv_hr", 64, 64)
+    b.conv("conv_last", cfg["in_chans"], 64)
     return s
 
 
@@ -381,57 +394,37 @@ def hat_param_shapes(cfg) -> Shapes:
     "pixelshuffle" and "1conv", in state_dict() order, its two global index buffers (HAT_BUFFERS) first; cfg: a mapping as
     gyre_amd.config.tiny_hat returns."""
     s: Shapes = OrderedDict()
+    b = _WindowShapes(s, cfg)
     C, heads, upscale = cfg["embed_dim"], cfg["num_heads"], cfg["upscale"]
-    hidden = int(C * cfg["mlp_ratio"])
     mid, sq = C // cfg["compress_ratio"], C // cfg["squeeze_factor"]
-
-    def conv(p, o, i, k=3):
-        s[p + ".weight"] = (o, i, k, k)
-        s[p + ".bias"] = (o,)
-
-    def lin(p, o, i):
-        s[p + ".weight"] = (o, i)
-        s[p + ".bias"] = (o,)
-
-    def norm(p):
-        s[p + ".weight"] = (C,)
-        s[p + ".bias"] = (C,)
-
-    def mlp(p):
-        norm(p + ".norm2")
-        lin(p + ".mlp.fc1", hidden, C)
-        lin(p + ".mlp.fc2", C, hidden)
-
     s["relative_position_index_SA"] = (256, 256)
     s["relative_position_index_OCA"] = (256, 576)
-    conv("conv_first", C, cfg["in_chans"])
-    norm("patch_embed.norm")
+    b.conv("conv_first", C, cfg["in_chans"])
+    b.norm("patch_embed.norm")
     for i, depth in enumerate(cfg["depths"]):
         for j in range(depth):
             p = f"layers.{i}.residual_group.blocks.{j}"
-            norm(p + ".norm1")
+            b.norm(p + ".norm1")
             s[p + ".attn.relative_position_bias_table"] = (961, heads[i])
-            lin(p + ".attn.qkv", 3 * C, C)
-            lin(p + ".attn.proj", C, C)
-            conv(p + ".conv_block.cab.0", mid, C)
-            conv(p + ".conv_block.cab.2", C, mid)
-            conv(p + ".conv_block.cab.3.attention.1", sq, C, 1)
-            conv(p + ".conv_block.cab.3.attention.3", C, sq, 1)
-            mlp(p)
+            b.qkv_proj(p + ".attn")
+            b.conv(p + ".conv_block.cab.0", mid, C)
+            b.conv(p + ".conv_block.cab.2", C, mid)
+            b.conv(p + ".conv_block.cab.3.attention.1", sq, C, 1)
+            b.conv(p + ".conv_block.cab.3.attention.3", C, sq, 1)
+            b.mlp(p)
         p = f"layers.{i}.residual_group.overlap_attn"
         s[p + ".relative_position_bias_table"] = (1521, heads[i])
-        norm(p + ".norm1")
-        lin(p + ".qkv", 3 * C, C)
-        lin(p + ".proj", C, C)
-        mlp(p)
-        conv(f"layers.{i}.conv", C, C)
-    norm("norm")
-    conv("conv_after_body", C, C)
-    conv("conv_before_upsample.0", 64, C)
-    conv("upsample.0", 256, 64)
+        b.norm(p + ".norm1")
+        b.qkv_proj(p)
+        b.mlp(p)
+        b.conv(f"layers.{i}.conv", C, C)
+    b.norm("norm")
+    b.conv("conv_after_body", C, C)
+    b.conv("conv_before_upsample.0", 64, C)
+    b.conv("upsample.0", 256, 64)
     if upscale == 4:
-        conv("upsample.2", 256, 64)
-    conv("conv_last", cfg["in_chans"], 64)
+        b.conv("upsample.2", 256, 64)
+    b.conv("conv_last", cfg["in_chans"], 64)
     return s
 
 
