@@ -97,6 +97,17 @@ class HATCfg(C.Structure):
                 ("overlap_ratio", C.c_float)]
 
 
+class LineartCfg(C.Structure):
+    """gyre_lineart_cfg (include/gyre_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("input_nc", "output_nc", "n_residual_blocks", "sigmoid")]
+
+
+class InormApplyArgs(C.Structure):
+    """gyre_inorm_apply_args (include/gyre_hip.h): one launch of the instance-normalisation apply pass, for tests."""
+    _fields_ = [(n, C.c_void_p) for n in ("x", "stats", "res", "out")] + \
+               [(n, C.c_int32) for n in ("B", "H", "W", "C", "shuffled", "relu", "res_pad", "pad", "patch")]
+
+
 class RdbEpilogue(C.Structure):
     """gyre_rdb_epilogue (include/gyre_hip.h): v = alpha (acc + bias); leaky-relu(0.2) if act; + beta1 r1; + beta2 r2."""
     _fields_ = [("bias", C.c_void_p), ("alpha", C.c_float), ("act", C.c_int32), ("r1", C.c_void_p), ("ldr1", C.c_int32),
@@ -299,9 +310,16 @@ _SIGS = {
     "gyre_op_scale_add": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _sz, _i]),
     "gyre_op_pixel_shuffle2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_ctrl_emit": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _i]),
+    "gyre_op_conv3x3_valid": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "gyre_op_inorm_workspace": (_sz, [_i, _sz, _i]),
+    "gyre_op_inorm_stats": (_i, [_vp, _vp, _i, _i, _sz, _i, _f, _vp, _vp]),
+    "gyre_op_inorm_apply": (_i, [_vp, C.POINTER(InormApplyArgs)]),
+    "gyre_op_tconv_compose": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "gyre_op_conv7_in": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "gyre_op_conv7_out": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
 }
-# the handle surface of the three upscaler families: image in, image out
-for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg)):
+# the handle surface of the three upscaler families and of the line-art hinter: image in, image out
+for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg)):
     _SIGS.update({f"gyre_{_kind}_create": (_i, [C.POINTER(_cfg), _i, C.POINTER(_vp)]),
                   f"gyre_{_kind}_destroy": (None, [_vp]),
                   f"gyre_{_kind}_num_params": (_i, [_vp]),

@@ -213,6 +213,31 @@ def tiny_rrdb(**kw) -> RRDBConfig:
     return rrdb_config(**{"num_block": 2, **kw})
 
 
+class LineartConfig(_AttrDict):
+    """Configuration of the line-art hinter - the arguments of the reference's ``DrawingGenerator`` constructor
+    (gyre/pipeline/hinters/models/informative_drawings.py:57): a mapping that also reads as attributes."""
+
+
+def lineart_config(input_nc: int, output_nc: int, n_residual_blocks: int = 9, sigmoid: bool = True, **kw) -> LineartConfig:
+    """The constructor's defaults, refused (NotImplementedError) outside what the native path builds: input_nc 3, output_nc 1 and
+    1 to 16 residual blocks (every configuration the reference ships is 3 / 1 / 3).  A keyword that is not a constructor argument
+    is refused too."""
+    if kw:
+        raise NotImplementedError(f"DrawingGenerator: {sorted(kw)} are not arguments of the DrawingGenerator constructor "
+                                  f"(a configuration of another model family?)")
+    cfg = LineartConfig(input_nc=int(input_nc), output_nc=int(output_nc), n_residual_blocks=int(n_residual_blocks), sigmoid=bool(sigmoid))
+    if cfg["input_nc"] != 3 or cfg["output_nc"] != 1:
+        raise NotImplementedError(f"DrawingGenerator: input_nc {input_nc} / output_nc {output_nc} is outside the native path (3 / 1 is built)")
+    if not 1 <= cfg["n_residual_blocks"] <= 16:
+        raise NotImplementedError(f"DrawingGenerator: n_residual_blocks {n_residual_blocks} is outside the native path (1 to 16 are built)")
+    return cfg
+
+
+def tiny_lineart(**kw) -> LineartConfig:
+    """One residual block, no sigmoid: every kind of layer the generator has, once."""
+    return lineart_config(**{**dict(input_nc=3, output_nc=1, n_residual_blocks=1, sigmoid=False), **kw})
+
+
 class SwinIRConfig(_AttrDict):
     """Configuration of a SwinIR upscaler - the keyword arguments of the reference's ``SwinIR`` constructor
     (gyre/pipeline/upscalers/models/network_swinir.py:651-657): a mapping that also reads as attributes."""

@@ -224,6 +224,36 @@ int launch_scale_add(hipStream_t st, bf16_t* y, int ldy, const bf16_t* c2, int l
 // PixelShuffle(2) on NHWC: out[b][2 y + i][2 x + j][c] = x[b][y][x][4 c + 2 i + j], c < Co (a multiple of 8); bit copies
 int launch_pixel_shuffle2(hipStream_t st, const bf16_t* x, int ld_x, int B, int H, int W, int Co, bf16_t* out, int ld_out);
 
+// ---- line-art hinter kernels (kernels_inorm.hip) ----------------------------------
+// Instance normalisation over NHWC rows [B][HW] of stride ld (C = 64, 128 or 256 live channels): stats [B][C][2] = (mean, rstd) with the
+// biased variance, fp32, shifted sums in a fixed order (512-row chunks, then the chunks in eight interleaved slices, then the slices): a sample's statistics do
+// not depend on B.  partial: inorm_partial_floats(B, HW, C) floats of scratch
+size_t inorm_partial_floats(int B, size_t HW, int C);
+int launch_inorm_stats(hipStream_t st, const bf16_t* x, int ld, int B, size_t HW, int C, float eps, float* partial, float* stats);
+// out = relu?((x - mean) * rstd) (+ res), fp32, one rounding, over the logical image [B][H][W][C] (dense, pixel stride C):
+//   shuffled  x is [B][H/2][W/2][(a, b, C)], pixel (2i + a, 2j + b) at row (i, j), columns (2a + b) C + c (a sub-pixel transposed conv's output)
+//   res       an image of the same logical size stored with a border of res_pad pixels, [B][H + 2 res_pad][W + 2 res_pad][C]
+//   pad       0, 1 or 3 (< H, W): out is [B][H + 2 pad][W + 2 pad][C] with nn.ReflectionPad2d's mirrored border
+//   patch     out is [B][H][W][4 C]: row (y, x) holds pixels (y + dy, x + dx) in (dy, dx, c) order, zeros past the last row / column (pad 0)
+struct InormApply {
+    const bf16_t* x = nullptr; const float* stats = nullptr; const bf16_t* res = nullptr; bf16_t* out = nullptr;
+    int B = 0, H = 0, W = 0, C = 0;
+    int shuffled = 0, relu = 0, res_pad = 0, pad = 0, patch = 0;
+};
+int inorm_apply_check(const InormApply& a);              // the launch's argument checks alone (no device call)
+int launch_inorm_apply(hipStream_t st, const InormApply& a);
+// ConvTranspose2d(k 3, s 2, p 1, output_padding 1) weight [Cin][Cout][3][3] of a runtime dtype -> out [4 Cout][4 Cin] storage: rows
+// (a, b, co) of the output parity, columns (dy, dx, ci) of the 2x2 source patch; a = 0: ky = 1 at dy = 0; a = 1: ky = 2 at dy = 0, ky = 0
+// at dy = 1 (columns alike); the other 7 of the 16 blocks are zero
+int launch_tconv_compose(hipStream_t st, const void* w, int dtype, int Cin, int Cout, bf16_t* out);
+// 7x7 / reflection padding 3 convolution of x NHWC [B][H][W][8] (3 live channels) into 64 channels: Wt [64][7][7][8], bias [64], out
+// NHWC [B][H][W][64]; H, W >= 4
+int launch_conv7_in(hipStream_t st, const bf16_t* x, int B, int H, int W, const bf16_t* Wt, const float* bias, bf16_t* out);
+// 7x7 / no padding convolution of xp NHWC [B][Ho + 6][Wo + 6][64] into ONE channel: Wt [7][7][64], bias [1], optional sigmoid, out NCHW
+// [B][1][Ho][Wo] of a runtime dtype
+int launch_conv7_out(hipStream_t st, const bf16_t* xp, int B, int Ho, int Wo, const bf16_t* Wt, const float* bias, int sigmoid,
+                     void* out, int out_dtype);
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

@@ -1,5 +1,5 @@
 // Model runtime internals shared by model.hip (forward graphs + C ABI), model_vjp.hip (input-gradient graphs), model_ctrl.hip,
-// model_t2i.hip and, through model_upscaler.h, the upscaler graphs (model_rrdb.hip, model_swinir.hip, model_hat.hip): workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
+// model_t2i.hip and, through model_upscaler.h, the upscaler graphs (model_rrdb.hip, model_swinir.hip, model_hat.hip) and the line-art graph (model_lineart.hip): workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
 #pragma once
 #include "../../include/gyre_hip.h"
 #include "kernels.h"
@@ -92,7 +92,11 @@ struct Tn {  // NHWC bf16 activation (or a raw byte buffer when C == 0)
 enum ParamKind { PK_CONV3 = 0, PK_MAT = 1, PK_VEC = 2, PK_MAT_GEGLU = 3, PK_VEC_GEGLU = 4,
                  // SwinIR (model_swinir.hip): a fused qkv projection [3 heads 30][I] whose 30-row groups (q, k, v of every head) land at
                  // 32-row pitch, rows 30 and 31 of a group staying the zeros of the allocation; its bias likewise; a plain fp32 table
-                 PK_MAT_HEAD30 = 5, PK_VEC_HEAD30 = 6, PK_TABLE_F32 = 7 };
+                 PK_MAT_HEAD30 = 5, PK_VEC_HEAD30 = 6, PK_TABLE_F32 = 7,
+                 // line-art hinter (model_lineart.hip): a 7x7 convolution [O][7][7][i_pad]; a ConvTranspose2d(3, s 2, p 1, op 1) weight
+                 // [I][O][3][3] composed into its sub-pixel matrix [4 O][4 I] (launch_tconv_compose), and that layer's bias written once
+                 // per output parity, [4][O]
+                 PK_CONV7 = 8, PK_TCONV_SUBPIX = 9, PK_VEC_REP4 = 10 };
 struct Param {
     std::string key;
     std::vector<int64_t> shape;  // PyTorch shape expected from the caller
@@ -271,6 +275,11 @@ struct Store {
                 }
                 break;
             }
+            case PK_CONV7: TRY(launch_repack_conv(st, src, dtype, O, (int)p.shape[1], 7, 7, p.i_pad, (bf16_t*)p.dev)); break;
+            case PK_TCONV_SUBPIX: TRY(launch_tconv_compose(st, src, dtype, O, (int)p.shape[1], (bf16_t*)p.dev)); break;
+            case PK_VEC_REP4:
+                for (int q = 0; q < 4; ++q) TRY(launch_cast_f32(st, src, dtype, (size_t)O, 0, (float*)p.dev + (size_t)q * O));
+                break;
             case PK_TABLE_F32: {
                 size_t n = 1;
                 for (auto d : p.shape) n *= (size_t)d;
@@ -1921,8 +1930,8 @@ struct gyre_vae : DebugTaps {
 };
 
 // ------------------------------------------------------------------------------------------
-// C ABI bodies the handle types share (gyre_{unet,vae,ctrl,t2i,rrdb,swinir,hat}_create / _num_params / _param_key / _finalize;
-// _set_weight where it does no more than this: t2i, rrdb, swinir, hat)
+// C ABI bodies the handle types share (gyre_{unet,vae,ctrl,t2i,rrdb,swinir,hat,lineart}_create / _num_params / _param_key / _finalize;
+// _set_weight where it does no more than this: t2i, rrdb, swinir, hat, lineart)
 // ------------------------------------------------------------------------------------------
 template <typename H, typename Cfg> static int handle_create(const Cfg* cfg, int device, H** out) {
     if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
@@ -1950,7 +1959,7 @@ template <typename H> static int handle_set_weight(H* h, const char* key, const 
     h->finalized = false;
     return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
 }
-// the two below: handles of the image-in / image-out shape (gyre_{rrdb,swinir,hat}), whose run(dry, stream, image, dtype, B, H, W,
+// the two below: handles of the image-in / image-out shape (gyre_{rrdb,swinir,hat,lineart}), whose run(dry, stream, image, dtype, B, H, W,
 // workspace, bytes, out, dtype) sizes the workspace when dry
 template <typename H> static size_t handle_workspace_bytes(H* h, int B, int H_, int W) {
     if (!h) return 0;

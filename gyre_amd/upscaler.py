@@ -43,7 +43,7 @@ _UNSHUFFLE = {4: 1, 2: 2, 1: 4}          # model scale -> pixel-unshuffle factor
 class _NativeUpscaler(_NativeModule):
     """What the three upscaler shells share: the configuration merge, the parameter tree with the family's buffers, the workspace
     query and the native call (gyre_{kind}_workspace_bytes / gyre_{kind}_forward).  A family names its configuration
-    (``_make_config``, ``_param_shapes``, the keys of its channel count and scale), its buffers (``_is_buffer``, ``_buffer_dtype``) and
+    (``_make_config``, ``_param_shapes``, the keys of its channel count and scale - ``_scale_key = None``: the output has the input's scale), its buffers (``_is_buffer``, ``_buffer_dtype``) and
     its size rule (``_padding``), and builds its C configuration (``_c_cfg``)."""
 
     _make_config = _param_shapes = None
@@ -55,9 +55,15 @@ class _NativeUpscaler(_NativeModule):
         super().__init__()
         cfg = dict(config or {})
         cfg.update(kw)
-        self.config = type(self)._make_config(**cfg)
-        self._scale = self.config[self._scale_key]
-        self._window_size = self.config.get("window_size", 32)
+        self._adopt(type(self)._make_config(**cfg))
+
+    def _adopt(self, config) -> None:
+        """The checked configuration -> what a pipeline reads from the module (``_scale``: 1 for a family that names no scale key;
+        ``_window_size``) and the parameter tree with the family's buffers.  A family whose constructor has its own signature calls
+        this after ``_NativeModule.__init__``."""
+        self.config = config
+        self._scale = config[self._scale_key] if self._scale_key else 1
+        self._window_size = config.get("window_size", 32)
         shapes = self._shapes()
         _build_tree(self, {k: v for k, v in shapes.items() if not self._is_buffer(k)})
         for key, shape in shapes.items():

@@ -308,6 +308,28 @@ def rrdb_param_shapes(cfg) -> Shapes:
     return s
 
 
+def lineart_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``DrawingGenerator`` (gyre/pipeline/hinters/models/informative_drawings.py) in
+    state_dict() order; the ``model3`` weights have ConvTranspose2d's [Cin, Cout, 3, 3] layout, the affine-free instance
+    normalisations have no entries.  cfg: a mapping as gyre_amd.config.lineart_config returns."""
+    s: Shapes = OrderedDict()
+
+    def conv(p, o, i, k, transposed=False):
+        s[p + ".weight"] = (i, o, k, k) if transposed else (o, i, k, k)
+        s[p + ".bias"] = (o,)
+
+    conv("model0.1", 64, cfg["input_nc"], 7)
+    conv("model1.0", 128, 64, 3)
+    conv("model1.3", 256, 128, 3)
+    for i in range(cfg["n_residual_blocks"]):
+        conv(f"model2.{i}.conv_block.1", 256, 256, 3)
+        conv(f"model2.{i}.conv_block.5", 256, 256, 3)
+    conv("model3.0", 128, 256, 3, transposed=True)
+    conv("model3.3", 64, 128, 3, transposed=True)
+    conv("model4.1", cfg["output_nc"], 64, 7)
+    return s
+
+
 class _WindowShapes:
     """The entries the SwinIR and HAT state dicts are made of, appended to ``s`` in call order: cfg gives the width and the MLP ratio."""
 

@@ -188,9 +188,30 @@ typedef struct {
     float overlap_ratio;             /* 0.5 */
 } gyre_hat_cfg;
 
+/* Line-art hinter (the reference's gyre/pipeline/hinters/models/informative_drawings.py, DrawingGenerator; its three engines
+ * hinters-lineart-anime / -contour / -opensketch are all input_nc 3, output_nc 1, n_residual_blocks 3).  Built: input_nc 3,
+ * output_nc 1, 1 to 16 residual blocks, sigmoid 0 or 1. */
+typedef struct {
+    int32_t input_nc;                /* 3 */
+    int32_t output_nc;               /* 1 */
+    int32_t n_residual_blocks;       /* 3 as shipped, 9 the constructor's default (1 .. 16) */
+    int32_t sigmoid;                 /* 1: the closing nn.Sigmoid */
+} gyre_lineart_cfg;
+
+/* One launch of the instance-normalisation apply pass (kernels_inorm.hip), for tests: out = relu?((x - mean) * rstd) (+ res) over the
+ * logical image [B][H][W][C].  shuffled: x is [B][H/2][W/2][(a, b, C)] (a sub-pixel transposed convolution's output); res: the same
+ * logical image stored with a border of res_pad pixels; pad 0 / 1 / 3: out is [B][H + 2 pad][W + 2 pad][C] with a mirrored border;
+ * patch: out is [B][H][W][4 C], the 2x2 patch (y + dy, x + dx) in (dy, dx, c) order with zeros past the last row / column. */
+typedef struct {
+    const void* x; const float* stats; const void* res; void* out;
+    int32_t B, H, W, C;
+    int32_t shuffled, relu, res_pad, pad, patch;
+} gyre_inorm_apply_args;
+
 typedef struct gyre_unet gyre_unet;
 typedef struct gyre_swinir gyre_swinir;
 typedef struct gyre_hat gyre_hat;
+typedef struct gyre_lineart gyre_lineart;
 typedef struct gyre_vae gyre_vae;
 typedef struct gyre_t2i gyre_t2i;
 typedef struct gyre_ctrl gyre_ctrl;
@@ -495,6 +516,25 @@ size_t gyre_hat_workspace_bytes(gyre_hat* h, int B, int H, int W);
  * result does not depend on the batch it runs in. */
 int gyre_hat_forward(gyre_hat* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                      void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
+
+/* ---- line-art hinter -------------------------------------------------------
+ * Replaces the host model behind the reference's edge_detection task for the informative-drawings engines (services/generate.py:315-317).
+ * Weight keys, in the reference's state-dict order (.weight and .bias each): model0.1, model1.0, model1.3, model2.{i}.conv_block.1,
+ * model2.{i}.conv_block.5, model3.0, model3.3 (ConvTranspose2d layout [Cin, Cout, 3, 3]), model4.1.  The instance normalisations are
+ * affine-free and have no keys.  Same weight store, workspace and dry-run sizing rules as the other handles.  A configuration outside
+ * the built list (gyre_lineart_cfg): GYRE_ERR_UNSUPPORTED at create. */
+int gyre_lineart_create(const gyre_lineart_cfg* cfg, int device, gyre_lineart** out);
+void gyre_lineart_destroy(gyre_lineart* h);
+int gyre_lineart_num_params(const gyre_lineart* h);
+const char* gyre_lineart_param_key(const gyre_lineart* h, int i);
+int gyre_lineart_set_weight(gyre_lineart* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_lineart_finalize(gyre_lineart* h, void* stream);
+size_t gyre_lineart_workspace_bytes(gyre_lineart* h, int B, int H, int W);
+/* out[B, 1, Ho, Wo] = DrawingGenerator(image[B, 3, H, W]) with Ho = 4 ceil(ceil(H / 2) / 2) (= H when H % 4 == 0; W alike), the size
+ * the reference's layers produce.  H, W >= 5 (GYRE_ERR_INVALID below: torch's reflection paddings refuse those too).  A sample's
+ * result does not depend on the batch it runs in. */
+int gyre_lineart_forward(gyre_lineart* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                         void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -933,6 +973,24 @@ int gyre_op_chan_gate(void* stream, const float* pool, int B, int C, int Cs, con
                       const float* b2, float scale, float* s, int ld_s);
 int gyre_op_scale_add(void* stream, void* y, int ldy, const void* c2, int ldc, const float* s, int ld_s, int B, size_t HW, int Cn);
 int gyre_op_pixel_shuffle2(void* stream, const void* x, int ld_x, int B, int H, int W, int Co, void* out, int ld_out);
+/* The kernels of the line-art hinter (kernels_inorm.hip), one launch each.
+ * inorm_stats: stats[b][c] = (mean, rstd) over the HW rows (stride ld) of x, biased variance, c < C = 64 / 128 / 256, fp32 in a fixed
+ * order; partial = gyre_op_inorm_workspace bytes.  inorm_apply: see gyre_inorm_apply_args.  tconv_compose: a ConvTranspose2d(3, stride 2,
+ * padding 1, output_padding 1) weight [Cin][Cout][3][3] of a runtime dtype -> its sub-pixel matrix [4 Cout][4 Cin] in the storage type,
+ * rows (a, b, co), columns (dy, dx, ci), 7 of the 16 blocks zero.  conv7_in: reflection padding 3 + 7x7 conv of the 8-channel NHWC entry
+ * tensor (3 live) into NHWC 64; w [64][3][7][7] of w_dtype, w_scratch 64 * 49 * 8 storage elements.  conv7_out: 7x7 conv of the pad-3
+ * NHWC image [B][Ho + 6][Wo + 6][64] into one NCHW plane of out_dtype, + bias, optional sigmoid; w [1][64][7][7], w_scratch 49 * 64. */
+/* conv3x3_valid: the planner convolution in the form the line-art graph runs over a reflect-padded image - no padding, stride 1,
+ * y NHWC [B][Hi - 2][Wi - 2][Cout] from x NHWC [B][Hi][Wi][Cin], w [Cout][3][3][Cin] storage, planned as if each sample ran alone. */
+int gyre_op_conv3x3_valid(void* stream, const void* x, int B, int Hi, int Wi, int Cin, const void* w, int Cout, const float* bias, void* y);
+size_t gyre_op_inorm_workspace(int B, size_t HW, int C);
+int gyre_op_inorm_stats(void* stream, const void* x, int ld, int B, size_t HW, int C, float eps, float* partial, float* stats);
+int gyre_op_inorm_apply(void* stream, const gyre_inorm_apply_args* args);
+int gyre_op_tconv_compose(void* stream, const void* w, int dtype, int Cin, int Cout, void* out);
+int gyre_op_conv7_in(void* stream, const void* x8, int B, int H, int W, const void* w, int w_dtype, void* w_scratch, const float* bias,
+                     void* out);
+int gyre_op_conv7_out(void* stream, const void* xp, int B, int Ho, int Wo, const void* w, int w_dtype, void* w_scratch, const float* bias,
+                      int sigmoid, void* out, int out_dtype);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
