@@ -102,6 +102,18 @@ class LineartCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_nc", "output_nc", "n_residual_blocks", "sigmoid")]
 
 
+class HedCfg(C.Structure):
+    """gyre_hed_cfg (include/gyre_hip.h): the network has no constructor arguments."""
+    _fields_ = [("reserved", C.c_int32)]
+
+
+class HedFuseArgs(C.Structure):
+    """gyre_hed_fuse_args (include/gyre_hip.h): one launch of the HED fuse kernel, for tests."""
+    _fields_ = [("so", C.c_void_p * 5)] + [(n, C.c_int32 * 5) for n in ("Hk", "Wk", "oy", "ox")] + \
+               [("wf", C.c_void_p), ("bf", C.c_void_p), ("out", C.c_void_p), ("out_dtype", C.c_int32)] + \
+               [(n, C.c_int32) for n in ("B", "H", "W")]
+
+
 class InormApplyArgs(C.Structure):
     """gyre_inorm_apply_args (include/gyre_hip.h): one launch of the instance-normalisation apply pass, for tests."""
     _fields_ = [(n, C.c_void_p) for n in ("x", "stats", "res", "out")] + \
@@ -317,9 +329,13 @@ _SIGS = {
     "gyre_op_tconv_compose": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "gyre_op_conv7_in": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "gyre_op_conv7_out": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    "gyre_hed_geometry": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gyre_op_hed_entry": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "gyre_op_hed_tail": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gyre_op_hed_fuse": (_i, [_vp, C.POINTER(HedFuseArgs)]),
 }
-# the handle surface of the three upscaler families and of the line-art hinter: image in, image out
-for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg)):
+# the handle surface of the three upscaler families and of the two hinters: image in, image out
+for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg), ("hed", HedCfg)):
     _SIGS.update({f"gyre_{_kind}_create": (_i, [C.POINTER(_cfg), _i, C.POINTER(_vp)]),
                   f"gyre_{_kind}_destroy": (None, [_vp]),
                   f"gyre_{_kind}_num_params": (_i, [_vp]),

@@ -238,6 +238,23 @@ def tiny_lineart(**kw) -> LineartConfig:
     return lineart_config(**{**dict(input_nc=3, output_nc=1, n_residual_blocks=1, sigmoid=False), **kw})
 
 
+class HedConfig(_AttrDict):
+    """Configuration of the HED edge detector: the reference's ``HED`` (gyre/pipeline/hinters/models/hed.py) takes no constructor
+    arguments, so the mapping holds the one fact its shell asks for - the three input channels."""
+
+
+def hed_config(**kw) -> HedConfig:
+    if kw:
+        raise NotImplementedError(f"HED: {sorted(kw)} are not arguments of the HED constructor, which has none "
+                                  f"(a configuration of another model family?)")
+    return HedConfig(input_nc=3)
+
+
+# the VGG trunk of HED: convolutions per stage and their width
+HED_STAGES = ((2, 64), (2, 128), (3, 256), (3, 512), (3, 512))
+HED_BORDER = 34                    # conv1_1's padding 35, less the ordinary 1
+
+
 class SwinIRConfig(_AttrDict):
     """Configuration of a SwinIR upscaler - the keyword arguments of the reference's ``SwinIR`` constructor
     (gyre/pipeline/upscalers/models/network_swinir.py:651-657): a mapping that also reads as attributes."""

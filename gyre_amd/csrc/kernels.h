@@ -254,6 +254,29 @@ int launch_conv7_in(hipStream_t st, const bf16_t* x, int B, int H, int W, const 
 int launch_conv7_out(hipStream_t st, const bf16_t* xp, int B, int Ho, int Wo, const bf16_t* Wt, const float* bias, int sigmoid,
                      void* out, int out_dtype);
 
+// ---- HED edge-detector kernels (kernels_hed.hip) ------------------------------------
+// entry: x NCHW [B][3][H][W] of a runtime dtype -> y NHWC storage [B][H + 68][W + 68][8]: the image inside a zero border of HED_BORDER
+// pixels, channels 3 .. 7 zero (conv1_1's padding 35 = this border + the planner's padding 1)
+constexpr int HED_BORDER = 34;
+int launch_hed_entry(hipStream_t st, const void* x, int dtype, int B, int H, int W, bf16_t* y);
+// The end of a VGG stage over its last convolution BEFORE the ReLU, x NHWC [B][Hs][Ws][C], C = 64 / 128 / 256 / 512, read once:
+//   pool [B][ceil(Hs / 2)][ceil(Ws / 2)][C] = relu(max over the 2x2 ceil-mode window), exact; null: not written (stage 5)
+//   so   [B][Hs][Ws] fp32 = bias[0] + sum_c w[c] relu(x[c]), fp32 in an order that depends on C alone
+int hed_tail_check(const bf16_t* x, int B, int Hs, int Ws, int C, const float* w, const float* bias, const bf16_t* pool, const float* so);
+int launch_hed_tail(hipStream_t st, const bf16_t* x, int B, int Hs, int Ws, int C, const float* w, const float* bias, bf16_t* pool, float* so);
+// out [6][B][1][H][W] of out_dtype = sigmoid of (so1 .. so5 cropped, their fuse): so[0] [B][Hk[0]][Wk[0]] read at (y + oy[0], x + ox[0]);
+// so[k], k = 1 .. 4, through the bilinear transposed convolution of kernel 2 s and stride s = 1 << k, whose (Hk[k] + 1) s image is read
+// at (y + oy[k], x + ox[k]); fuse = bf[0] + sum_k wf[k] l_k.  All fp32, one rounding.
+struct HedFuse {
+    const float* so[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int Hk[5] = {0, 0, 0, 0, 0}, Wk[5] = {0, 0, 0, 0, 0}, oy[5] = {0, 0, 0, 0, 0}, ox[5] = {0, 0, 0, 0, 0};
+    const float* wf = nullptr; const float* bf = nullptr;
+    void* out = nullptr; int out_dtype = 0;
+    int B = 0, H = 0, W = 0;
+};
+int hed_fuse_check(const HedFuse& a);                    // the launch's argument checks alone (no device call)
+int launch_hed_fuse(hipStream_t st, const HedFuse& a);
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

@@ -1,5 +1,5 @@
 // Model runtime internals shared by model.hip (forward graphs + C ABI), model_vjp.hip (input-gradient graphs), model_ctrl.hip,
-// model_t2i.hip and, through model_upscaler.h, the upscaler graphs (model_rrdb.hip, model_swinir.hip, model_hat.hip) and the line-art graph (model_lineart.hip): workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
+// model_t2i.hip and, through model_upscaler.h, the upscaler graphs (model_rrdb.hip, model_swinir.hip, model_hat.hip) and the hinter graphs (model_lineart.hip, model_hed.hip): workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
 #pragma once
 #include "../../include/gyre_hip.h"
 #include "kernels.h"
@@ -92,6 +92,7 @@ struct Tn {  // NHWC bf16 activation (or a raw byte buffer when C == 0)
 enum ParamKind { PK_CONV3 = 0, PK_MAT = 1, PK_VEC = 2, PK_MAT_GEGLU = 3, PK_VEC_GEGLU = 4,
                  // SwinIR (model_swinir.hip): a fused qkv projection [3 heads 30][I] whose 30-row groups (q, k, v of every head) land at
                  // 32-row pitch, rows 30 and 31 of a group staying the zeros of the allocation; its bias likewise; a plain fp32 table
+                 // (PK_TABLE_F32 also holds the HED side scores and score_final, model_hed.hip: 1x1 convolutions to one channel read as fp32 vectors)
                  PK_MAT_HEAD30 = 5, PK_VEC_HEAD30 = 6, PK_TABLE_F32 = 7,
                  // line-art hinter (model_lineart.hip): a 7x7 convolution [O][7][7][i_pad]; a ConvTranspose2d(3, s 2, p 1, op 1) weight
                  // [I][O][3][3] composed into its sub-pixel matrix [4 O][4 I] (launch_tconv_compose), and that layer's bias written once
@@ -1930,8 +1931,8 @@ struct gyre_vae : DebugTaps {
 };
 
 // ------------------------------------------------------------------------------------------
-// C ABI bodies the handle types share (gyre_{unet,vae,ctrl,t2i,rrdb,swinir,hat,lineart}_create / _num_params / _param_key / _finalize;
-// _set_weight where it does no more than this: t2i, rrdb, swinir, hat, lineart)
+// C ABI bodies the handle types share (gyre_{unet,vae,ctrl,t2i,rrdb,swinir,hat,lineart,hed}_create / _num_params / _param_key / _finalize;
+// _set_weight where it does no more than this: t2i, rrdb, swinir, hat, lineart, hed)
 // ------------------------------------------------------------------------------------------
 template <typename H, typename Cfg> static int handle_create(const Cfg* cfg, int device, H** out) {
     if (!cfg || !out) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
@@ -1959,7 +1960,7 @@ template <typename H> static int handle_set_weight(H* h, const char* key, const 
     h->finalized = false;
     return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
 }
-// the two below: handles of the image-in / image-out shape (gyre_{rrdb,swinir,hat,lineart}), whose run(dry, stream, image, dtype, B, H, W,
+// the two below: handles of the image-in / image-out shape (gyre_{rrdb,swinir,hat,lineart,hed}), whose run(dry, stream, image, dtype, B, H, W,
 // workspace, bytes, out, dtype) sizes the workspace when dry
 template <typename H> static size_t handle_workspace_bytes(H* h, int B, int H_, int W) {
     if (!h) return 0;

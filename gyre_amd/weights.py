@@ -330,6 +330,28 @@ def lineart_param_shapes(cfg) -> Shapes:
     return s
 
 
+def hed_param_shapes(cfg=None) -> Shapes:
+    """State-dict keys and shapes of the reference's ``HED`` (gyre/pipeline/hinters/models/hed.py) in state_dict() order: the 13 VGG
+    convolutions, the five side scores and ``score_final`` - 38 entries; the bilinear ``weight_deconv*`` buffers are not persistent.
+    The network has no configuration (cfg is accepted and ignored, for the shells that pass theirs)."""
+    from .config import HED_STAGES
+    s: Shapes = OrderedDict()
+
+    def conv(p, o, i, k):
+        s[p + ".weight"] = (o, i, k, k)
+        s[p + ".bias"] = (o,)
+
+    cin = 3
+    for k, (n, width) in enumerate(HED_STAGES):
+        for j in range(n):
+            conv(f"conv{k + 1}_{j + 1}", width, cin, 3)
+            cin = width
+    for k, (_, width) in enumerate(HED_STAGES):
+        conv(f"score_dsn{k + 1}", 1, width, 1)
+    conv("score_final", 1, 5, 1)
+    return s
+
+
 class _WindowShapes:
     """The entries the SwinIR and HAT state dicts are made of, appended to ``s`` in call order: cfg gives the width and the MLP ratio."""
 

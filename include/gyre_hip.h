@@ -208,7 +208,26 @@ typedef struct {
     int32_t shuffled, relu, res_pad, pad, patch;
 } gyre_inorm_apply_args;
 
+/* HED edge detector (the reference's gyre/pipeline/hinters/models/hed.py, HED; its engines hinters-hed / hinters-hed-alt).  The network
+ * has no constructor arguments. */
+typedef struct {
+    int32_t reserved;                /* 0 */
+} gyre_hed_cfg;
+
+/* One launch of the HED fuse kernel (kernels_hed.hip), for tests: out [6][B][1][H][W] of out_dtype = sigmoid of so1 .. so5 (cropped) and
+ * of their fuse.  so[k]: fp32 [B][Hk[k]][Wk[k]]; so[0] is read at (y + oy[0], x + ox[0]), so[k] (k = 1 .. 4) through its bilinear
+ * transposed convolution of kernel 2 s, stride s = 1 << k, whose (Hk[k] + 1) s image is read at (y + oy[k], x + ox[k]); wf [5], bf [1]:
+ * score_final. */
+typedef struct {
+    const float* so[5];
+    int32_t Hk[5], Wk[5], oy[5], ox[5];
+    const float* wf; const float* bf;
+    void* out; int32_t out_dtype;
+    int32_t B, H, W;
+} gyre_hed_fuse_args;
+
 typedef struct gyre_unet gyre_unet;
+typedef struct gyre_hed gyre_hed;
 typedef struct gyre_swinir gyre_swinir;
 typedef struct gyre_hat gyre_hat;
 typedef struct gyre_lineart gyre_lineart;
@@ -535,6 +554,27 @@ size_t gyre_lineart_workspace_bytes(gyre_lineart* h, int B, int H, int W);
  * result does not depend on the batch it runs in. */
 int gyre_lineart_forward(gyre_lineart* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                          void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
+
+/* ---- HED edge detector -----------------------------------------------------
+ * Replaces the host model behind the reference's edge_detection task for the hinters-hed engines.  Weight keys, in the reference's
+ * state-dict order (.weight and .bias each): conv1_1, conv1_2, conv2_1, conv2_2, conv3_1 .. conv3_3, conv4_1 .. conv4_3, conv5_1 ..
+ * conv5_3, score_dsn1 .. score_dsn5, score_final (38 entries; the bilinear weight_deconv buffers are not persistent and have no keys).
+ * Same weight store, workspace and dry-run sizing rules as the other handles. */
+int gyre_hed_create(const gyre_hed_cfg* cfg, int device, gyre_hed** out);
+void gyre_hed_destroy(gyre_hed* h);
+int gyre_hed_num_params(const gyre_hed* h);
+const char* gyre_hed_param_key(const gyre_hed* h, int i);
+int gyre_hed_set_weight(gyre_hed* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_hed_finalize(gyre_hed* h, void* stream);
+size_t gyre_hed_workspace_bytes(gyre_hed* h, int B, int H, int W);
+/* out[6][B][1][H][W] = HED(image[B, 3, H, W]): the five side outputs and their fuse, each already sigmoided, in the reference's order.
+ * H, W >= 1; B (H + 68)(W + 68) < 2^30 (GYRE_ERR_INVALID otherwise, before any launch).  A sample's result does not depend on the batch
+ * it runs in. */
+int gyre_hed_forward(gyre_hed* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                     void* workspace, size_t workspace_bytes, void* out, int out_dtype);
+/* The geometry of an image side n: sizes[5] = n + 68 and its ceil halves, offsets[5] = the crop offsets int(round(d / 2.)) of the five
+ * maps, halves to even as Python rounds. */
+int gyre_hed_geometry(int n, int32_t* sizes, int32_t* offsets);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -991,6 +1031,14 @@ int gyre_op_conv7_in(void* stream, const void* x8, int B, int H, int W, const vo
                      void* out);
 int gyre_op_conv7_out(void* stream, const void* xp, int B, int Ho, int Wo, const void* w, int w_dtype, void* w_scratch, const float* bias,
                       int sigmoid, void* out, int out_dtype);
+/* The kernels of the HED edge detector (kernels_hed.hip), one launch each.
+ * hed_entry: x NCHW [B][3][H][W] of dtype -> y NHWC storage [B][H + 68][W + 68][8], the image inside a 34-pixel zero border, channels
+ * 3 .. 7 zero.  hed_tail: x NHWC storage [B][Hs][Ws][C] (C = 64 / 128 / 256 / 512; a stage's last convolution before its ReLU) ->
+ * pool [B][ceil(Hs / 2)][ceil(Ws / 2)][C] = relu(max over the 2x2 ceil-mode window) (null: not written) and so [B][Hs][Ws] fp32 =
+ * bias[0] + sum_c w[c] relu(x[c]).  hed_fuse: see gyre_hed_fuse_args. */
+int gyre_op_hed_entry(void* stream, const void* x, int dtype, int B, int H, int W, void* y);
+int gyre_op_hed_tail(void* stream, const void* x, int B, int Hs, int Ws, int C, const float* w, const float* bias, void* pool, float* so);
+int gyre_op_hed_fuse(void* stream, const gyre_hed_fuse_args* args);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
