@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void k_chan_gate(const float* __restrict__ poo
     if (t < Cs) {
         float a = b1[t];
         for (int c = 0; c < C; ++c) a = fmaf(w1[(size_t)t * C + c], pool[(size_t)b * C + c], a);
-        h[t] = fmaxf(a, 0.f);
+        h[t] = a <= 0.f ? 0.f : a;                     // keeps a NaN, as torch's relu does (fmaxf would return 0)
     }
     __syncthreads();
     for (int c = t; c < ld_s; c += 256) {

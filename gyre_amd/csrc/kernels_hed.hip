@@ -82,9 +82,10 @@ __global__ __launch_bounds__(256) void k_hed_tail(const bf16_t* __restrict__ x, 
             float d = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float r = fmaxf(v[j], 0.f);
+                // compare / select, not fmaxf: fmaxf returns its other operand for a NaN, torch's relu and max_pool2d return the NaN
+                const float r = v[j] <= 0.f ? 0.f : v[j];
                 d = fmaf(wv[j], r, d);
-                m[j] = q ? fmaxf(m[j], r) : r;         // relu(max) = max(relu): pixel 0 of a window is always inside
+                m[j] = q ? ((r > m[j] || r != r) ? r : m[j]) : r;      // relu(max) = max(relu): pixel 0 of a window is always inside
             }
             dot[q] = d;
         } else if (q == 0) {

@@ -115,7 +115,8 @@ __global__ __launch_bounds__(256) void k_inorm_final(const bf16_t* __restrict__ 
     if (sl) return;
     for (int j = 1; j < 8; ++j) { s1 += sm[0][j][cl]; s2 += sm[1][j][cl]; }
     const float n = (float)HW, md = s1 / n;
-    const float var = fmaxf(s2 / n - md * md, 0.f);
+    float var = s2 / n - md * md;
+    var = var < 0.f ? 0.f : var;               // (not fmaxf: an inf or NaN in the plane gives a NaN variance, which must reach rstd)
     stats[((size_t)b * C + c) * 2] = bf16_to_f32(x[(size_t)b * HW * ld + c]) + md;
     stats[((size_t)b * C + c) * 2 + 1] = 1.f / sqrtf(var + eps);
 }
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void k_inorm_apply(InormApply a, size_t total)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         v[j] = (v[j] - ms[2 * j]) * ms[2 * j + 1];
-        if (a.relu) v[j] = fmaxf(v[j], 0.f);
+        if (a.relu) v[j] = v[j] <= 0.f ? 0.f : v[j];       // keeps a NaN, as torch's relu does (fmaxf would return 0)
     }
     if (a.res) {
         const int rp = a.res_pad;
