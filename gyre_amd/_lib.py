@@ -70,6 +70,17 @@ class T2ICfg(C.Structure):
                 ("nums_rb", C.c_int32), ("ksize", C.c_int32), ("sk", C.c_int32), ("use_conv", C.c_int32)]
 
 
+class T2ISeqCfg(C.Structure):
+    """gyre_t2i_seq_cfg (include/gyre_hip.h): kind 0 = style adapter, 1 = co-adapter fuser."""
+    _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("num_head", C.c_int32), ("n_layers", C.c_int32), ("num_token", C.c_int32),
+                ("context_dim", C.c_int32), ("unet_channels", C.c_int32 * 4)]
+
+
+class FuserInput(C.Structure):
+    """gyre_fuser_input (include/gyre_hip.h): one co-adapter's four spatial states (tokens == 0) or its token tensor."""
+    _fields_ = [("task", C.c_int32), ("tokens", C.c_int32), ("in_", C.c_void_p * 4), ("h", C.c_int32 * 4), ("w", C.c_int32 * 4)]
+
+
 class CtrlCfg(C.Structure):
     _fields_ = [("in_channels", C.c_int32), ("n_levels", C.c_int32), ("block_out_channels", C.c_int32 * MAX_LEVELS),
                 ("layers_per_block", C.c_int32), ("attn_levels", C.c_int32 * MAX_LEVELS), ("num_heads", C.c_int32 * MAX_LEVELS),
@@ -220,6 +231,15 @@ _SIGS = {
     "gyre_t2i_finalize": (_i, [_vp, _vp]),
     "gyre_t2i_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "gyre_t2i_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(_vp), _i, _i]),
+    "gyre_t2i_seq_create": (_i, [C.POINTER(T2ISeqCfg), _i, C.POINTER(_vp)]),
+    "gyre_t2i_seq_destroy": (None, [_vp]),
+    "gyre_t2i_seq_num_params": (_i, [_vp]),
+    "gyre_t2i_seq_param_key": (C.c_char_p, [_vp, _i]),
+    "gyre_t2i_seq_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
+    "gyre_t2i_seq_finalize": (_i, [_vp, _vp]),
+    "gyre_t2i_seq_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "gyre_t2i_style_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _i]),
+    "gyre_t2i_fuser_forward": (_i, [_vp, _vp, C.POINTER(FuserInput), _i, _i, _i, _vp, _sz, C.POINTER(_vp), _vp]),
     "gyre_rrdb_set_path": (_i, [_vp, _i]),
     "gyre_ctrl_create": (_i, [C.POINTER(CtrlCfg), _i, C.POINTER(_vp)]),
     "gyre_ctrl_destroy": (None, [_vp]),
@@ -333,6 +353,11 @@ _SIGS = {
     "gyre_op_hed_entry": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "gyre_op_hed_tail": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gyre_op_hed_fuse": (_i, [_vp, C.POINTER(HedFuseArgs)]),
+    "gyre_op_seq_attn_max_len": (_i, [_i]),
+    "gyre_op_seq_attn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
+    "gyre_op_quick_gelu": (_i, [_vp, _vp, _sz]),
+    "gyre_op_fuser_pool": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i]),
+    "gyre_op_fuser_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _vp, _i]),
 }
 # the handle surface of the three upscaler families and of the two hinters: image in, image out
 for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg), ("hed", HedCfg)):

@@ -186,6 +186,46 @@ def tiny_t2i(kind: str = "main", **kw) -> T2IConfig:
     return t2i_config(kind, **{"channels": (32, 64, 128, 128), **kw})
 
 
+# the reference's defaults for its two token-sequence networks (t2i_adapter/models.py: T2iAdapter_style, CoAdapterFuser; adapter.py:175, 267)
+T2I_STYLE_DEFAULTS = dict(width=1024, context_dim=768, num_head=8, n_layes=3, num_token=8)
+T2I_FUSER_DEFAULTS = dict(unet_channels=(320, 640, 1280, 1280), width=768, num_head=8, n_layes=3)
+T2I_SEQ_HEAD_DIMS = (32, 64, 96, 128)            # what the attention kernel is built for (csrc/kernels_seq.hip)
+# adapter.py ExtraCondition: the row of the fuser's task_embedding a co-adapter of that kind adds
+EXTRA_CONDITION = {"sketch": 0, "keypose": 1, "seg": 2, "depth": 3, "canny": 4, "style": 5, "color": 6, "openpose": 7}
+
+
+def _t2i_seq_config(type: str, defaults: dict, kw: dict) -> T2IConfig:
+    unknown = set(kw) - set(defaults)
+    if unknown:
+        raise TypeError(f"unknown {type} configuration keys: {sorted(unknown)}")
+    cfg = T2IConfig(type=type, **{**defaults, **kw})
+    if cfg["num_head"] < 1 or cfg["width"] % cfg["num_head"] or cfg["width"] // cfg["num_head"] not in T2I_SEQ_HEAD_DIMS:
+        raise NotImplementedError(f"{type}: width / num_head must be one of {T2I_SEQ_HEAD_DIMS}, got {cfg['width']} / {cfg['num_head']}")
+    return cfg
+
+
+def t2i_style_config(**kw) -> T2IConfig:
+    """StyleAdapter(width, context_dim, num_head, n_layes, num_token) at the reference's defaults."""
+    return _t2i_seq_config("style", T2I_STYLE_DEFAULTS, kw)
+
+
+def t2i_fuser_config(**kw) -> T2IConfig:
+    """CoAdapterFuser(unet_channels, width, num_head, n_layes) at the reference's defaults."""
+    cfg = _t2i_seq_config("fuser", T2I_FUSER_DEFAULTS, kw)
+    cfg["unet_channels"] = tuple(cfg["unet_channels"])
+    if len(cfg["unet_channels"]) != 4 or any(c < 8 or c % 8 for c in cfg["unet_channels"]):
+        raise NotImplementedError("fuser: four channel counts, each a positive multiple of 8")
+    return cfg
+
+
+def tiny_t2i_style(**kw) -> T2IConfig:
+    return t2i_style_config(**{**dict(width=64, context_dim=64, num_head=2, n_layes=2, num_token=3), **kw})
+
+
+def tiny_t2i_fuser(**kw) -> T2IConfig:
+    return t2i_fuser_config(**{**dict(unet_channels=(32, 64, 128, 128), width=64, num_head=2, n_layes=2), **kw})
+
+
 class RRDBConfig(_AttrDict):
     """Configuration of an RRDBNet upscaler (BasicSR ``RRDBNet(num_in_ch, num_out_ch, scale, num_feat, num_block, num_grow_ch)``
     plus ``plus`` for the reference's ESRGAN+ blocks): a mapping that also reads as attributes."""

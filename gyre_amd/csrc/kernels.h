@@ -224,6 +224,41 @@ int launch_scale_add(hipStream_t st, bf16_t* y, int ldy, const bf16_t* c2, int l
 // PixelShuffle(2) on NHWC: out[b][2 y + i][2 x + j][c] = x[b][y][x][4 c + 2 i + j], c < Co (a multiple of 8); bit copies
 int launch_pixel_shuffle2(hipStream_t st, const bf16_t* x, int ld_x, int B, int H, int W, int Co, bf16_t* out, int ld_out);
 
+// ---- token-sequence T2I kernels (kernels_seq.hip) ---------------------------------
+// Multi-head self-attention over the packed in_proj output (arithmetic and layouts: header of kernels_seq.hip).
+//   qkv [N L][ld_qkv] sample-major rows, q / k / v of head h at columns h D / heads D + h D / 2 heads D + h D; o [N L][ld_o], head h
+//   written at [h D, h D + D) of the N L rows and nothing else.  No mask, no bias; the scale D^-1/2 multiplies the fp32 dot products.
+// D = 32, 64, 96 or 128 and L <= seq_attn_max_len(D) (K and V of one head in LDS: 1120 / 576 / 384 / 288); GYRE_ERR_UNSUPPORTED beyond,
+// GYRE_ERR_INVALID for bad arguments, nothing written either way.  seq_attn_max_len is 0 for a head dim that is not built.
+int seq_attn_max_len(int D);
+int seq_attn_check(const bf16_t* qkv, int ld_qkv, const bf16_t* o, int ld_o, int N, int L, int heads, int D);
+int launch_seq_attn(hipStream_t st, const bf16_t* qkv, int ld_qkv, bf16_t* o, int ld_o, int N, int L, int heads, int D);
+// x sigmoid(1.702 x) in place over n contiguous elements (n % 8 == 0), fp32, one rounding
+int launch_quick_gelu(hipStream_t st, bf16_t* x, size_t n);
+// out[n][c] = silu(mean over HW of x[n][c][.]) of an NCHW storage map, rounded once (rows of stride ld_out >= C); fixed summation order
+int launch_fuser_pool(hipStream_t st, const bf16_t* x, int N, int C, size_t HW, bf16_t* out, int ld_out);
+// out[n][c][.] = x[n][c][.] (alpha[n][c] + 1), or += with accumulate = 1, over NCHW storage maps; alpha fp32 rows of stride ld_a >= C
+int launch_fuser_gain(hipStream_t st, const bf16_t* x, const float* alpha, int ld_a, int N, int C, size_t HW, bf16_t* out, int accumulate);
+// The token passes of the two graphs (model_t2i_seq.hip), element strides throughout, boundary dtypes 0 f32 / 1 bf16 / 2 f16:
+// dst[n][r][c] = ((src[n][r][c] + add0[c]) + add1[r][c]) for n < N, r < R, c < W; src, add0 [W] and add1 [R][W] each optional; fp32
+// sums in that order, one rounding.  Copies and converts rows (concat, gather), writes broadcast embedding rows, adds embeddings.
+struct SeqRows {
+    const void* src = nullptr; int src_dtype = 0; size_t src_ss = 0, src_rs = 0;      // sample stride, row stride
+    const float* add0 = nullptr; const float* add1 = nullptr;
+    void* dst = nullptr; int dst_dtype = 0; size_t dst_ss = 0, dst_rs = 0;
+    int N = 0, R = 0, W = 0;
+};
+int launch_seq_rows(hipStream_t st, const SeqRows& a);
+// out[n][t][c] = tok[n][t][c] (g[n][t][c] + 1): tok [N][T][W] contiguous and out (sample stride out_ss, row stride W) of `dtype`, g storage
+// (sample stride g_ss, row stride W); the sum and the product round in fp32 on their own, then one rounding to out
+struct SeqTokenGain {
+    const void* tok = nullptr; const bf16_t* g = nullptr; size_t g_ss = 0; void* out = nullptr; size_t out_ss = 0; int dtype = 0;
+    int N = 0, T = 0, W = 0;
+};
+int launch_seq_token_gain(hipStream_t st, const SeqTokenGain& a);
+// dst[c][r] = src[r][c]: a parameter used as x @ P, P [R][Cc] of a runtime dtype, into the row-major [Cc][i_pad] the GEMMs read
+int launch_repack_transposed(hipStream_t st, const void* src, int dtype, int R, int Cc, int i_pad, bf16_t* dst);
+
 // ---- line-art hinter kernels (kernels_inorm.hip) ----------------------------------
 // Instance normalisation over NHWC rows [B][HW] of stride ld (C = 64, 128 or 256 live channels): stats [B][C][2] = (mean, rstd) with the
 // biased variance, fp32, shifted sums in a fixed order (512-row chunks, then the chunks in eight interleaved slices, then the slices): a sample's statistics do

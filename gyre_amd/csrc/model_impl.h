@@ -97,7 +97,9 @@ enum ParamKind { PK_CONV3 = 0, PK_MAT = 1, PK_VEC = 2, PK_MAT_GEGLU = 3, PK_VEC_
                  // line-art hinter (model_lineart.hip): a 7x7 convolution [O][7][7][i_pad]; a ConvTranspose2d(3, s 2, p 1, op 1) weight
                  // [I][O][3][3] composed into its sub-pixel matrix [4 O][4 I] (launch_tconv_compose), and that layer's bias written once
                  // per output parity, [4][O]
-                 PK_CONV7 = 8, PK_TCONV_SUBPIX = 9, PK_VEC_REP4 = 10 };
+                 PK_CONV7 = 8, PK_TCONV_SUBPIX = 9, PK_VEC_REP4 = 10,
+                 // token-sequence T2I networks (model_t2i_seq.hip): a parameter P [I][O] used as x @ P, stored transposed [o_pad][i_pad]
+                 PK_MAT_T = 11 };
 struct Param {
     std::string key;
     std::vector<int64_t> shape;  // PyTorch shape expected from the caller
@@ -281,6 +283,7 @@ struct Store {
             case PK_VEC_REP4:
                 for (int q = 0; q < 4; ++q) TRY(launch_cast_f32(st, src, dtype, (size_t)O, 0, (float*)p.dev + (size_t)q * O));
                 break;
+            case PK_MAT_T: TRY(launch_repack_transposed(st, src, dtype, O, (int)p.shape[1], p.i_pad, (bf16_t*)p.dev)); break;
             case PK_TABLE_F32: {
                 size_t n = 1;
                 for (auto d : p.shape) n *= (size_t)d;

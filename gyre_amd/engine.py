@@ -26,11 +26,12 @@ into PNG artifacts.  What this class has to honour is therefore exactly what the
   * no-op memory knobs (attention / VAE slicing, xformers): 288 GB of HBM3E, the whole batch stays resident.
 
 Hint images handled by a T2I adapter (gyre_amd/t2i.py GyreHipT2IAdapter through the engine's ``hintset_manager``) run natively:
-the adapter once per request, its states added inside the UNet on every step (gyre_amd/hints.py).  Hint images handled by a ControlNet
+the adapter once per request, its states added inside the UNet on every step (gyre_amd/hints.py); style adapters and co-adapters with
+their fuser likewise (GyreHipT2IStyleAdapter / GyreHipT2IFuser: style tokens extend the text context once per request).  Hint images handled by a ControlNet
 (gyre_amd/controlnet.py GyreHipControlNet) run natively as well: the hint image and the text context are bound once per request, the
 control model runs once per UNet evaluation and its residuals go to the UNet's residual inputs (schedulers.UNetWithControlnet).
 Features outside the native hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py): depth maps /
-depth UNets, foreign hint handlers, style adapters and co-adapters, masked hints, hints together with hires fix / grafted inpaint /
+depth UNets, foreign hint handlers, masked hints, hints together with hires fix / grafted inpaint /
 CLIP guidance / shard_devices, ControlNet hints with a 9-channel inpaint UNet.  CLIP guidance
 is implemented (gyre_amd/clipguided.py over the native input-gradient sweeps).  ``lora=`` takes LoRA files (kohya-ss, diffusers) and,
 as the reference routes them (unified_pipeline.py:2210-2233: what ``detect_lora_type`` refuses goes to ``apply_lycoris``), LyCORIS files
@@ -400,12 +401,13 @@ class GyreUnifiedPipeline:
 
     def _hints(self, hint_images, mask_image) -> list:
         """The reference's hint loop (unified_pipeline.py:1994-2047) for what is native: every hint image needs exactly one model
-        from the hintset manager and that model must be a GyreHipT2IAdapter (-> hints.T2IHint) or a GyreHipControlNet
-        (-> hints.ControlNetHint; same priority and weight mapping).  Depth hints routed to a depth UNet and foreign handlers stay
+        from the hintset manager and that model must be a GyreHipT2IAdapter (-> hints.T2IHint, or hints.CoAdapterHint with the
+        hintset's fuser when it was loaded as a co-adapter), a GyreHipT2IStyleAdapter (-> hints.StyleHint with the hintset's clip_model,
+        feature_extractor, fuser and the hint's clip_layer) or a GyreHipControlNet (-> hints.ControlNetHint; same priority and weight mapping).  Depth hints routed to a depth UNet and foreign handlers stay
         NotImplementedError; a hint type nobody handles is the reference's EnvironmentError."""
         from .controlnet import GyreHipControlNet
-        from .hints import ControlNetHint, T2IHint
-        from .t2i import GyreHipT2IAdapter
+        from .hints import CoAdapterHint, ControlNetHint, StyleHint, T2IHint
+        from .t2i import GyreHipT2IAdapter, GyreHipT2IStyleAdapter
         hints = []
         for hint_image in hint_images or ():
             hint_type = hint_image.hint_type
@@ -417,8 +419,7 @@ class GyreUnifiedPipeline:
             if not handler_models:
                 raise EnvironmentError(f"Pipeline doesn't know how to handle hint image of type {hint_type}")
             models = dict(handler_models)
-            for extra in ("clip_model", "feature_extractor", "fuser"):
-                models.pop(extra, None)
+            extras = {extra: models.pop(extra, None) for extra in ("clip_model", "feature_extractor", "fuser")}
             if len(models) != 1:
                 raise ValueError(f"Unknown set of hint models: {models.keys()}")
             _, model = models.popitem()
@@ -428,10 +429,19 @@ class GyreUnifiedPipeline:
                 hints.append(ControlNetHint(model, hint_image.image, mask=None, weight=weight, soft_injection=priority != "balanced",
                                             cfg_only=priority == "hint"))
                 continue
+            common = dict(mask=None, weight=weight, soft_injection=priority != "balanced", cfg_only=priority == "hint")
+            if isinstance(model, GyreHipT2IStyleAdapter):          # t2i-adapter-style, coadapter-style (UnifiedPipelineHint_T2i, style path)
+                hints.append(StyleHint(model, hint_image.image, extras["clip_model"], extras["feature_extractor"], fuser=extras["fuser"],
+                                       clip_layer=getattr(hint_image, "clip_layer", None), **common))
+                continue
             if not isinstance(model, GyreHipT2IAdapter):
                 raise NotImplementedError(f"hint model {type(model).__name__} (ControlNet and foreign adapters are outside the native hot path)")
-            hints.append(T2IHint(model, hint_image.image, mask=None, weight=weight, soft_injection=priority != "balanced",
-                                 cfg_only=priority == "hint"))
+            if getattr(model, "_coadapter_type", False):           # coadapter/*: the states go through the hintset's fuser
+                if mask_image is not None:
+                    raise NotImplementedError("co-adapter hints together with a mask")
+                hints.append(CoAdapterHint(model, hint_image.image, extras["fuser"], **common))
+                continue
+            hints.append(T2IHint(model, hint_image.image, **common))
         return hints
 
     # ---- the generation call (keywords of reference UnifiedPipeline.__call__, unified_pipeline.py:1722-1790) ---------------

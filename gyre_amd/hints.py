@@ -6,8 +6,9 @@
                                                                     schedulers.UNetWithControlnet, unet/core.py:40-64)
 
 The adapter itself runs natively (gyre_amd/t2i.py); what is here is the per-level weighting of its states and the sums the CFG
-wrappers receive.  Style adapters, co-adapters with their fuser, and masked hints (the mask resize is an unpinned lanczos3) raise
-NotImplementedError.  The ControlNet itself runs natively too (gyre_amd/controlnet.py): its hint only decides the per-residual scales,
+wrappers receive.  T2IHint and combine_t2i_states refuse style adapters and co-adapters; those enter through StyleHint, CoAdapterHint
+and build_t2i_conditioning at the end of this file (gyre_amd/pipeline.py calls them once per request, engine._hints builds them).  Masked hints
+(the mask resize is an unpinned lanczos3) raise NotImplementedError.  The ControlNet itself runs natively too (gyre_amd/controlnet.py): its hint only decides the per-residual scales,
 which half of a CFG call the model sees and where in the shared residual buffers its outputs land; masked ControlNet hints raise for
 the same reason.
 """
@@ -37,6 +38,9 @@ class T2IHint:
                  cfg_only: bool = False):
         if getattr(model, "_coadapter_type", False):
             raise NotImplementedError("T2I co-adapters (fuser) are outside the native path")
+        self._bind(model, image, mask, weight, soft_injection, cfg_only)
+
+    def _bind(self, model, image, mask, weight, soft_injection, cfg_only):
         if image.ndim == 3:
             image = image[None]
         if mask is None and image.shape[1] == 4:
@@ -154,3 +158,177 @@ class ControlNetHint:
         else:
             self.model(x, t, scales=self.scales(), out=out, accumulate=accumulate)
         return True
+
+
+# ---- style adapters and co-adapters ---------------------------------------------------------------------------------------
+# The host side of the two token-sequence T2I networks (gyre_amd/t2i.py GyreHipT2IStyleAdapter / GyreHipT2IFuser):
+#   StyleHint                UnifiedPipelineHint_T2i, style path          unified_pipeline.py:843-854, 921-948
+#   CoAdapterHint            a spatial hint whose adapter is a co-adapter  unified_pipeline.py:886-892, 953-954
+#   build_t2i_conditioning   UNetWithT2I.__init__                          unet/core.py:103-211
+#   extend_style_context     UNetWithT2I.__call__, the context extension   unet/core.py:220-237
+# T2IHint and combine_t2i_states above keep refusing co-adapters and style states: these are the names the new capability enters by.
+def normalise_clip_layer(clip_layer, default=None):
+    """reference prompt_types.normalise_clip_layer: "final" | "penultimate" | n (the n-th hidden state from the end, n >= 3)"""
+    if clip_layer is None:
+        clip_layer = default
+    if isinstance(clip_layer, int):
+        clip_layer = abs(clip_layer)
+    if clip_layer == 0 or clip_layer == 1 or clip_layer == "final":
+        return "final"
+    if clip_layer == 2 or clip_layer == "penultimate":
+        return "penultimate"
+    return clip_layer
+
+
+class CoAdapterHint(T2IHint):
+    """A spatial hint whose adapter was loaded as a co-adapter (``model._coadapter_type`` names its condition): the weighted states go
+    through ``fuser`` together with the request's other co-adapters (build_t2i_conditioning)."""
+
+    def __init__(self, model, image: Tensor, fuser, mask: Optional[Tensor] = None, weight: float = 1.0, soft_injection: bool = False,
+                 cfg_only: bool = False):
+        cotype = getattr(model, "_coadapter_type", False)
+        if not cotype:
+            raise ValueError("CoAdapterHint needs an adapter loaded with coadapter=<condition name>")
+        if fuser is None:
+            raise ValueError("T2i Coadapter model needs a fuser model")
+        self._bind(model, image, mask, weight, soft_injection, cfg_only)      # (T2IHint's own constructor keeps refusing co-adapters)
+        self.fuser = fuser
+
+    def coadapter_type(self):
+        return getattr(self.model, "_coadapter_type", False)
+
+
+class StyleHint:
+    """One style image bound to its style adapter, the host CLIP model and its feature extractor.  Calling it returns the weighted
+    style tokens [N, num_token, context_dim].  With a model loaded as a co-adapter it needs the ``fuser`` as well."""
+
+    def __init__(self, model, image: Tensor, clip_model, feature_extractor, fuser=None, mask: Optional[Tensor] = None, weight: float = 1.0,
+                 soft_injection: bool = False, cfg_only: bool = False, clip_layer=None):
+        import warnings
+        if mask is not None:
+            warnings.warn("Style T2iAdapters don't make sense with masks - ignoring")
+        if soft_injection:
+            warnings.warn("Style T2iAdapters don't make sense with soft_injection - ignoring")
+        if clip_model is None or feature_extractor is None:
+            raise ValueError("T2i Style model needs a clip model and feature extractor")
+        if image.ndim == 3:
+            image = image[None]
+        self.model, self.image = model, normalise_tensor(image, 3)          # (an alpha plane would be the ignored mask)
+        self.weight, self.soft_injection, self.cfg_only = weight, False, cfg_only
+        self.clip_model, self.feature_extractor, self.fuser, self.clip_layer = clip_model, feature_extractor, fuser, clip_layer
+        if self.coadapter_type() and fuser is None:
+            raise ValueError("T2i Coadapter model needs a fuser model")
+        self.mean, self.std = list(feature_extractor.image_mean), list(feature_extractor.image_std)
+        size = feature_extractor.size
+        self.clip_size = size["shortest_edge"] if isinstance(size, dict) else size
+
+    def coadapter_type(self):
+        return getattr(self.model, "_coadapter_type", False)
+
+    def to(self, device=None, dtype=None):
+        self.image = self.image.to(device, dtype)
+        return self
+
+    def preprocess(self, image: Tensor) -> Tensor:
+        """rescale(image, clip_size, clip_size, "cover") and torchvision's Normalize(image_mean, image_std)"""
+        from .images import rescale
+        image = rescale(image, self.clip_size, self.clip_size, "cover")
+        mean = torch.as_tensor(self.mean, dtype=image.dtype, device=image.device).view(1, -1, 1, 1)
+        std = torch.as_tensor(self.std, dtype=image.dtype, device=image.device).view(1, -1, 1, 1)
+        return (image - mean) / std
+
+    def __call__(self) -> Tensor:
+        layer = normalise_clip_layer(self.clip_layer, "final")
+        image = self.preprocess(self.image)
+        vision = self.clip_model.vision_model
+        first = next(iter(vision.parameters()), None) if hasattr(vision, "parameters") else None
+        if first is not None:                              # the CLIP vision tower is a host (PyTorch) model, wherever it lives
+            image = image.to(first.device, first.dtype)
+        embeds = vision(image, output_hidden_states=(layer != "final"), return_dict=True)
+        if layer == "final":
+            hidden = embeds.last_hidden_state
+        elif layer == "penultimate":
+            hidden = embeds.hidden_states[-2]
+        else:
+            hidden = embeds.hidden_states[-layer]
+        result = self.model(hidden.to(device=getattr(self.model, "device", hidden.device), dtype=self.model.dtype)).to(image.dtype)
+        return result * self.weight
+
+
+def _fuse(fuser, coadapters, side):
+    """UNetWithT2I._fuse: the states of each condition summed (spatial) or concatenated (style tokens), then the fuser.  side "all":
+    every hint as it is; "either": cfg_only hints replaced by zeros."""
+    if fuser is None:
+        raise ValueError("fuser is missing")
+    summed = {}
+    for cotype, items in coadapters.items():
+        states = [(torch.zeros_like(s) if isinstance(s, Tensor) else [torch.zeros_like(t) for t in s]) if (cfg_only and side == "either") else s
+                  for s, cfg_only in items]
+        summed[cotype] = [sum(i) for i in zip(*states)] if isinstance(states[0], list) else torch.cat(states, dim=1)
+    if not summed:
+        return None, None
+    return fuser(summed)
+
+
+def build_t2i_conditioning(hints: Sequence):
+    """(states, style): states = {"u", "g", "f"} per-level sums as combine_t2i_states returns them (None without spatial states), style
+    = the style tokens [N, T, context_dim] concatenated along the sequence (None without a style hint) - the whole of
+    UNetWithT2I.__init__ over standard hints, style hints and co-adapters with their fuser."""
+    gs, us, styles, coadapters, spatial_cfg_only, fuser = [], [], [], {}, set(), None
+    for hint in hints:
+        state, cfg_only = hint(), hint.cfg_only
+        cotype = hint.coadapter_type()
+        if cotype:
+            if isinstance(state, list):
+                spatial_cfg_only.add(bool(cfg_only))
+                coadapters.setdefault(cotype, []).append((state, bool(cfg_only)))
+            else:
+                coadapters.setdefault(cotype, []).append((state, False))      # (style tokens are never zeroed, core.py:145)
+            fuser = hint.fuser
+        elif isinstance(state, list):
+            gs.append(state)
+            us.append([torch.zeros_like(s) for s in state] if cfg_only else state)
+        else:
+            styles.append(state)
+    if coadapters:
+        if len(spatial_cfg_only) <= 1:
+            cfg_only = spatial_cfg_only.pop() if spatial_cfg_only else False
+            maps, tokens = _fuse(fuser, coadapters, "all")
+            if maps is not None:
+                gs.append(maps)
+                us.append([torch.zeros_like(t) for t in maps] if cfg_only else maps)
+            if tokens is not None:
+                styles.append(tokens)
+        else:                                             # the co-adapters disagree on cfg_only: one fuse per side (core.py:177-191)
+            for guided in (True, False):
+                maps, tokens = _fuse(fuser, coadapters, "all" if guided else "either")
+                if maps is not None:
+                    (gs if guided else us).append(maps)
+                if not guided and tokens is not None:
+                    styles.append(tokens)
+    states = None
+    if gs:
+        assert len(us) == len(gs)
+        states = {"u": [sum(i) for i in zip(*us)], "g": [sum(i) for i in zip(*gs)]}
+        states["f"] = [torch.cat([u, g], dim=0) for u, g in zip(states["u"], states["g"])]
+    return states, (torch.cat(styles, dim=1) if styles else None)
+
+
+def extend_style_context(encoder_hidden_states: Tensor, style: Optional[Tensor], side: str) -> Tensor:
+    """UNetWithT2I.__call__'s context extension: the guided context gets the style tokens appended, the unconditional one its own last
+    T rows again; side "f" is cat[unconditional, guided] along the batch."""
+    if style is None:
+        return encoder_hidden_states
+    T = style.shape[1]
+    if side == "f":
+        uncond, cond = encoder_hidden_states.chunk(2)
+    elif side == "u":
+        uncond, cond = encoder_hidden_states, None
+    else:
+        uncond, cond = None, encoder_hidden_states
+    res = []
+    if uncond is not None:
+        res.append(torch.cat([uncond, uncond[:, -T:, :]], dim=1))
+    if cond is not None:
+        res.append(torch.cat([cond, style.to(cond.dtype)], dim=1))
+    return torch.cat(res, dim=0)

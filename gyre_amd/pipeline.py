@@ -339,8 +339,9 @@ class GyrePipeline:
                  t2i_hints: Optional[Sequence] = None, controlnet_hints: Optional[Sequence] = None):
         """clip_*: CLIP guidance (reference keywords of UnifiedPipeline.__call__, unified_pipeline.py:1756-1764).  The text
         side comes as ``clip_input_ids`` (encoded by clip_model.get_text_features) or ``clip_text_embeddings`` [B, D].
-        t2i_hints: gyre_amd.hints.T2IHint objects (hint image bound to its adapter).  Their states are computed once per request
-        and added inside the UNet's down path on every step.  Together with hires fix, a grafted inpaint pair or CLIP guidance
+        t2i_hints: gyre_amd.hints.T2IHint / CoAdapterHint / StyleHint objects (hint image bound to its adapter).  Their states are
+        computed once per request and added inside the UNet's down path on every step; style tokens extend the text context once
+        per request (cond -> cat[cond, style], uncond -> cat[uncond, its own last rows]).  Together with hires fix, a grafted inpaint pair or CLIP guidance
         they are refused (NotImplementedError) before any device work.
         controlnet_hints: gyre_amd.hints.ControlNetHint objects (hint image bound to its native ControlNet).  Each model runs once per
         UNet evaluation on the latents, the timestep and the text context of that evaluation; the hint image and the context are bound
@@ -493,9 +494,28 @@ class GyrePipeline:
             self._construct_leaf(leaf, generators, B)
         t2i_states = None
         if t2i_hints:                          # once per request; the states do not depend on the step (unet/core.py:125-206)
-            from .hints import combine_t2i_states
-            t2i_states = combine_t2i_states(t2i_hints)
+            from .hints import StyleHint, build_t2i_conditioning, combine_t2i_states, extend_style_context
+            style = None
+            if any(isinstance(h, StyleHint) or h.coadapter_type() for h in t2i_hints):
+                t2i_states, style = build_t2i_conditioning(t2i_hints)      # style adapters, co-adapters with their fuser
+            else:
+                t2i_states = combine_t2i_states(t2i_hints)
+            if style is not None:
+                # the style extension of the context (unet/core.py:220-237), built ONCE per request: one tensor per side, so the
+                # native UNet keeps recognising the context it already projected by tensor identity on every step
+                if added_cond is not None or style.shape[-1] != text_embeddings.shape[-1]:
+                    raise NotImplementedError(f"style tokens of width {style.shape[-1]} with a context of width {text_embeddings.shape[-1]}"
+                                              " (SDXL engines with style tokens are outside the native path)")
+                style = style.to(dev, text_embeddings.dtype)
+                if style.shape[0] == 1 and B > 1:
+                    style = style.expand(B, -1, -1)
+                if style.shape[0] != B:
+                    raise ValueError(f"hint image batch must be 1 or the number of seeds ({B})")
+                text_embeddings = extend_style_context(text_embeddings, style, "g").contiguous()
+                if do_cfg:
+                    uncond_embeddings = extend_style_context(uncond_embeddings, style, "u").contiguous()
             grow = lambda s: (s.expand(B, -1, -1, -1) if s.shape[0] == 1 and B > 1 else s).to(dev).contiguous()
+        if t2i_states is not None:             # (None: style hints alone)
             t2i_states = {k: [grow(s) for s in t2i_states[k]] for k in ("u", "g")}
             if any(s.shape[0] != B for s in t2i_states["g"]):
                 raise ValueError(f"hint image batch must be 1 or the number of seeds ({B})")

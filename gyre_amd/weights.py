@@ -283,6 +283,57 @@ def t2i_param_shapes(cfg) -> Shapes:
     return s
 
 
+def _residual_attention_shapes(s: Shapes, width: int, n_layes: int) -> None:
+    """adapter.py:150-170 ResidualAttentionBlock in the order torch registers its parameters"""
+    for i in range(n_layes):
+        p = f"transformer_layes.{i}"
+        s[p + ".attn.in_proj_weight"] = (3 * width, width)
+        s[p + ".attn.in_proj_bias"] = (3 * width,)
+        s[p + ".attn.out_proj.weight"] = (width, width)
+        s[p + ".attn.out_proj.bias"] = (width,)
+        s[p + ".ln_1.weight"] = (width,)
+        s[p + ".ln_1.bias"] = (width,)
+        s[p + ".mlp.c_fc.weight"] = (4 * width, width)
+        s[p + ".mlp.c_fc.bias"] = (4 * width,)
+        s[p + ".mlp.c_proj.weight"] = (width, 4 * width)
+        s[p + ".mlp.c_proj.bias"] = (width,)
+        s[p + ".ln_2.weight"] = (width,)
+        s[p + ".ln_2.bias"] = (width,)
+
+
+def t2i_style_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``StyleAdapter`` (adapter.py:173-185); cfg: gyre_amd.config.t2i_style_config."""
+    s: Shapes = OrderedDict()
+    w = cfg["width"]
+    s["style_embedding"] = (1, cfg["num_token"], w)
+    s["proj"] = (w, cfg["context_dim"])
+    _residual_attention_shapes(s, w, cfg["n_layes"])
+    for n in ("ln_post", "ln_pre"):
+        s[n + ".weight"] = (w,)
+        s[n + ".bias"] = (w,)
+    return s
+
+
+def t2i_fuser_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``CoAdapterFuser`` (adapter.py:266-285); cfg: gyre_amd.config.t2i_fuser_config."""
+    s: Shapes = OrderedDict()
+    w, ch = cfg["width"], tuple(cfg["unet_channels"])
+    s["task_embedding"] = (16, w)
+    s["positional_embedding"] = (len(ch), w)
+    s["seq_proj"] = (w, w)
+    for i, c in enumerate(ch):
+        s[f"spatial_feat_mapping.{i}.1.weight"] = (w, c)
+        s[f"spatial_feat_mapping.{i}.1.bias"] = (w,)
+    _residual_attention_shapes(s, w, cfg["n_layes"])
+    for n in ("ln_post", "ln_pre"):
+        s[n + ".weight"] = (w,)
+        s[n + ".bias"] = (w,)
+    for i, c in enumerate(ch):
+        s[f"spatial_ch_projs.{i}.weight"] = (c, w)
+        s[f"spatial_ch_projs.{i}.bias"] = (c,)
+    return s
+
+
 def rrdb_param_shapes(cfg) -> Shapes:
     """State-dict keys and shapes of BasicSR's ``RRDBNet`` (and of the reference's ``RRDBNet_Plus`` when cfg["plus"]: one bias-free
     ``conv1x1`` per dense block); cfg: a mapping as gyre_amd.config.tiny_rrdb returns."""

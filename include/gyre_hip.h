@@ -102,6 +102,30 @@ typedef struct {
     int32_t use_conv;                /* main: 1 = stride-2 conv downsampling (down_opt.op), 0 = 2x2 average pool */
 } gyre_t2i_cfg;
 
+/* Token-sequence T2I networks (reference gyre/pipeline/t2i_adapter/adapter.py: StyleAdapter, CoAdapterFuser): pre-LN transformers of
+ * n_layers ResidualAttentionBlocks of `width` channels and num_head heads; width / num_head must be 32, 64, 96 or 128
+ * (GYRE_ERR_UNSUPPORTED at create otherwise). */
+enum { GYRE_T2I_SEQ_STYLE = 0, GYRE_T2I_SEQ_FUSER = 1 };
+typedef struct {
+    int32_t kind;                    /* GYRE_T2I_SEQ_STYLE / GYRE_T2I_SEQ_FUSER */
+    int32_t width;                   /* 1024 (style), 768 (fuser) */
+    int32_t num_head;                /* 8 */
+    int32_t n_layers;                /* 3 (the reference spells it n_layes) */
+    int32_t num_token;               /* style: rows of style_embedding = tokens returned, 8 */
+    int32_t context_dim;             /* style: columns of proj, 768 */
+    int32_t unet_channels[4];        /* fuser: 320,640,1280,1280 (multiples of 8) */
+} gyre_t2i_seq_cfg;
+/* One entry of the fuser's ordered input (the reference's `features` dict): the ExtraCondition index of the co-adapter (sketch 0,
+ * keypose 1, seg 2, depth 3, canny 4, style 5, color 6, openpose 7) and either its four spatial states - tokens == 0, in[i] NCHW
+ * [N][unet_channels[i]][h[i]][w[i]] in the STORAGE type - or one token tensor - tokens = T > 0, in[0] [N][T][width] of the call's
+ * token dtype. */
+typedef struct {
+    int32_t task;
+    int32_t tokens;
+    const void* in[4];
+    int32_t h[4], w[4];
+} gyre_fuser_input;
+
 /* ControlNet (reference gyre/pipeline/controlnet/models.py ControlNetModel): the encoder-relevant fields of gyre_unet_cfg, the channels
  * of the hint image and the widths of its conditioning embedding. */
 typedef struct {
@@ -233,6 +257,7 @@ typedef struct gyre_hat gyre_hat;
 typedef struct gyre_lineart gyre_lineart;
 typedef struct gyre_vae gyre_vae;
 typedef struct gyre_t2i gyre_t2i;
+typedef struct gyre_t2i_seq gyre_t2i_seq;
 typedef struct gyre_ctrl gyre_ctrl;
 typedef struct gyre_rrdb gyre_rrdb;
 
@@ -475,6 +500,28 @@ size_t gyre_t2i_workspace_bytes(gyre_t2i* h, int B, int H, int W);
  * of 8; n = n_levels).  The stride-2 conv downsampling (use_conv) rounds an odd size up, the average pool down, as torch does. */
 int gyre_t2i_forward(gyre_t2i* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                      void* workspace, size_t workspace_bytes, void* const* features_out_nchw, int n, int out_dtype);
+
+/* ---- T2I style adapter and co-adapter fuser --------------------------------- */
+/* Weight keys are the state-dict keys of the reference's StyleAdapter / CoAdapterFuser (transformer_layes.{i}.attn.in_proj_weight, ...,
+ * style_embedding, proj / task_embedding, positional_embedding, spatial_feat_mapping.{i}.1, spatial_ch_projs.{i}, seq_proj); proj and
+ * seq_proj, used as x @ P, are stored transposed at load.  Same weight store, workspace and dry-run sizing rules as the other handles.
+ * workspace_bytes: style - S input tokens (n_spatial ignored); fuser - S = the token rows of all token inputs together, n_spatial = the
+ * number of spatial inputs.  A sequence longer than gyre_op_seq_attn_max_len(width / num_head) is GYRE_ERR_UNSUPPORTED (0 here). */
+int gyre_t2i_seq_create(const gyre_t2i_seq_cfg* cfg, int device, gyre_t2i_seq** out);
+void gyre_t2i_seq_destroy(gyre_t2i_seq* h);
+int gyre_t2i_seq_num_params(const gyre_t2i_seq* h);
+const char* gyre_t2i_seq_param_key(const gyre_t2i_seq* h, int i);
+int gyre_t2i_seq_set_weight(gyre_t2i_seq* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_t2i_seq_finalize(gyre_t2i_seq* h, void* stream);
+size_t gyre_t2i_seq_workspace_bytes(gyre_t2i_seq* h, int N, int S, int n_spatial);
+/* out[N][num_token][context_dim] = ln_post(blocks(ln_pre(cat[x, style_embedding]))[:, -num_token:]) @ proj over x[N][S][width]. */
+int gyre_t2i_style_forward(gyre_t2i_seq* h, void* stream, const void* x, int in_dtype, int N, int S, void* workspace, size_t workspace_bytes,
+                           void* out, int out_dtype);
+/* CoAdapterFuser.forward over the inputs in their order.  maps_out[i] NCHW storage [N][unet_channels[i]][h[i]][w[i]] = the sum over the
+ * spatial inputs of state (alpha + 1) (null when there is no spatial input); tokens_out [N][sum of T][width] of token_dtype = the
+ * token inputs, each times (x @ seq_proj + 1), concatenated in order (null when there is no token input). */
+int gyre_t2i_fuser_forward(gyre_t2i_seq* h, void* stream, const gyre_fuser_input* inputs, int n_inputs, int token_dtype, int N,
+                           void* workspace, size_t workspace_bytes, void* const* maps_out, void* tokens_out);
 
 /* ---- RRDBNet upscaler ------------------------------------------------------- */
 /* Weight keys are BasicSR's state-dict names: conv_first, body.{i}.rdb{1,2,3}.conv{1..5}.{weight,bias}, body.{i}.rdb{j}.conv1x1.weight
@@ -1039,6 +1086,21 @@ int gyre_op_conv7_out(void* stream, const void* xp, int B, int Ho, int Wo, const
 int gyre_op_hed_entry(void* stream, const void* x, int dtype, int B, int H, int W, void* y);
 int gyre_op_hed_tail(void* stream, const void* x, int B, int Hs, int Ws, int C, const float* w, const float* bias, void* pool, float* so);
 int gyre_op_hed_fuse(void* stream, const gyre_hed_fuse_args* args);
+/* The kernels of the token-sequence T2I networks (StyleAdapter, CoAdapterFuser; kernels_seq.hip), one launch each.
+ * seq_attn: multi-head self-attention over the packed in_proj output.  qkv [N L][ld_qkv] storage, sample-major rows (row n L + l), q / k
+ * / v of head h at columns h D / heads D + h D / 2 heads D + h D; o [N L][ld_o], head h written at [h D, h D + D), every other element
+ * keeps its bits.  softmax(D^-1/2 q k^T) v over the L keys of the sample: fp32 logits and statistics, probabilities and outputs rounded
+ * once; no mask, no bias.  D = 32, 64, 96 or 128 and L <= gyre_op_seq_attn_max_len(D) (1120 / 576 / 384 / 288; 0 for another D):
+ * GYRE_ERR_UNSUPPORTED beyond, GYRE_ERR_INVALID for bad arguments, nothing written either way.
+ * quick_gelu: x sigmoid(1.702 x) in place on n storage elements (n % 8 == 0), fp32 math, one rounding.
+ * fuser_pool: x NCHW storage [N][C][HW] -> out[n][c] = silu(mean over HW), storage rows of stride ld_out >= C, a fixed summation order.
+ * fuser_gain: out[n][c][.] = x[n][c][.] (alpha[n][c] + 1) (accumulate 0) or out += the same (accumulate 1) over NCHW storage maps;
+ * alpha fp32 rows of stride ld_a >= C; each fp32 operation rounds on its own, then one rounding to storage. */
+int gyre_op_seq_attn_max_len(int D);
+int gyre_op_seq_attn(void* stream, const void* qkv, int ld_qkv, void* o, int ld_o, int N, int L, int heads, int D);
+int gyre_op_quick_gelu(void* stream, void* x, size_t n);
+int gyre_op_fuser_pool(void* stream, const void* x, int N, int C, size_t HW, void* out, int ld_out);
+int gyre_op_fuser_gain(void* stream, const void* x, const float* alpha, int ld_a, int N, int C, size_t HW, void* out, int accumulate);
 /* Device-side memcpy-rate probe used by bench.py to calibrate the HBM roofline on the box. */
 int gyre_op_copy_probe(void* stream, const void* src, void* dst, size_t bytes);
 
