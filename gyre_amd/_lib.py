@@ -172,7 +172,6 @@ class DeltaTerm(C.Structure):
                 ("w1", C.c_void_p), ("O1", C.c_int), ("I1", C.c_int), ("scale", C.c_float)]
 
 
-LORA_MAX_PAIRS = 8
 DELTA_MAX_TERMS = 8
 DELTA_LORA, DELTA_HADA, DELTA_KRON, DELTA_FULL = 0, 1, 2, 3
 _vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float

@@ -105,6 +105,12 @@ __device__ __forceinline__ void store_from_f32(void* p, int dtype, size_t i, flo
     else if (dtype == 1) ((uint16_t*)p)[i] = __builtin_bit_cast(uint16_t, (__bf16)v);
     else ((__half*)p)[i] = __float2half(v);
 }
+// the source row of packed row r of a GEGLU projection [2F][I]: value and gate rows interleaved in blocks of 16 (kernels_elem.hip
+// k_repack_linear / k_cast_f32, and the delta-merge repack of kernels_lyco.hip, whose operand rows follow the source row)
+__device__ __forceinline__ int geglu_src_row(int r, int F) {
+    int p = r >> 5, i = r & 31;
+    return i < 16 ? p * 16 + i : F + p * 16 + (i - 16);
+}
 
 // ---- host side error plumbing (thread-local message, int status; nothing throws) ----
 void gyre_set_error(const std::string& msg);

@@ -99,24 +99,12 @@ int launch_repack_conv(hipStream_t st, const void* w, int dtype, int O, int I, i
 int launch_repack_linear(hipStream_t st, const void* w, int dtype, int O, int I, int geglu_interleave, bf16_t* out);
 int launch_cast_f32(hipStream_t st, const void* w, int dtype, size_t n, int geglu_interleave, float* out, float scale = 1.f);
 int launch_copy_probe(hipStream_t st, const void* src, void* dst, size_t bytes);
-// fused LoRA delta-merge repack (kernels_lora.hip): launch_repack_conv / _linear of  base + sum_j s[j] up[j] down[j]  (factors in
-// PyTorch layout, up [O][rank], down [rank][I][KH][KW], each pair in its own dtype), summed in fp32 in front of the one rounding;
-// n = 0 gives the plain repack's bits.  Operation order: header of kernels_lora.hip.
-#define GYRE_LORA_MAX_PAIRS 8
-struct LoraArgs {
-    const void* up[GYRE_LORA_MAX_PAIRS];
-    const void* down[GYRE_LORA_MAX_PAIRS];
-    int dtype[GYRE_LORA_MAX_PAIRS];
-    int rank[GYRE_LORA_MAX_PAIRS];
-    float s[GYRE_LORA_MAX_PAIRS];
-    int n = 0;
-};
-int launch_repack_lora(hipStream_t st, const void* base, int base_dtype, int O, int I, int KH, int KW, int Ipad, int geglu_interleave,
-                       float scale_p, const LoraArgs& la, bf16_t* out);
-// fused LyCORIS delta-merge repack (kernels_lyco.hip): launch_repack_lora with TERMS instead of pairs - a low-rank product (LORA), the
-// Hadamard product of two (HADA), a Kronecker product of a dense w1 with a low-rank or dense right factor (KRON), a dense diff
-// (FULL).  Operand layouts, the rank == 0 convention of a dense KRON right factor and the operation order: header of
-// kernels_lyco.hip.  Kind values are those of gyre_delta_term (include/gyre_hip.h).
+// fused delta-merge repack (kernels_lyco.hip): launch_repack_conv / _linear of  base + sum_j s[j] D_j  (operands in PyTorch layout,
+// each in its own dtype), summed in fp32 in front of the one rounding; n = 0 gives the plain repack's bits.  A TERM D_j is a
+// low-rank product (LORA: a LoRA pair, up [O][rank], down [rank][I][KH][KW]), the Hadamard product of two (HADA), a Kronecker
+// product of a dense w1 with a low-rank or dense right factor (KRON), or a dense diff (FULL).  LORA terms alone (or none) run a
+// LoRA-only instantiation of the kernel, chosen from the arguments.  Operand layouts, the rank == 0 convention of a dense KRON right
+// factor and the operation order: header of kernels_lyco.hip.  Kind values are those of gyre_delta_term (include/gyre_hip.h).
 #define GYRE_DELTA_MAX_TERMS 8
 enum { DELTA_LORA = 0, DELTA_HADA = 1, DELTA_KRON = 2, DELTA_FULL = 3 };
 struct DeltaArgs {

@@ -1101,10 +1101,6 @@ int launch_repack_conv(hipStream_t st, const void* w, int dtype, int O, int I, i
     GYRE_LAUNCH_CHECK();
     return 0;
 }
-__device__ __forceinline__ int geglu_src_row(int r, int F) {
-    int p = r >> 5, i = r & 31;
-    return i < 16 ? p * 16 + i : F + p * 16 + (i - 16);
-}
 __global__ void k_repack_linear(const void* __restrict__ w, int dtype, int O, int I, int inter,
                                 bf16_t* __restrict__ out, size_t total) {
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,5 +1,6 @@
-// Fused LyCORIS delta-merge repack (gfx950): k_repack_lora (kernels_lora.hip) generalised from low-rank PAIRS to TERMS, plus the
-// small core contraction that turns a Tucker form into an operand of such a term.
+// Fused delta-merge repack (gfx950): k_repack_conv / k_repack_linear (kernels_elem.hip) with a sum of adapter TERMS - LoRA pairs and
+// the LyCORIS forms - folded in front of the single rounding to the storage type, plus the small core contraction that turns a
+// Tucker form into an operand of such a term.
 //
 //   out[o][ky][kx][ci] = round_storage( scale_p * ( base[so, ci, ky, kx] + sum_j s_j * D_j[so, ci, ky, kx] ) )
 //
@@ -15,32 +16,43 @@
 //          d = w1[so / O2][ci / I2] * d2                                             w1 dense fp32 [O1][I1], O = O1 O2, I = I1 I2
 //   FULL   d = diff[so, ci, t]                                                       (down0)
 //
-// Operation order (fp32, restated by the host emulation in tests/lyco_ref.py - change both or neither):
+// Operation order (fp32, restated by the host emulations in tests/lora_ref.py and tests/lyco_ref.py - change all or none):
 //   acc = base
 //   for j in argument order:  d = D_j as above (HADA: d1 completely, then d2, then one multiplication)
 //                             acc = fma(s_j, d, acc)
 //   out = round_storage(acc * scale_p)                      one multiplication after the sum, as k_repack_conv applies Param::scale
-// With no terms this is k_repack_conv (and k_repack_linear where scale_p = 1) bit for bit; with LORA terms only it is
-// k_repack_lora bit for bit (the same fma chain on the same values).
+// With no terms this is k_repack_conv (and k_repack_linear where scale_p = 1) bit for bit.
 //
-// Form: that of k_repack_lora.  One 256-thread workgroup per 64 x 64 tile of (output row) x (repacked column c = t I_pad + ci),
-// each lane a 4 x 4 fp32 tile (4 K-contiguous columns, one 8-byte store per row).  The two operands of a product pass through LDS
-// in rank chunks of 32 (the last one partial), converted to fp32 while staged; a HADA term stages its second product through the
-// same two buffers after the first.  A 64-row tile and a lane's 4 columns may both straddle a Kronecker factor boundary
-// (O2 = 24, I2 = 6 ...): the staging computes row % O2 and col % I2 per staged element and the w1 factor is looked up per
-// output element, nothing is assumed per tile or per lane.
-//   Us[rr][row], Ds[rr][col]  (row stride 68 floats): the LDS image of k_repack_lora, staged the same way (Us with lanes along r,
-//   Ds in column order).  What its header derives from the banking rules holds unchanged: ds_read_b128 of a lane's 4 rows /
-//   4 columns is conflict-free (the 4 ty addresses broadcast, the 16 tx addresses cover 64 distinct banks), the Us staging store
-//   is 4-way on 8 banks (about 2x on 8 stores per lane and chunk beside 512 FMAs), the Ds staging store is bank-consecutive.
+// Form: one 256-thread workgroup per 64 x 64 tile of (output row) x (repacked column c = t I_pad + ci); each lane owns a 4 x 4 fp32
+// tile (rows 4 ty .., columns 4 tx ..: the 4 columns are K-contiguous, one 8-byte store per row).  The two operands of a product
+// pass through LDS in rank chunks of 32 (the last one partial), converted to fp32 while staged, so every factor element is read
+// from memory once per tile instead of once per output element; a HADA term stages its second product through the same two buffers
+// after the first.  A 64-row tile and a lane's 4 columns may both straddle a Kronecker factor boundary (O2 = 24, I2 = 6 ...): the
+// staging computes row % O2 and col % I2 per staged element and the w1 factor is looked up per output element, nothing is assumed
+// per tile or per lane.
+//   Us[rr][row]  (row stride 68 floats): a lane reads its 4 rows as one ds_read_b128; the wave's 4 (ty) addresses broadcast.
+//                Staged with lanes along r (contiguous in memory): a 32-lane store group holds one row m and rr = 0..31, word
+//                offset 68 rr + m, i.e. bank (4 rr + m) mod 32 for ds_write_b32 - 8 banks, 4 addresses each, which by the
+//                banking rules costs about 2x on a store.  An estimate from those rules, not a measured counter; it concerns
+//                8 stores per lane and chunk beside 512 FMAs.
+//   Ds[rr][col]  (row stride 68 floats): a lane reads its 4 columns as one ds_read_b128, the 16 tx addresses of a lane group
+//                cover 64 distinct banks.  Staged in COLUMN order (lanes along the repacked column): the stride-KH*KW walk of a
+//                3x3 factor is on the global side, where the L2 serves it (a down factor is r x I x 9 elements, < 1 MB), and the
+//                LDS stores are bank-consecutive - the LDS image needs no padding beyond the 16-byte row alignment (likewise
+//                reasoned from the banking rules, not measured; the alternative is a source-order gather into a padded image).
 //   All of this is REASONED from the banking rules; no LDS counter was collected for this kernel.  MEASURED are only the
-//   request times in profiles/lyco_request_time.json.
-// 2 x 32 x 68 x 4 = 17 KB of LDS; a HADA term holds d1, d2 and acc (48 accumulator registers), and with every kind inlined the
-// compiler reports 141 VGPRs, no scratch, 3 waves per SIMD (k_repack_lora: 68 VGPRs) - three resident workgroups per CU, whose
-// staging phases overlap each other's FMA phases.  The dense forms (KRON dense right factor, FULL) read their operand once per
-// output element, like base.
+//   request times in profiles/lora_request_time.json, profiles/lyco_request_time.json and profiles/adapter_path_refactor.json.
+// 2 x 32 x 68 x 4 = 17 KB of LDS.  A HADA term holds d1, d2 and acc (48 accumulator registers), and with every kind inlined the
+// compiler reports 141 VGPRs, no scratch, 3 waves per SIMD - three resident workgroups per CU, whose staging phases overlap each
+// other's FMA phases.  The dense forms (KRON dense right factor, FULL) read their operand once per output element, like base.
+// So the tile has a compile-time LORA_ONLY flag that takes kind = DELTA_LORA as a constant and never reads da.kind: the other kinds'
+// code and registers are gone, the fma chain on the same values is the same.  launch_repack_delta picks that instantiation of
+// k_repack_delta exactly when every term is a LORA term (a LoRA file, a LoCon with or without a mid tensor; no terms at all) - from
+// the arguments, there is no switch.  That instantiation has 68 VGPRs, no scratch, 7 waves per SIMD in both storage builds: occupancy
+// is not its limiter, the fp32 FMA rate is (gyre_amd/build.py records both instantiations, tests/test_merge_delta_ref_host.py reads
+// the record).
 //
-// k_merge_delta<OUT>: the same tile with another store policy (lyco_tile<OUT>), for a weight that lives outside the native store - a
+// k_merge_delta<OUT>: the same tile with another store policy (lyco_tile<OUT, false>), for a weight that lives outside the native store - a
 // CLIP text encoder's nn.Linear, a plain row-major [O][I] tensor of the dtype the encoder was loaded in:
 //   out[o][i] = round_out( base[o][i] + sum_j s_j * D_j[o][i] )        OUT = GYRE_F32 | GYRE_BF16 | GYRE_F16, in BOTH storage builds
 // Matrix only (KK = 1), no interleave, no pad columns (I % 4 == 0), no scale_p.  Operation order (restated in
@@ -64,18 +76,18 @@
 #define LYCO_RCHUNK 32
 #define LYCO_LD 68
 
-__device__ __forceinline__ int lyco_src_row(int r, int F, int geglu) {          // geglu_src_row of kernels_elem.hip
-    if (!geglu) return r;
-    const int p = r >> 5, i = r & 31;
-    return i < 16 ? p * 16 + i : F + p * 16 + (i - 16);
-}
+__device__ __forceinline__ int lyco_src_row(int r, int F, int geglu) { return geglu ? geglu_src_row(r, F) : r; }
 
-// the isolated scale-and-round of kernels_lora.hip (lora_scale_round, see there): the same expression compiled on its own, so that
-// zero terms give gyre_unet_set_weight's bits in both storage builds
+// k_repack_conv's last step, f32_to_bf16(v * scale), kept as a function of its own: in the fp16 build the compiler contracts the
+// scalar product and its conversion into one mixed-precision instruction (v_fma_mixlo_f16: ONE rounding), while four products
+// side by side become v_pk_mul_f32 + v_cvt_pk_f16_f32 (rounded to fp32 first), which differs from set_weight's bits in about one
+// element in 10^4.  Those bits are the contract (zero terms must restore them), so the expression is compiled in isolation here
+// exactly as k_repack_conv has it; tests/test_gpu_lora_native.py compares every key of a model on both builds.
 static __device__ __attribute__((noinline)) uint32_t lyco_scale_round(float v, float scale) { return f32_to_bf16(v * scale); }
 
-// d += P(up, down) over this tile: up row = src_row(o) % Omod, down column = ci % Imod of a [rank][Imod][KK] tensor.  Omod = O and
-// Imod = I give the LORA indexing of k_repack_lora (so < O, ci < I).
+// d += P(up, down) over this tile.  KRON: the pair is a Kronecker right factor, up row = src_row(o) % Omod, down column = ci % Imod
+// of a [rank][Imod][KK] tensor; else (LORA, HADA) Omod = O and Imod = I, the remainders are the values themselves and are not taken.
+template <bool KRON>
 __device__ __forceinline__ void lyco_product(float (&d)[4][4], float (*Us)[LYCO_LD], float (*Ds)[LYCO_LD], const void* __restrict__ up,
                                              const void* __restrict__ down, int dt, int rank, int Omod, int Imod, int O, int I, int KK,
                                              int Ipad, int Kp, int F, int geglu, int row0, int col0, int tid, int tx, int ty) {
@@ -86,7 +98,10 @@ __device__ __forceinline__ void lyco_product(float (&d)[4][4], float (*Us)[LYCO_
             const int rr = idx & (LYCO_RCHUNK - 1), m = idx / LYCO_RCHUNK;
             const int o = row0 + m;
             float v = 0.f;
-            if (o < O && rr < nr) v = load_as_f32(up, dt, (size_t)(lyco_src_row(o, F, geglu) % Omod) * rank + r0 + rr);
+            if (o < O && rr < nr) {
+                const int so = lyco_src_row(o, F, geglu);
+                v = load_as_f32(up, dt, (size_t)(KRON ? so % Omod : so) * rank + r0 + rr);
+            }
             Us[rr][m] = v;
         }
         for (int idx = tid; idx < LYCO_TILE * LYCO_RCHUNK; idx += 256) {
@@ -95,7 +110,7 @@ __device__ __forceinline__ void lyco_product(float (&d)[4][4], float (*Us)[LYCO_
             float v = 0.f;
             if (c < Kp && rr < nr) {
                 const int t = c / Ipad, ci = c % Ipad;
-                if (ci < I) v = load_as_f32(down, dt, ((size_t)(r0 + rr) * Imod + ci % Imod) * KK + t);
+                if (ci < I) v = load_as_f32(down, dt, ((size_t)(r0 + rr) * Imod + (KRON ? ci % Imod : ci)) * KK + t);
             }
             Ds[rr][cc] = v;
         }
@@ -114,9 +129,9 @@ __device__ __forceinline__ void lyco_product(float (&d)[4][4], float (*Us)[LYCO_
 // The tile of both kernels.  OUT is the store policy: LYCO_OUT_PACKED writes the repacked storage layout (k_repack_delta: tap-major
 // padded columns, GEGLU interleave, round_storage(acc * scale_p)), GYRE_F32 / BF16 / F16 write a row-major [O][I] matrix of that type
 // (k_merge_delta: KK = 1, Ipad = I, geglu = 0 are constants there, acc is rounded as it stands).  Everything in front of the store
-// is the same code.
+// is the same code.  LORA_ONLY: every term is a LORA term (the launcher has looked), the kind is a constant and da.kind is not read.
 #define LYCO_OUT_PACKED (-1)
-template <int OUT>
+template <int OUT, bool LORA_ONLY>
 __device__ __forceinline__ void lyco_tile(const void* __restrict__ base, int bdt, int O, int I, int KK, int Ipad, int geglu, float scale_p,
                                           const DeltaArgs& da, void* __restrict__ outv) {
     if constexpr (OUT != LYCO_OUT_PACKED) { KK = 1; Ipad = I; geglu = 0; }
@@ -149,14 +164,14 @@ __device__ __forceinline__ void lyco_tile(const void* __restrict__ base, int bdt
         }
 
     for (int p = 0; p < da.n; ++p) {            // (uniform over the workgroup: the barriers inside lyco_product are reached by all)
-        const int kind = da.kind[p];
+        const int kind = LORA_ONLY ? DELTA_LORA : da.kind[p];
         float d[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) d[i][j] = 0.f;
         if (kind == DELTA_LORA || kind == DELTA_HADA) {
-            lyco_product(d, Us, Ds, da.up[p][0], da.down[p][0], da.dtype[p][0], da.rank[p][0], O, I, O, I, KK, Ipad, Kp, F, geglu,
+            lyco_product<false>(d, Us, Ds, da.up[p][0], da.down[p][0], da.dtype[p][0], da.rank[p][0], O, I, O, I, KK, Ipad, Kp, F, geglu,
                          row0, col0, tid, tx, ty);
             if (kind == DELTA_HADA) {
                 float e[4][4];
@@ -164,7 +179,7 @@ __device__ __forceinline__ void lyco_tile(const void* __restrict__ base, int bdt
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) e[i][j] = 0.f;
-                lyco_product(e, Us, Ds, da.up[p][1], da.down[p][1], da.dtype[p][1], da.rank[p][1], O, I, O, I, KK, Ipad, Kp, F, geglu,
+                lyco_product<false>(e, Us, Ds, da.up[p][1], da.down[p][1], da.dtype[p][1], da.rank[p][1], O, I, O, I, KK, Ipad, Kp, F, geglu,
                              row0, col0, tid, tx, ty);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -174,7 +189,7 @@ __device__ __forceinline__ void lyco_tile(const void* __restrict__ base, int bdt
         } else if (kind == DELTA_KRON) {
             const int O2 = O / da.O1[p], I2 = I / da.I1[p], I1 = da.I1[p];
             if (da.rank[p][0] > 0) {
-                lyco_product(d, Us, Ds, da.up[p][0], da.down[p][0], da.dtype[p][0], da.rank[p][0], O2, I2, O, I, KK, Ipad, Kp, F, geglu,
+                lyco_product<true>(d, Us, Ds, da.up[p][0], da.down[p][0], da.dtype[p][0], da.rank[p][0], O2, I2, O, I, KK, Ipad, Kp, F, geglu,
                              row0, col0, tid, tx, ty);
             } else {
                 const void* __restrict__ w2 = da.down[p][0];
@@ -237,14 +252,15 @@ __device__ __forceinline__ void lyco_tile(const void* __restrict__ base, int bdt
     }
 }
 
+template <bool LORA_ONLY>
 __global__ __launch_bounds__(256) void k_repack_delta(const void* __restrict__ base, int bdt, int O, int I, int KK, int Ipad, int geglu,
                                                       float scale_p, DeltaArgs da, bf16_t* __restrict__ out) {
-    lyco_tile<LYCO_OUT_PACKED>(base, bdt, O, I, KK, Ipad, geglu, scale_p, da, out);
+    lyco_tile<LYCO_OUT_PACKED, LORA_ONLY>(base, bdt, O, I, KK, Ipad, geglu, scale_p, da, out);
 }
 
 template <int OUT>
 __global__ __launch_bounds__(256) void k_merge_delta(const void* __restrict__ base, int bdt, int O, int I, DeltaArgs da, void* __restrict__ out) {
-    lyco_tile<OUT>(base, bdt, O, I, 1, I, 0, 1.f, da, out);
+    lyco_tile<OUT, false>(base, bdt, O, I, 1, I, 0, 1.f, da, out);
 }
 
 __global__ __launch_bounds__(256) void k_lyco_core(const void* __restrict__ core, int cdt, const void* __restrict__ right, int rdt,
@@ -298,8 +314,11 @@ int launch_repack_delta(hipStream_t st, const void* base, int base_dtype, int O,
     if ((size_t)O * KH * KW * Ipad >= ((size_t)1 << 31)) GYRE_FAIL(-1, "repack_delta: matrix too large");
     const int Kp = KH * KW * Ipad;
     GyreProfScope prof_(KC_LORA, st, flops, (double)O * Kp * 2.0 + (double)O * I * KH * KW * (base_dtype == 0 ? 4.0 : 2.0));
-    hipLaunchKernelGGL(k_repack_delta, dim3((Kp + LYCO_TILE - 1) / LYCO_TILE, (O + LYCO_TILE - 1) / LYCO_TILE), dim3(256), 0, st,
-                       base, base_dtype, O, I, KH * KW, Ipad, geglu, scale_p, da, out);
+    bool lora_only = true;                        // (no terms: the plain repack, which needs no kind either)
+    for (int p = 0; p < da.n; ++p) lora_only = lora_only && da.kind[p] == DELTA_LORA;
+    const dim3 grid((Kp + LYCO_TILE - 1) / LYCO_TILE, (O + LYCO_TILE - 1) / LYCO_TILE);
+    if (lora_only) hipLaunchKernelGGL(k_repack_delta<true>, grid, dim3(256), 0, st, base, base_dtype, O, I, KH * KW, Ipad, geglu, scale_p, da, out);
+    else hipLaunchKernelGGL(k_repack_delta<false>, grid, dim3(256), 0, st, base, base_dtype, O, I, KH * KW, Ipad, geglu, scale_p, da, out);
     GYRE_LAUNCH_CHECK();
     return 0;
 }

@@ -82,7 +82,8 @@ int gyre_unet_set_weight_lora(gyre_unet* h, const char* key, const void* base, i
                               int n_pairs, const gyre_lora_pair* pairs, void* st) {
     if (!h || !key || !base || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     bool was_set = false;
-    TRY(h->store.set_weight_lora(key, base, base_dtype, shape, ndim, n_pairs, pairs, (hipStream_t)st, &was_set));
+    TRY(h->store.set_weight_delta(key, base, base_dtype, shape, ndim, "a LoRA",
+                                  [&](DeltaArgs& da) { return lora_pairs_to_args(n_pairs, pairs, da, "set_weight_lora"); }, (hipStream_t)st, &was_set));
     if (!was_set) h->finalized = false;          // a key set before leaves a finalized handle finalized: no re-upload of the rest
     h->invalidate_contexts();                    // the cached K / V projections of the text contexts were made with the old weights
     return 0;
@@ -91,7 +92,8 @@ int gyre_unet_set_weight_delta(gyre_unet* h, const char* key, const void* base, 
                                int n_terms, const gyre_delta_term* terms, void* st) {
     if (!h || !key || !base || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     bool was_set = false;
-    TRY(h->store.set_weight_delta(key, base, base_dtype, shape, ndim, n_terms, terms, (hipStream_t)st, &was_set));
+    TRY(h->store.set_weight_delta(key, base, base_dtype, shape, ndim, "a LyCORIS delta",
+                                  [&](DeltaArgs& da) { return delta_terms_to_args(n_terms, terms, da); }, (hipStream_t)st, &was_set));
     if (!was_set) h->finalized = false;          // as gyre_unet_set_weight_lora
     h->invalidate_contexts();
     return 0;
@@ -644,13 +646,9 @@ int gyre_op_repack_linear_weight(void* st, const float* w, int O, int I, int geg
 int gyre_op_repack_lora(void* st, const void* base, int base_dtype, int O, int I, int KH, int KW, int I_pad, int geglu, float scale_p,
                         int n_pairs, const gyre_lora_pair* pairs, void* out) {
     if (!base || !out || (n_pairs > 0 && !pairs)) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
-    if (n_pairs < 0 || n_pairs > GYRE_LORA_MAX_PAIRS) GYRE_FAIL(GYRE_ERR_INVALID, "repack_lora: 0 to 8 LoRA pairs per call");
-    LoraArgs la;
-    la.n = n_pairs;
-    for (int j = 0; j < n_pairs; ++j) {
-        la.up[j] = pairs[j].up; la.down[j] = pairs[j].down; la.dtype[j] = pairs[j].dtype; la.rank[j] = pairs[j].rank; la.s[j] = pairs[j].scale;
-    }
-    return launch_repack_lora((hipStream_t)st, base, base_dtype, O, I, KH, KW, I_pad, geglu, scale_p, la, (bf16_t*)out);
+    DeltaArgs da;
+    TRY(lora_pairs_to_args(n_pairs, pairs, da, "repack_lora"));
+    return launch_repack_delta((hipStream_t)st, base, base_dtype, O, I, KH, KW, I_pad, geglu, scale_p, da, (bf16_t*)out);
 }
 int gyre_op_repack_delta(void* st, const void* base, int base_dtype, int O, int I, int KH, int KW, int I_pad, int geglu, float scale_p,
                          int n_terms, const gyre_delta_term* terms, void* out) {

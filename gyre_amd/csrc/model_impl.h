@@ -33,6 +33,22 @@ static inline int delta_terms_to_args(int n_terms, const gyre_delta_term* terms,
     }
     return 0;
 }
+// gyre_lora_pair[] (C ABI) -> the same kernel argument, every pair a LORA term; the LoRA entries' own refusals, `who` in front
+static inline int lora_pairs_to_args(int n_pairs, const gyre_lora_pair* pairs, DeltaArgs& da, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (n_pairs < 0 || n_pairs > GYRE_DELTA_MAX_TERMS || (n_pairs > 0 && !pairs)) GYRE_FAIL(GYRE_ERR_INVALID, w + "0 to 8 LoRA pairs per call");
+    da.n = n_pairs;
+    for (int j = 0; j < n_pairs; ++j) {
+        if (!pairs[j].up || !pairs[j].down) GYRE_FAIL(GYRE_ERR_INVALID, w + "null factor");
+        if (pairs[j].dtype < 0 || pairs[j].dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, w + "bad factor dtype");
+        if (pairs[j].rank < 1) GYRE_FAIL(GYRE_ERR_INVALID, w + "rank must be >= 1");
+        da.kind[j] = DELTA_LORA;
+        da.up[j][0] = pairs[j].up; da.down[j][0] = pairs[j].down; da.dtype[j][0] = pairs[j].dtype; da.rank[j][0] = pairs[j].rank;
+        da.up[j][1] = da.down[j][1] = nullptr; da.dtype[j][1] = da.rank[j][1] = 0;
+        da.w1[j] = nullptr; da.O1[j] = da.I1[j] = 0; da.s[j] = pairs[j].scale;
+    }
+    return 0;
+}
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int pad8(int c) { return (c + 7) / 8 * 8; }
 
@@ -294,46 +310,21 @@ struct Store {
         mark_set(p);
         return 0;
     }
-    // set_weight of  base + sum_j scale_j up_j down_j  (per-request LoRA, reference gyre/pipeline/lora.py:96-160) for one matrix /
-    // conv key: the low-rank sum joins the repack pass in fp32 (launch_repack_lora), nothing is multiplied out or copied by the
-    // caller.  Same key / shape rules as set_weight; n_pairs == 0 writes set_weight's bits (how a LoRA is taken off again).  The
-    // derived copies share the one version counter and are refreshed by the next forward.
-    int set_weight_lora(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, int n_pairs,
-                        const gyre_lora_pair* pairs, hipStream_t st, bool* was_set) {
+    // set_weight of  base + sum_j scale_j D_j  for one matrix / conv key, per-request adapters: LoRA pairs (reference
+    // gyre/pipeline/lora.py:96-160) and LyCORIS terms (gyre_delta_term, reference gyre/pipeline/lycoris.py:99-228), a pair being a LORA
+    // term.  The sum joins the repack pass in fp32 (launch_repack_delta), nothing is multiplied out or copied by the caller.  Same key /
+    // shape rules as set_weight (what: "a LoRA", "a LyCORIS delta" - the refusal of a vector key names it); fill(da) turns the caller's
+    // pairs or terms into the kernel argument behind the key lookup (lora_pairs_to_args, delta_terms_to_args).  No terms write
+    // set_weight's bits (how an adapter is taken off again).  The derived copies share the one version counter and are refreshed by
+    // the next forward.  Every check (fill, launch_repack_delta) precedes the launch.
+    template <class Fill>
+    int set_weight_delta(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, const char* what, Fill&& fill,
+                         hipStream_t st, bool* was_set) {
         Param* pp;
-        TRY(locate(key, dtype, shape, ndim, &pp, "a LoRA"));
-        Param& p = *pp;
-        if (n_pairs < 0 || n_pairs > GYRE_LORA_MAX_PAIRS || (n_pairs > 0 && !pairs)) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: 0 to 8 LoRA pairs per call");
-        LoraArgs la;
-        la.n = n_pairs;
-        for (int j = 0; j < n_pairs; ++j) {
-            if (!pairs[j].up || !pairs[j].down) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: null factor");
-            if (pairs[j].dtype < 0 || pairs[j].dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: bad factor dtype");
-            if (pairs[j].rank < 1) GYRE_FAIL(GYRE_ERR_INVALID, "set_weight_lora: rank must be >= 1");
-            la.up[j] = pairs[j].up; la.down[j] = pairs[j].down; la.dtype[j] = pairs[j].dtype; la.rank[j] = pairs[j].rank; la.s[j] = pairs[j].scale;
-        }
-        const int O = (int)p.shape[0], I = (int)p.shape[1];
-        if (p.kind == PK_CONV3) {
-            TRY(launch_repack_lora(st, src, dtype, O, I, 3, 3, p.i_pad, 0, 1.f, la, (bf16_t*)p.dev));
-        } else if (p.kind == PK_MAT_GEGLU) {
-            if (p.i_pad != I) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "geglu weight with padded K");
-            TRY(launch_repack_lora(st, src, dtype, O, I, 1, 1, I, 1, 1.f, la, (bf16_t*)p.dev));
-        } else {
-            TRY(launch_repack_lora(st, src, dtype, O, I, 1, 1, p.i_pad, 0, p.scale, la, (bf16_t*)p.dev));
-        }
-        mark_set(p, was_set);
-        return 0;
-    }
-    // set_weight of  base + sum_j scale_j D_j  with LyCORIS terms (gyre_delta_term, reference gyre/pipeline/lycoris.py:99-228): set_weight_lora
-    // with launch_repack_delta in place of launch_repack_lora - same key / shape rules, same version counter, n_terms == 0 writes
-    // set_weight's bits.  Every check (delta_terms_to_args, launch_repack_delta) precedes the launch.
-    int set_weight_delta(const char* key, const void* src, int dtype, const int64_t* shape, int ndim, int n_terms,
-                         const gyre_delta_term* terms, hipStream_t st, bool* was_set) {
-        Param* pp;
-        TRY(locate(key, dtype, shape, ndim, &pp, "a LyCORIS delta"));
+        TRY(locate(key, dtype, shape, ndim, &pp, what));
         Param& p = *pp;
         DeltaArgs da;
-        TRY(delta_terms_to_args(n_terms, terms, da));
+        TRY(fill(da));
         const int O = (int)p.shape[0], I = (int)p.shape[1];
         if (p.kind == PK_CONV3) {
             TRY(launch_repack_delta(st, src, dtype, O, I, 3, 3, p.i_pad, 0, 1.f, da, (bf16_t*)p.dev));

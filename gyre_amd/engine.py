@@ -118,7 +118,7 @@ class GyreUnifiedPipeline:
         self._shard_devices: list = []       # engine option "shard_devices": fan one request over these device slots
         self._shard_bit_exact = False
         self._executor = None
-        self._lora_uploads: list = []        # LoraFactors / LycoFactors of the last four LoRA / LyCORIS tensors mappings seen (_lora_factors)
+        self._lora_uploads: list = []        # lora.Factors of the last four LoRA / LyCORIS tensors mappings seen (_lora_factors)
         self._text_uploads: list = []        # ... and their text-encoder sides (text_adapters.TextFactors, _text_factors)
         self.clip_default_config = CG.ClipGuidanceConfig()
 
@@ -338,7 +338,7 @@ class GyreUnifiedPipeline:
         referenced, its address cannot be recycled), the four most
         recently used sets are kept."""
         dev = self.unet.device
-        cache = self._lora_uploads                          # [(tensors mapping, unet the shapes were checked against, LoraFactors)]
+        cache = self._lora_uploads                          # [(tensors mapping, unet the shapes were checked against, lora.Factors)]
         for i, (src, net, f) in enumerate(cache):
             if src is tensors and net is self.unet and f.device == dev:
                 cache.append(cache.pop(i))

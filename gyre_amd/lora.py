@@ -25,8 +25,8 @@ for ``state_dict()`` consumers only.
 
 Device path (``attach_lora`` / ``set_attached_scale`` / ``detach_loras``): the same map without the host.  The factors are kept
 as they come (never multiplied out), live on the module's device in their own dtype, and for each TOUCHED weight one
-``gyre_unet_set_weight_lora`` call hands the untouched master parameter and the factor pairs to the fused repack kernel
-(csrc/kernels_lora.hip): base + sum_j s_j up_j down_j in fp32, rounded once.  Untouched weights are not uploaded again, and
+``gyre_unet_set_weight_delta`` call hands the untouched master parameter and the factor pairs, as LORA terms, to the fused
+repack kernel (csrc/kernels_lyco.hip): base + sum_j s_j up_j down_j in fp32, rounded once.  Untouched weights are not uploaded again, and
 detaching re-issues the touched keys with zero pairs, which restores the base bits.  On this path the master parameters are
 NEVER written: ``state_dict()`` keeps showing the base weights while a LoRA is attached - which is what the reference's hooks do
 (they leave ``module.weight`` alone).  The two paths do not stack: attaching onto a host-merged module, or merging into a module
@@ -202,70 +202,129 @@ def remove_lora_from_model(unet) -> None:
 
 
 # ---- device path: factors stay factors, merged inside the repack kernel -------------------------------------------------
-class LoraFactors:
-    """One LoRA's factors on a device, as attach_lora keeps them: ``pairs[name] = (up, down, alpha / r)`` with up [O, r] and
-    down [r, I(, KH, KW)] contiguous in their own dtype.  ``source`` keeps the tensors mapping they were made from referenced
-    (an identity-keyed cache of uploads must not see its key's address recycled)."""
+_FACTOR_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
-    def __init__(self, pairs, device, source=None):
-        self.pairs, self.device, self.source = pairs, device, source
+
+class Term:
+    """One gyre_delta_term with its device tensors: ``kind`` (_lib.DELTA_*), ``ops`` = up to two (up, down) pairs (up None for a
+    dense operand), ``w1`` (KRON: dense fp32 [O1, I1]) and the file scale.  A LoRA pair is a LORA term (lora_term); the LyCORIS
+    forms are lycoris.make_term's."""
+
+    def __init__(self, kind, ops, scale, w1=None):
+        self.kind, self.ops, self.scale, self.w1 = kind, ops, scale, w1
+
+    def to(self, device):
+        mv = lambda t: None if t is None else t.to(device)
+        return Term(self.kind, [(mv(u), mv(d)) for u, d in self.ops], self.scale, mv(self.w1))
+
+    def tensors(self):
+        return [t for pair in self.ops for t in pair if t is not None] + ([self.w1] if self.w1 is not None else [])
+
+    def fits(self, w: Tensor) -> bool:
+        """Do the operands give a delta of ``w``'s shape (the kernel trusts this)?"""
+        from . import _lib
+        O, I = w.shape[0], w.shape[1]
+        kk = w.numel() // (O * I)
+        if not all(t.is_contiguous() for t in self.tensors()):
+            return False
+        if self.kind == _lib.DELTA_KRON:
+            if self.w1 is None or self.w1.ndim != 2 or self.w1.dtype != torch.float32:
+                return False
+            O1, I1 = self.w1.shape
+            if O % O1 or I % I1:
+                return False
+            O, I = O // O1, I // I1
+        for up, down in self.ops:
+            if up is None:
+                if down.numel() != O * I * kk or down.shape[0] != O:
+                    return False
+            elif up.ndim != 2 or up.shape[0] != O or up.dtype != down.dtype or down.shape[0] != up.shape[1] or up.shape[1] < 1 \
+                    or down.numel() != up.shape[1] * I * kk:
+                return False
+        return True
+
+    def fill(self, c, user_scale: float) -> None:
+        from . import _lib
+        c.kind, c.scale = self.kind, user_scale * self.scale
+        for q, (up, down) in enumerate(self.ops):
+            c.up[q], c.down[q] = (None if up is None else up.data_ptr()), down.data_ptr()
+            c.dtype[q], c.rank[q] = _lib.dtype_code(down), (0 if up is None else up.shape[1])
+        if self.w1 is not None:
+            c.w1, c.O1, c.I1 = self.w1.data_ptr(), self.w1.shape[0], self.w1.shape[1]
+
+
+class Factors:
+    """One LoRA or LyCORIS file's terms on a device, as attach_loras keeps them: ``terms[name] = Term`` per touched weight.
+    ``source`` keeps the tensors mapping they were made from referenced (an identity-keyed cache of uploads must not see its key's
+    address recycled)."""
+
+    def __init__(self, terms: Dict[str, Term], device, source=None):
+        self.terms, self.device, self.source = terms, device, source
 
     def names(self):
-        return self.pairs.keys()
+        return self.terms.keys()
 
     def hits(self, name) -> list:
-        """What hits the weight ``name``: [(up, down, alpha / r)] (lycoris.LycoFactors answers with its Term objects)."""
-        return [self.pairs[name]] if name in self.pairs else []
+        """What hits the weight ``name``: [Term], or []."""
+        return [self.terms[name]] if name in self.terms else []
 
     def to(self, device):
         """These factors on ``device``: this object where they already are, a NEW one otherwise (an upload may be shared between
         modules and devices - it is never changed in place)."""
         if device == self.device:
             return self
-        return LoraFactors({k: (u.to(device), d.to(device), s) for k, (u, d, s) in self.pairs.items()}, device, self.source)
+        return Factors({k: t.to(device) for k, t in self.terms.items()}, device, self.source)
 
 
-_FACTOR_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+def fix_factor(t: Tensor, device) -> Tensor:
+    """A file tensor as the kernels read it: on ``device``, contiguous, in its own dtype where that is fp32 / bf16 / fp16."""
+    return (t if t.dtype in _FACTOR_DTYPES else t.to(torch.float32)).detach().to(device).contiguous()
 
 
-def upload_factors(unet, lora: Mapping[str, Tensor], device=None) -> LoraFactors:
-    """Parse ``lora`` (the key rules of apply_lora) and put its factors on ``device`` (default: the module's), each in its own
-    dtype; nothing is multiplied out.  Shapes are checked against the weights they target (ValueError)."""
+def lora_term(up: Tensor, down: Tensor, alpha, w: Tensor, name: str, device) -> Term:
+    """The LORA term of one LoRA pair for the weight ``w`` (its shape only): up [O, r] (a conv's 1 x 1 up flattened), down
+    [r, I(, KH, KW)] on ``device``, scale alpha / r (alpha absent: 1).  Each factor keeps its own dtype unless the two differ - a
+    term's pair has ONE dtype, so both are then promoted to fp32.  ValueError where the pair does not give the weight's shape.
+    The one constructor of a LoRA file's terms: upload_factors here and text_adapters.upload_text_factors."""
+    from . import _lib
+    if down.ndim not in (2, 4) or up.ndim != down.ndim:
+        raise ValueError(f"Can't apply LoRA of rank-{down.ndim} tensors")
+    if down.ndim == 4 and tuple(up.shape[2:]) != (1, 1):
+        raise ValueError("conv LoRA: the up projection must be 1x1")
+    r = down.shape[0]
+    if r < 1 or up.shape[1] != r:
+        raise ValueError(f"LoRA for {name}: up has rank {up.shape[1]}, down rank {r}")
+    if w.ndim != down.ndim or up.shape[0] != w.shape[0] or tuple(down.shape[1:]) != tuple(w.shape[1:]):
+        raise ValueError(f"LoRA for {name}: up {tuple(up.shape)} x down {tuple(down.shape)} does not give the weight's "
+                         f"shape {tuple(w.shape)}")
+    up, down = fix_factor(up, device).reshape(up.shape[0], r), fix_factor(down, device)
+    if up.dtype != down.dtype:
+        up, down = up.float(), down.float()
+    return Term(_lib.DELTA_LORA, [(up, down)], float(alpha) / r if alpha is not None else 1.0)
+
+
+def upload_factors(unet, lora: Mapping[str, Tensor], device=None) -> Factors:
+    """Parse ``lora`` (the key rules of apply_lora) and put its factors on ``device`` (default: the module's) as LORA terms
+    (lora_term); nothing is multiplied out.  Shapes are checked against the weights they target (ValueError)."""
     device = torch.device(device) if device is not None else unet.device
     params = dict(unet.named_parameters())
-    pairs = {}
-    for name, up, down, alpha in _pairs(unet, lora):
-        w = params[name]
-        if down.ndim not in (2, 4) or up.ndim != down.ndim:
-            raise ValueError(f"Can't apply LoRA of rank-{down.ndim} tensors")
-        if down.ndim == 4 and tuple(up.shape[2:]) != (1, 1):
-            raise ValueError("conv LoRA: the up projection must be 1x1")
-        r = down.shape[0]
-        if r < 1 or up.shape[1] != r:
-            raise ValueError(f"LoRA for {name}: up has rank {up.shape[1]}, down rank {r}")
-        if w.ndim != down.ndim or up.shape[0] != w.shape[0] or tuple(down.shape[1:]) != tuple(w.shape[1:]):
-            raise ValueError(f"LoRA for {name}: up {tuple(up.shape)} x down {tuple(down.shape)} does not give the weight's "
-                             f"shape {tuple(w.shape)}")
-        iscale = float(alpha) / r if alpha is not None else 1.0
-        fix = lambda t: (t if t.dtype in _FACTOR_DTYPES else t.to(torch.float32)).detach().to(device).contiguous()
-        pairs[name] = (fix(up), fix(down), iscale)
-    return LoraFactors(pairs, device, lora)
+    return Factors({name: lora_term(up, down, alpha, params[name], name, device) for name, up, down, alpha in _pairs(unet, lora)},
+                   device, lora)
 
 
 def _attached(unet):
     at = getattr(unet, "_lora_attached", None)
     if at is None:
-        at = {"loras": {}}                       # id -> (LoraFactors or lycoris.LycoFactors, user scale), in attach order
+        at = {"loras": {}}                       # id -> (Factors, user scale), in attach order
         unet._lora_attached = at
     return at
 
 
 def _issue(unet, names) -> None:
-    """One repack call for each of ``names`` on the module's live handle: the untouched master parameter plus every attached LoRA
-    pair and LyCORIS term that hits the key, in attach order (none: the base bits).  A key hit by LoRA pairs only (or by nothing)
-    goes to gyre_unet_set_weight_lora, one with a LyCORIS term to gyre_unet_set_weight_delta, where a pair is a LORA term - the
-    same kernel arithmetic either way.  A module whose native copy is stale anyway (``_dirty``: after ``.to(...)``) is left to
-    ``_sync``, which re-applies the attached set behind its full upload."""
+    """One gyre_unet_set_weight_delta call for each of ``names`` on the module's live handle: the untouched master parameter plus
+    every attached term (a LoRA pair is a LORA term) that hits the key, in attach order (none: the base bits).  A module whose
+    native copy is stale anyway (``_dirty``: after ``.to(...)``) is left to ``_sync``, which re-applies the attached set behind its
+    full upload."""
     import ctypes as C
     from . import _lib
     names = list(names)
@@ -283,19 +342,12 @@ def _issue(unet, names) -> None:
         plan = {}
         for name in names:                       # (scale 0 contributes nothing, as in the host merge)
             w = params[name]
-            plan[name] = [(hit, scale) for f, scale in at["loras"].values() if scale != 0 for hit in f.hits(name)]
-            if len(plan[name]) > _lib.LORA_MAX_PAIRS:
-                raise ValueError(f"{len(plan[name])} LoRA pairs / LyCORIS terms hit {name}: at most {_lib.LORA_MAX_PAIRS} per weight")
-            for hit, _ in plan[name]:
-                if not isinstance(hit, tuple):
-                    if w.ndim not in (2, 4) or not hit.fits(w):
-                        raise ValueError(f"LyCORIS term does not fit {name} {tuple(w.shape)} (factors uploaded for another model?)")
-                    continue
-                up, down, _ = hit
-                if up.ndim != w.ndim or down.ndim != w.ndim or up.shape[0] != w.shape[0] or up.shape[1] != down.shape[0] \
-                        or tuple(down.shape[1:]) != tuple(w.shape[1:]) or not (up.is_contiguous() and down.is_contiguous()):
-                    raise ValueError(f"LoRA factors up {tuple(up.shape)} x down {tuple(down.shape)} do not fit {name} "
-                                     f"{tuple(w.shape)} (factors uploaded for another model?)")
+            plan[name] = [(term, scale) for f, scale in at["loras"].values() if scale != 0 for term in f.hits(name)]
+            if len(plan[name]) > _lib.DELTA_MAX_TERMS:
+                raise ValueError(f"{len(plan[name])} LoRA pairs / LyCORIS terms hit {name}: at most {_lib.DELTA_MAX_TERMS} per weight")
+            for term, _ in plan[name]:
+                if w.ndim not in (2, 4) or not term.fits(w):
+                    raise ValueError(f"LoRA / LyCORIS term does not fit {name} {tuple(w.shape)} (factors uploaded for another model?)")
         try:
             with torch.cuda.device(dev):
                 st = _lib.stream_ptr(dev)
@@ -303,27 +355,13 @@ def _issue(unet, names) -> None:
                     base = params[name].detach()
                     base = (base if base.device == dev else base.to(dev)).contiguous()
                     shape = (C.c_int64 * base.ndim)(*base.shape)
-                    if all(isinstance(hit, tuple) for hit, _ in hits):
-                        arr = (_lib.LoraPair * max(len(hits), 1))()
-                        for j, ((up, down, iscale), scale) in enumerate(hits):
-                            arr[j].up, arr[j].down = up.data_ptr(), down.data_ptr()
-                            arr[j].dtype, arr[j].rank, arr[j].scale = _lib.dtype_code(up), down.shape[0], scale * iscale
-                        _lib.check(L.gyre_unet_set_weight_lora(C.c_void_p(unet._handle), name.encode(), C.c_void_p(base.data_ptr()),
-                                                               _lib.dtype_code(base), shape, base.ndim, len(hits), arr, C.c_void_p(st)), L)
-                        continue
-                    arr = (_lib.DeltaTerm * len(hits))()
-                    for j, (hit, scale) in enumerate(hits):
-                        if isinstance(hit, tuple):
-                            up, down, iscale = hit
-                            arr[j].kind, arr[j].scale = _lib.DELTA_LORA, scale * iscale
-                            arr[j].up[0], arr[j].down[0] = up.data_ptr(), down.data_ptr()
-                            arr[j].dtype[0], arr[j].rank[0] = _lib.dtype_code(up), down.shape[0]
-                        else:
-                            hit.fill(arr[j], scale)
+                    arr = (_lib.DeltaTerm * max(len(hits), 1))()
+                    for j, (term, scale) in enumerate(hits):
+                        term.fill(arr[j], scale)
                     _lib.check(L.gyre_unet_set_weight_delta(C.c_void_p(unet._handle), name.encode(), C.c_void_p(base.data_ptr()),
                                                             _lib.dtype_code(base), shape, base.ndim, len(hits), arr, C.c_void_p(st)), L)
         except Exception:
-            # some keys may carry the new pairs and others not: the native copy no longer matches any registry state, so the next
+            # some keys may carry the new terms and others not: the native copy no longer matches any registry state, so the next
             # use uploads everything again and re-applies whatever the caller leaves attached
             unet._invalidate()
             raise
@@ -340,21 +378,21 @@ def _reapply_attached(unet) -> None:
 
 
 def attach_lora(unet, tensors, lora_id, scale: float = 1.0) -> int:
-    """Attach one LoRA (a dict of tensors, or the LoraFactors upload_factors made of one) under ``lora_id`` on the device path:
+    """Attach one LoRA (a dict of tensors, or the Factors upload_factors made of one) under ``lora_id`` on the device path:
     only the weights it touches are repacked, from the master parameter and the factors (module docstring).  Returns the number
     of weights touched.  The module must be on a GPU (GyreError otherwise, as for a forward)."""
     return attach_loras(unet, [(tensors, lora_id, scale)])[0]
 
 
 def attach_loras(unet, specs) -> list:
-    """Several LoRAs at once, ``specs = [(tensors or LoraFactors, lora_id, scale), ...]``: all are registered first and every
+    """Several LoRAs at once, ``specs = [(tensors or Factors, lora_id, scale), ...]``: all are registered first and every
     touched weight is repacked ONCE, with all the pairs that hit it.  Returns the number of weights each one touches.  An entry
-    may also be the LycoFactors of an uploaded LyCORIS file (lycoris.upload_factors; lycoris.attach_adapters routes mappings of
+    may also be the Factors of an uploaded LyCORIS file (lycoris.upload_factors; lycoris.attach_adapters routes mappings of
     either kind); a tensors mapping given here is read as a LoRA and a LyCORIS one is refused by detect_lora_type."""
     if (getattr(unet, "_lora_state", None) or {"loras": {}})["loras"]:
         raise ValueError("this module has host-merged LoRAs (apply_lora): the two LoRA paths do not stack - "
                          "remove_lora_from_model() first")
-    is_factors = lambda t: hasattr(t, "hits")                  # LoraFactors, or the LycoFactors of lycoris.upload_factors
+    is_factors = lambda t: isinstance(t, Factors)
     for tensors, _, _ in specs:                                # format errors come first
         if not is_factors(tensors) and detect_lora_type(tensors) == "cloneofsimo":
             raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")

@@ -39,6 +39,7 @@ from typing import Dict, List, Mapping, Optional
 import torch
 
 from . import lora as LR
+from .lora import Factors, Term
 
 Tensor = torch.Tensor
 
@@ -212,72 +213,6 @@ def apply_lycoris(unet, tensors, lyco_id, scale: float = 1.0) -> int:
 
 
 # ---- device path ---------------------------------------------------------------------------------------------------------
-class Term:
-    """One gyre_delta_term with its device tensors: ``kind`` (_lib.DELTA_*), ``ops`` = up to two (up, down) pairs (up None for a
-    dense operand), ``w1`` (KRON: dense fp32 [O1, I1]) and the file scale."""
-
-    def __init__(self, kind, ops, scale, w1=None):
-        self.kind, self.ops, self.scale, self.w1 = kind, ops, scale, w1
-
-    def to(self, device):
-        mv = lambda t: None if t is None else t.to(device)
-        return Term(self.kind, [(mv(u), mv(d)) for u, d in self.ops], self.scale, mv(self.w1))
-
-    def tensors(self):
-        return [t for pair in self.ops for t in pair if t is not None] + ([self.w1] if self.w1 is not None else [])
-
-    def fits(self, w: Tensor) -> bool:
-        """Do the operands give a delta of ``w``'s shape (the kernel trusts this)?"""
-        from . import _lib
-        O, I = w.shape[0], w.shape[1]
-        kk = w[0, 0].numel()
-        if not all(t.is_contiguous() for t in self.tensors()):
-            return False
-        if self.kind == _lib.DELTA_KRON:
-            if self.w1 is None or self.w1.ndim != 2 or self.w1.dtype != torch.float32:
-                return False
-            O1, I1 = self.w1.shape
-            if O % O1 or I % I1:
-                return False
-            O, I = O // O1, I // I1
-        for up, down in self.ops:
-            if up is None:
-                if down.numel() != O * I * kk or down.shape[0] != O:
-                    return False
-            elif up.ndim != 2 or up.shape[0] != O or up.dtype != down.dtype or down.shape[0] != up.shape[1] or up.shape[1] < 1 \
-                    or down.numel() != up.shape[1] * I * kk:
-                return False
-        return True
-
-    def fill(self, c, user_scale: float) -> None:
-        from . import _lib
-        c.kind, c.scale = self.kind, user_scale * self.scale
-        for q, (up, down) in enumerate(self.ops):
-            c.up[q], c.down[q] = (None if up is None else up.data_ptr()), down.data_ptr()
-            c.dtype[q], c.rank[q] = _lib.dtype_code(down), (0 if up is None else up.shape[1])
-        if self.w1 is not None:
-            c.w1, c.O1, c.I1 = self.w1.data_ptr(), self.w1.shape[0], self.w1.shape[1]
-
-
-class LycoFactors:
-    """One LyCORIS file's terms on a device: ``terms[name] = Term`` per touched weight.  ``source`` keeps the mapping they were made
-    from referenced (as lora.LoraFactors does for an identity-keyed cache)."""
-
-    def __init__(self, terms: Dict[str, Term], device, source=None):
-        self.terms, self.device, self.source = terms, device, source
-
-    def names(self):
-        return self.terms.keys()
-
-    def hits(self, name) -> list:
-        return [self.terms[name]] if name in self.terms else []
-
-    def to(self, device):
-        if device == self.device:
-            return self
-        return LycoFactors({k: t.to(device) for k, t in self.terms.items()}, device, self.source)
-
-
 def _core(L, core: Tensor, right: Tensor) -> Tensor:
     """gyre_op_lyco_core: core [A, B, T...] x right [B, C] -> fp32 [A, C, T]."""
     from . import _lib
@@ -298,7 +233,7 @@ def make_term(L, fields: Mapping[str, Tensor], w: Tensor, name: str, device) -> 
     Tucker cores and a low-rank W1 are contracted here (gyre_op_lyco_core of the library ``L``, fp32); nothing else is multiplied
     out.  ValueError where the tensors do not give the weight's shape.  Shared by upload_factors and text_adapters."""
     from . import _lib
-    fix = lambda t: (t if t.dtype in LR._FACTOR_DTYPES else t.to(torch.float32)).detach().to(device).contiguous()
+    fix = lambda t: LR.fix_factor(t, device)
 
     def product(wa, wb, t):
         """(up [O', r], down [r, ...]) of one low-rank product; with a core: up = wa^T in fp32, down = core(t, wb)."""
@@ -347,7 +282,7 @@ def make_term(L, fields: Mapping[str, Tensor], w: Tensor, name: str, device) -> 
     return term
 
 
-def upload_factors(unet, tensors, device=None) -> LycoFactors:
+def upload_factors(unet, tensors, device=None) -> Factors:
     """Parse ``tensors`` (the key rules of apply_lycoris) and put its terms on ``device`` (default: the module's), each factor in its own
     dtype.  Tucker cores and a low-rank W1 are contracted once here (gyre_op_lyco_core, fp32); nothing else is multiplied out.
     Shapes are checked against the weights they target (ValueError)."""
@@ -358,7 +293,7 @@ def upload_factors(unet, tensors, device=None) -> LycoFactors:
     L = unet._L() if hasattr(unet, "_L") else _lib.lib()
     params = dict(unet.named_parameters())
     terms = {name: make_term(L, fields, params[name], name, device) for name, fields in _modules(unet, tensors)}
-    return LycoFactors(terms, device, tensors)
+    return Factors(terms, device, tensors)
 
 
 def is_lycoris(tensors) -> bool:
@@ -373,17 +308,17 @@ def is_lycoris(tensors) -> bool:
 
 def factors_for(unet, tensors, device=None):
     """lora.upload_factors or this module's, by that routing."""
-    if isinstance(tensors, (LR.LoraFactors, LycoFactors)):
+    if isinstance(tensors, Factors):
         return tensors
     return upload_factors(unet, tensors, device) if is_lycoris(tensors) else LR.upload_factors(unet, tensors, device)
 
 
 def attach_adapters(unet, specs) -> list:
-    """``specs = [(tensors | LoraFactors | LycoFactors, id, scale), ...]``, LoRA and LyCORIS files mixed: all are registered first
+    """``specs = [(tensors | Factors, id, scale), ...]``, LoRA and LyCORIS files mixed: all are registered first
     and every touched weight is repacked ONCE with every pair / term that hits it, in attach order (lora.attach_loras)."""
     specs = list(specs)
     for t, _, _ in specs:                                           # format errors come first, before any upload
-        if not isinstance(t, (LR.LoraFactors, LycoFactors)) and not is_lycoris(t) and LR.detect_lora_type(t) == "cloneofsimo":
+        if not isinstance(t, Factors) and not is_lycoris(t) and LR.detect_lora_type(t) == "cloneofsimo":
             raise NotImplementedError("cloneofsimo LoRA files need lora_diffusion's module search order (not vendored)")
     if specs:
         unet._sync(unet.device)                                     # raises off the GPU, before factors_for would
@@ -391,9 +326,9 @@ def attach_adapters(unet, specs) -> list:
 
 
 def attach_lycoris(unet, tensors, lyco_id, scale: float = 1.0) -> int:
-    """Attach one LyCORIS file (a dict of tensors, a safetensors handle, or the LycoFactors upload_factors made of one) on the
+    """Attach one LyCORIS file (a dict of tensors, a safetensors handle, or the Factors upload_factors made of one) on the
     device path.  Returns the number of weights touched."""
-    if not isinstance(tensors, LycoFactors):
+    if not isinstance(tensors, Factors):
         unet._sync(unet.device)
         tensors = upload_factors(unet, tensors, unet.device)
     return LR.attach_loras(unet, [(tensors, lyco_id, scale)])[0]

@@ -14,7 +14,7 @@ master must not accumulate deltas: an element below half an ulp of W would vanis
     not an nn.Linear (CLIP has no other): its ValueError.  diffusers-format files carry no text side (as in the reference); cloneofsimo
     files and the embeddings packed inside them stay unsupported (lora.py).
   * terms: built by the parsers of the UNet side, not by copies of them - lycoris._kind / file_scale / make_term (Term, _core) and
-    lora_delta's alpha / r rule; IA3, DyLoRA and sparse-bias modules are NotImplementedError exactly as there.  A module whose
+    lora.lora_term for a kohya LoRA pair; IA3, DyLoRA and sparse-bias modules are NotImplementedError exactly as there.  A module whose
     tensors are ALL zero is the zero delta whatever its shapes and is skipped before any shape rule (placeholders).
   * native path (the default wherever the encoder is on a GPU): ``upload_text_factors`` puts the factors on the device once per file,
     ``attach`` keeps each touched weight's original tensor as ``base`` (its own dtype) and issues ONE gyre_op_merge_delta per weight
@@ -143,22 +143,6 @@ def _device_of(text_encoder) -> torch.device:
     return torch.device("cpu")
 
 
-def _lora_term(fields, w: Tensor, name: str, device) -> LY.Term:
-    """A kohya LoRA pair as a LORA term: lora.upload_factors' checks, lora_delta's alpha / r rule."""
-    from . import _lib
-    up, down, alpha = fields["lora_up.weight"], fields["lora_down.weight"], fields.get("alpha")
-    if down.ndim != 2 or up.ndim != 2:
-        raise ValueError(f"Can't apply LoRA of rank-{down.ndim} tensors to {name}")
-    r = down.shape[0]
-    if r < 1 or up.shape[1] != r or up.shape[0] != w.shape[0] or down.shape[1] != w.shape[1]:
-        raise ValueError(f"LoRA for {name}: up {tuple(up.shape)} x down {tuple(down.shape)} does not give the weight's shape {tuple(w.shape)}")
-    fix = lambda t: (t if t.dtype in LR._FACTOR_DTYPES else t.to(torch.float32)).detach().to(device).contiguous()
-    up, down = fix(up), fix(down)
-    if up.dtype != down.dtype:
-        up, down = up.float(), down.float()
-    return LY.Term(_lib.DELTA_LORA, [(up, down)], float(alpha) / r if alpha is not None else 1.0)
-
-
 def upload_text_factors(text_encoder, tensors, device=None) -> TextFactors:
     """Parse the ``lora_te_`` side of ``tensors`` against ``text_encoder`` and prepare it for ``device`` (default: the encoder's):
     on a GPU the factors stay factors (each in its own dtype; Tucker cores and a low-rank W1 contracted once, gyre_op_lyco_core), off
@@ -177,7 +161,8 @@ def upload_text_factors(text_encoder, tensors, device=None) -> TextFactors:
     from . import _lib
     L = _lib.lib()
     with torch.cuda.device(device):
-        terms = [(module, LY.make_term(L, fields, module.weight, key, device) if lyco else _lora_term(fields, module.weight, key, device))
+        terms = [(module, LY.make_term(L, fields, module.weight, key, device) if lyco else
+                  LR.lora_term(fields["lora_up.weight"], fields["lora_down.weight"], fields.get("alpha"), module.weight, key, device))
                  for key, module, fields, lyco in mods]
     return TextFactors(terms, None, device, tensors)
 

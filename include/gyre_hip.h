@@ -295,7 +295,9 @@ int gyre_unet_set_weight(gyre_unet* h, const char* diffusers_key, const void* de
  * GYRE_ERR_INVALID.  Nothing else is uploaded: a finalized handle stays finalized (the key had been set before), the cached text
  * contexts are dropped, and the copies the library derives from weights (transposed, LayerNorm-folded, blocked, fragment-ordered,
  * folded-shortcut) are refreshed on the device by the next forward - all of them, they share one version counter.
- * Asynchronous on `stream`; base and the factors may be released once the stream has passed this point. */
+ * Asynchronous on `stream`; base and the factors may be released once the stream has passed this point.
+ * This entry is gyre_unet_set_weight_delta (below) restricted to GYRE_DELTA_LORA terms: pair j is the term (up_j, down_j, dtype,
+ * rank, scale_j), the same kernel writes the same bits either way. */
 typedef struct { const void* up; const void* down; int dtype; int rank; float scale; } gyre_lora_pair;
 int gyre_unet_set_weight_lora(gyre_unet* h, const char* diffusers_key, const void* base, int base_dtype,
                               const int64_t* shape, int ndim, int n_pairs, const gyre_lora_pair* pairs, void* stream);
@@ -906,7 +908,7 @@ int gyre_op_repack_conv_weight_scaled(void* stream, const void* w_oihw, int dtyp
                                       float scale, void* w_krsc);
 int gyre_op_repack_linear_weight(void* stream, const float* w_oi, int O, int I, int geglu_interleave, void* w_bf16);
 int gyre_op_repack_bias(void* stream, const float* b, int n, int geglu_interleave, float* out);
-/* The repack of gyre_unet_set_weight_lora as an operator: base (O x I x KH x KW, base_dtype) and n_pairs LoRA factor pairs ->
+/* The repack of gyre_unet_set_weight_lora as an operator (gyre_op_repack_delta restricted to GYRE_DELTA_LORA terms): base (O x I x KH x KW, base_dtype) and n_pairs LoRA factor pairs ->
  * out [O][KH][KW][I_pad] in the storage type (pad columns zero; KH = KW = 1 for a matrix; geglu != 0: the 16-row value / gate
  * interleave of gyre_op_repack_linear_weight, the up factor indexed by the SOURCE row), every value
  * round(scale_p * (base + sum_j scale_j up_j down_j)) with the sum in fp32: r ascending inside a pair, pairs in argument order.

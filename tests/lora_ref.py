@@ -1,4 +1,4 @@
-"""Reference, data families and error bound for the fused LoRA delta-merge repack (gyre_amd/csrc/kernels_lora.hip,
+"""Reference, data families and error bound for the fused LoRA delta-merge repack (gyre_amd/csrc/kernels_lyco.hip with LORA terms,
 gyre_op_repack_lora / gyre_unet_set_weight_lora):
 
     out[o][ky][kx][ci] = round_storage( scale_p * ( base[so,ci,ky,kx] + sum_j s_j * sum_r up_j[so,r] * down_j[r,ci,ky,kx] ) )
@@ -7,7 +7,7 @@ so = o, or the source row of the 16-row value / gate interleave for the GEGLU pr
 row 32p+16+i = gate row F+16p+i, F = O/2); pad columns ci >= I are zero.  A *pair* here is ``(up [O, r], down [r, I, KH, KW], s)``
 as numpy arrays (down may be [r, I] for a matrix).
 
-The kernel's stated operation order (header of kernels_lora.hip), restated by ``emulate``:
+The kernel's stated operation order (header of kernels_lyco.hip, LORA terms), restated by ``emulate``:
 
     acc = base
     for j in argument order:   d = 0;  for r ascending: d = fma(up_j[so,r], down_j[r,...], d)

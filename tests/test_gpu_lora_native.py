@@ -1,5 +1,5 @@
 """Per-request LoRA on the device (-m gpu): the fused delta-merge repack kernel (gyre_op_repack_lora), the store entry
-(gyre_unet_set_weight_lora), the module path (lora.attach_lora / set_attached_scale / detach_loras) and the engine's ``lora=``.
+(gyre_unet_set_weight_lora; the module path issues its pairs as LORA terms of gyre_unet_set_weight_delta), the module path (lora.attach_lora / set_attached_scale / detach_loras) and the engine's ``lora=``.
 
 Yardsticks (tests/lora_ref.py, checked on the CPU by tests/test_lora_ref_host.py): on the LATTICE family every value is exact in
 fp32 in any order and representable in the storage type, so the kernel must equal the float64 reference - and the host path
@@ -319,13 +319,13 @@ def test_gaussian_lora_against_the_fp32_oracle(nets, inputs):
 
 
 def test_no_reupload(nets, inputs):
-    """attach + forward + detach + forward: one gyre_unet_set_weight_lora per TOUCHED key each way, not one gyre_unet_set_weight,
+    """attach + forward + detach + forward: one gyre_unet_set_weight_delta per TOUCHED key each way, not one gyre_unet_set_weight,
     and no master parameter written."""
     a, _, base = nets
     L = a._L()
     fwd(a, inputs)
     calls = {"set_weight": 0, "lora_pairs": 0, "lora_restore": 0}
-    orig_set, orig_lora = L.gyre_unet_set_weight, L.gyre_unet_set_weight_lora
+    orig_set, orig_lora = L.gyre_unet_set_weight, L.gyre_unet_set_weight_delta
 
     class CountSet:
         def __call__(self, *args):
@@ -337,14 +337,14 @@ def test_no_reupload(nets, inputs):
             calls["lora_pairs" if args[6] > 0 else "lora_restore"] += 1
             return orig_lora(*args)
     versions = {k: p._version for k, p in a.named_parameters()}
-    L.gyre_unet_set_weight, L.gyre_unet_set_weight_lora = CountSet(), CountLora()
+    L.gyre_unet_set_weight, L.gyre_unet_set_weight_delta = CountSet(), CountLora()
     try:
         LR.attach_lora(a, kohya(a, seed=5), "x", 1.0)
         with_lora = fwd(a, inputs)
         LR.detach_loras(a)
         after = fwd(a, inputs)
     finally:
-        L.gyre_unet_set_weight, L.gyre_unet_set_weight_lora = orig_set, orig_lora
+        L.gyre_unet_set_weight, L.gyre_unet_set_weight_delta = orig_set, orig_lora
     k = len(TOUCHED)
     assert calls == {"set_weight": 0, "lora_pairs": k, "lora_restore": k}, calls
     assert k < len(list(a.named_parameters())) // 10
@@ -404,8 +404,8 @@ def test_errors(nets):
     with pytest.raises(ValueError):                                  # the two paths do not stack
         LR.apply_lora(a, good, "h")
     LR.detach_loras(a)
-    stale = LR.LoraFactors({name: (torch.zeros(w.shape[0] + 8, 4, device=DEV), torch.zeros(4, w.shape[1], device=DEV), 1.0)},
-                           a._handle_device)                       # factors uploaded for another model: refused before any call
+    stale = LR.Factors({name: LR.Term(_lib.DELTA_LORA, [(torch.zeros(w.shape[0] + 8, 4, device=DEV), torch.zeros(4, w.shape[1], device=DEV))], 1.0)},
+                       a._handle_device)                           # factors uploaded for another model: refused before any call
     with pytest.raises(ValueError):
         LR.attach_lora(a, stale, "z")
     assert not a._lora_attached["loras"] and not a._dirty

@@ -147,8 +147,11 @@ def test_operator_dtypes(name, bdt, mix):
                           LY.bound(base, terms, I_pad, geglu, 0.1803, HDT)) <= 1.0
 
 
-@pytest.mark.parametrize("shape", [(72, 12, 3, 3, 16, False, (33, 4)), (64, 24, 1, 1, 24, True, (130,)), (40, 20, 1, 1, 24, False, (1, 4, 33))],
-                         ids=["conv_pad", "geglu_r130", "matrix_pad"])
+BIT_SHAPES = [(72, 12, 3, 3, 16, False, (33, 4)), (64, 24, 1, 1, 24, True, (130,)), (40, 20, 1, 1, 24, False, (1, 4, 33))]
+BIT_IDS = ["conv_pad", "geglu_r130", "matrix_pad"]
+
+
+@pytest.mark.parametrize("shape", BIT_SHAPES, ids=BIT_IDS)
 def test_lora_terms_have_the_bits_of_repack_lora(shape):
     """LORA terms only, gaussian data (every rounding matters): bit-identical to gyre_op_repack_lora."""
     O, I, KH, KW, I_pad, geglu, ranks = shape
@@ -157,6 +160,26 @@ def test_lora_terms_have_the_bits_of_repack_lora(shape):
     pairs = [(up, down, float(np.float32(s))) for up, down, s in pairs]
     got = run_op(base, terms, I_pad, geglu, 0.1803)
     assert torch.equal(got.view(torch.int16), run_lora_op(base, pairs, I_pad, geglu, 0.1803).view(torch.int16))
+
+
+@pytest.mark.parametrize("bdt", [torch.float32, HDT], ids=["base_f32", "base_storage"])
+@pytest.mark.parametrize("shape", BIT_SHAPES, ids=BIT_IDS)
+def test_operator_instantiations_agree(shape, bdt):
+    """launch_repack_delta runs the LoRA-only instantiation of the kernel when every term is a LORA term and the general one
+    otherwise; on the same LORA terms the two must write the same bits.  The second call appends one FULL term whose diff is all
+    zeros at scale 1, which takes the general instantiation and adds fma(1, 0, acc) = acc to every element (exact unless acc is -0,
+    which gaussian data does not give; pad columns are written as +0 by both).  The shapes cover a partial row tile, pad columns,
+    the GEGLU interleave, ranks 1 and 33 around the 32-wide rank chunk and several terms.  The opposite mistake, a HADA or KRON
+    call sent to the LoRA-only instantiation, would compute those terms as low-rank products: the lattice cases of LY.CASES
+    (test_operator_lattice_is_bit_exact) already fail on that."""
+    O, I, KH, KW, I_pad, geglu, ranks = shape
+    base, pairs = LRF.gaussian(O, I, ranks, KH, KW, seed=21)
+    terms = [({"lora_up.weight": up, "lora_down.weight": down, "scale": np.float32(s)}, 1.0) for up, down, s in pairs]
+    zero = ({"diff": np.zeros(base.shape, np.float32), "scale": np.float32(1.0)}, 1.0)
+    lora_only = run_op(base, terms, I_pad, geglu, 0.1803, bdt)
+    general = run_op(base, terms + [zero], I_pad, geglu, 0.1803, bdt)
+    assert torch.equal(lora_only.view(torch.int16), general.view(torch.int16))
+    assert bool(lora_only[..., :I].any()) and not lora_only[..., I:].any()
 
 
 @pytest.mark.parametrize("shape", [(256, 256, 3, 3), (320, 250, 1, 1), (64, 24, 1, 1)], ids=["conv3x3", "matrix_padded_k", "geglu"])
@@ -333,9 +356,9 @@ def test_lora_and_lycoris_share_a_weight_one_repack_per_key(nets, inputs):
         bare = fwd(a, inputs)
     keys = [k for _, k, _ in attach]
     assert sorted(keys) == sorted(lyco_keys | lora_keys), "one repack per touched weight"
-    assert {k for f, k, _ in attach if f == "set_weight_delta"} == lyco_keys and {k for f, k, _ in attach if f == "set_weight_lora"} == lora_keys - lyco_keys
-    assert {k: n for f, k, n in attach if k in shared} == {k: 2 for k in shared}               # ... with both terms in it
-    assert sorted(k for _, k, _ in c.calls) == sorted(lyco_keys | lora_keys) and all(f == "set_weight_lora" and n == 0 for f, _, n in c.calls)
+    assert all(f == "set_weight_delta" for f, _, _ in attach), "every key goes through the one entry, never gyre_unet_set_weight"
+    assert {k: n for _, k, n in attach} == {k: (k in lyco_keys) + (k in lora_keys) for k in lyco_keys | lora_keys}      # pairs + terms that hit it
+    assert sorted(k for _, k, _ in c.calls) == sorted(lyco_keys | lora_keys) and all(f == "set_weight_delta" and n == 0 for f, _, n in c.calls)
     LC.apply_lycoris(b, lyco, "l", 0.5)                              # the same order on the host
     LR.apply_lora(b, lora, "k", 0.5)
     assert torch.equal(got, fwd(b, inputs)) and not torch.equal(got, base)
@@ -410,7 +433,7 @@ def test_errors(nets, inputs):
     assert list(a._lora_attached["loras"]) == list(range(8)) and not a._dirty
     LR.detach_loras(a)
     assert torch.equal(fwd(a, inputs), base)
-    stale = LC.LycoFactors({name: LC.Term(_lib.DELTA_FULL, [(None, torch.zeros(40, 32, device=DEV))], 1.0)}, a._handle_device)
+    stale = LC.Factors({name: LC.Term(_lib.DELTA_FULL, [(None, torch.zeros(40, 32, device=DEV))], 1.0)}, a._handle_device)
     with pytest.raises(ValueError):                                  # terms uploaded for another model: refused before any call
         LC.attach_lycoris(a, stale, "z")
     assert not a._lora_attached["loras"] and not a._dirty

@@ -133,3 +133,40 @@ def test_bf16_master_keeps_small_deltas():
     LR.remove_lora_from_model(net)
     assert torch.equal(w, base) and net._upload_source(name + ".weight", w) is not None
     assert not net._weight_overrides and net._upload_source(name + ".weight", w).dtype == torch.bfloat16
+
+
+def test_mixed_dtype_pair_is_one_fp32_lora_term():
+    """A file whose lora_up is fp16 and whose lora_down is fp32: a term's pair has ONE dtype code, so the constructor every LoRA
+    file goes through (lora.lora_term: upload_factors here, text_adapters.upload_text_factors for lora_te_ keys) promotes both
+    factors to fp32, for a matrix and for a conv with its 1 x 1 up, and the term fits the weight it was made for."""
+    from gyre_amd import _lib
+
+    class Shell(torch.nn.Module):
+        device = torch.device("cpu")
+
+        def __init__(self):
+            super().__init__()
+            self.lin, self.conv = torch.nn.Linear(8, 12), torch.nn.Conv2d(4, 6, 3)
+    net = Shell()
+    g = torch.Generator().manual_seed(0)
+    lora = {"lora_unet_lin.lora_up.weight": torch.randn(12, 2, generator=g).half(), "lora_unet_lin.lora_down.weight": torch.randn(2, 8, generator=g),
+            "lora_unet_lin.alpha": torch.tensor(1.0),
+            "lora_unet_conv.lora_up.weight": torch.randn(6, 3, 1, 1, generator=g).half(), "lora_unet_conv.lora_down.weight": torch.randn(3, 4, 3, 3, generator=g)}
+    f = LR.upload_factors(net, lora)
+    assert isinstance(f, LR.Factors) and sorted(f.names()) == ["conv.weight", "lin.weight"]
+    params = dict(net.named_parameters())
+    for name, key, scale in (("lin.weight", "lora_unet_lin", 0.5), ("conv.weight", "lora_unet_conv", 1.0)):
+        (term,) = f.hits(name)
+        (up, down), = term.ops
+        assert term.kind == _lib.DELTA_LORA and term.scale == scale and term.w1 is None
+        assert up.dtype == torch.float32 and down.dtype == torch.float32 and term.fits(params[name])
+        assert torch.equal(up, lora[key + ".lora_up.weight"].float().reshape(up.shape))               # the fp16 values, exactly
+        assert torch.equal(down, lora[key + ".lora_down.weight"])
+    # the text side builds its LORA terms with the same constructor, against an nn.Linear's weight
+    term = LR.lora_term(lora["lora_unet_lin.lora_up.weight"], lora["lora_unet_lin.lora_down.weight"], None, net.lin.weight,
+                        "lora_te_lin", torch.device("cpu"))
+    assert term.kind == _lib.DELTA_LORA and term.scale == 1.0 and {t.dtype for t in term.tensors()} == {torch.float32}
+    assert term.fits(net.lin.weight)
+    same = LR.lora_term(lora["lora_unet_lin.lora_up.weight"], lora["lora_unet_lin.lora_down.weight"].half(), None, net.lin.weight,
+                        "lora_te_lin", torch.device("cpu"))
+    assert {t.dtype for t in same.tensors()} == {torch.float16}                                       # one dtype: kept as it comes

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import lyco_ref as LY
-from gyre_amd import lora as LR, lycoris as LC
+from gyre_amd import _lib, lora as LR, lycoris as LC
 
 GOLDEN = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lycoris_vectors.npz"))
 META = json.loads(str(GOLDEN["meta"]))
@@ -150,5 +150,7 @@ def test_existing_lora_entry_points_still_refuse_lycoris():
     with pytest.raises(ValueError, match="Lycoris"):
         LR.apply_lora(net, mixed, "x")
     assert LC.is_lycoris(mixed) and LC.is_lycoris(_one()[1])
-    f = LR.LoraFactors({"lin.weight": (torch.zeros(12, 2), torch.zeros(2, 8), 0.5)}, torch.device("cpu"))
-    assert list(f.pairs) == ["lin.weight"] and list(f.names()) == ["lin.weight"] and f.hits("nope") == []
+    term = LR.Term(_lib.DELTA_LORA, [(torch.zeros(12, 2), torch.zeros(2, 8))], 0.5)
+    f = LR.Factors({"lin.weight": term}, torch.device("cpu"))
+    assert list(f.terms) == ["lin.weight"] and list(f.names()) == ["lin.weight"] and f.hits("nope") == []
+    assert f.hits("lin.weight") == [term] and LC.Term is LR.Term and LC.Factors is LR.Factors

@@ -92,3 +92,22 @@ def test_merge_kernels_have_no_scratch():
         for name in merge + [k for k in kernels if "k_repack_delta" in k]:
             assert kernels[name]["scratch_bytes_per_lane"] == 0, f"{name} in {src} spills"
             assert kernels[name]["lds_bytes"] == 2 * 32 * 68 * 4
+
+
+def test_lora_only_repack_keeps_the_occupancy_of_the_lora_kernel():
+    """k_repack_delta<true>, the instantiation a LoRA-only repack runs, in both storage builds: no scratch, 17408 bytes of LDS, and
+    an occupancy not below that of k_repack_lora, the separate LoRA kernel this instantiation replaced.  That kernel, compiled from
+    its last revision with the flags of gyre_amd/build.py and -Rpass-analysis=kernel-resource-usage, reported 68 VGPRs, no scratch
+    and 7 waves per SIMD in the bf16 build and the same three figures with -DGYRE_STORE_F16."""
+    import json
+    from gyre_amd import build as B
+    B.build()
+    data = json.load(open(B.RESOURCES_JSON))
+    lora_kernel_waves = {"kernels_lyco.hip": 7, "f16/kernels_lyco.hip": 7}
+    for src, waves in lora_kernel_waves.items():
+        both = {k: v for k, v in data[src].items() if "k_repack_delta" in k}
+        lora_only = [v for k, v in both.items() if "ILb1E" in k]                      # template <bool LORA_ONLY = true>
+        assert len(both) == 2 and len(lora_only) == 1, sorted(both)
+        r = lora_only[0]
+        assert r["scratch_bytes_per_lane"] == 0 and r["lds_bytes"] == 2 * 32 * 68 * 4, (src, r)
+        assert r["occupancy_waves_per_simd"] >= waves, (src, r)
