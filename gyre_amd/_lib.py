@@ -250,6 +250,10 @@ _SIGS = {
     "gyre_ctrl_bind": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _sz]),
     "gyre_ctrl_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "gyre_ctrl_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _sz, C.POINTER(_f), _i, _i, _i, C.POINTER(_vp), _i, _i]),
+    "gyre_ctrl_bind_slot_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "gyre_ctrl_bind_slot": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _vp, _sz]),
+    "gyre_ctrl_forward_slot": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, C.POINTER(_f), _i, _i, _i, C.POINTER(_vp), _i,
+                                    _i]),
     "gyre_prof_set_mask": (_i, [C.c_uint64]),
     "gyre_prof_num_classes": (_i, []),
     "gyre_prof_class_name": (C.c_char_p, [_i]),
@@ -341,6 +345,8 @@ _SIGS = {
     "gyre_op_scale_add": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _sz, _i]),
     "gyre_op_pixel_shuffle2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_ctrl_emit": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _i]),
+    "gyre_op_ctrl_emit_masked": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _i, _vp, _i]),
+    "gyre_op_nchw_to_nhwc_masked": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "gyre_op_conv3x3_valid": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "gyre_op_inorm_workspace": (_sz, [_i, _sz, _i]),
     "gyre_op_inorm_stats": (_i, [_vp, _vp, _i, _i, _sz, _i, _f, _vp, _vp]),
@@ -390,6 +396,10 @@ def lib(storage: Optional[int] = None) -> C.CDLL:
             l = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
         except OSError as e:  # pragma: no cover
             raise GyreError(f"cannot load {path}: {e}") from e
+        missing = [name for name in _SIGS if not hasattr(l, name)]
+        if missing:      # a library built from older sources: the ABI number has stayed 1 over additions, so say it here and not at a call
+            raise GyreError(f"{path} is stale: it lacks {len(missing)} entry point(s) ({', '.join(missing[:4])}"
+                            f"{', ...' if len(missing) > 4 else ''}); run `python -c 'import __graft_entry__ as g; g.build()'`")
         for name, (res, args) in _SIGS.items():
             fn = getattr(l, name)
             fn.restype = res

@@ -14,6 +14,11 @@ runs once per step and writes the N + 1 scaled residuals straight into NCHW buff
 window of them (``out_batch`` / ``out_offset``: the guided half of a CFG-parallel call) and on top of what another control model left
 there (``accumulate``).  Parameters carry the diffusers state-dict names, so checkpoints load with ``load_state_dict``.  All compute
 happens in the HIP library (gyre_ctrl_bind / gyre_ctrl_forward); there is no PyTorch fallback.
+
+A model keeps ``SLOTS`` independent binds (gyre_ctrl_bind_slot / gyre_ctrl_forward_slot): the leaves of a hires-fix or graft tree
+alternate on one control model every step, each with its own hint image, size and context.  A bind may carry one mask per residual
+(``masks``: the hint's mask at every residual resolution, multiplied in by the hand-off kernel), a forward a latent mask (``x_mask``:
+next to a 9-channel inpaint UNet the control model sees latents * mask channel, multiplied in by the entry pass).
 """
 from __future__ import annotations
 
@@ -42,7 +47,7 @@ class GyreHipControlNet(_NativeModule):
             raise NotImplementedError("the conditioning embedding has four widths, each a multiple of 8")
         if c.controlnet_conditioning_channel_order not in ("rgb", "bgr"):
             raise ValueError(f"unknown controlnet_conditioning_channel_order: {c.controlnet_conditioning_channel_order}")
-        self._bound = None            # (handle, B, image H, image W, S) of the last bind
+        self._bound = {}              # slot -> (handle, B, image H, image W, S) of its last bind
         self._outs = None             # residual buffers of the request
         _build_tree(self, controlnet_param_shapes(c))
 
@@ -113,7 +118,7 @@ class GyreHipControlNet(_NativeModule):
 
     def _invalidate(self):
         super()._invalidate()
-        self._bound = None            # new weights: the embedding and the projected context are stale (the library drops them too)
+        self._bound = {}              # new weights: the embeddings and the projected contexts are stale (the library drops them too)
 
     def residual_shapes(self, H: int, W: int) -> List[Tuple[int, int, int]]:
         """(channels, h, w) of the N down residuals and the mid residual for H x W latents (a stride-2 convolution rounds an odd size up)."""
@@ -128,10 +133,21 @@ class GyreHipControlNet(_NativeModule):
         out.append((c.block_out_channels[-1], h, w))
         return out
 
+    SLOTS = 4                         # include/gyre_hip.h GYRE_CTRL_SLOTS
+
+    def _check_slot(self, slot: int) -> int:
+        if not isinstance(slot, int) or slot < 0 or slot >= self.SLOTS:
+            raise ValueError(f"bind slot must be in [0, {self.SLOTS}), got {slot!r}")
+        return slot
+
     @torch.no_grad()
-    def bind(self, image: torch.Tensor, encoder_hidden_states: torch.Tensor) -> None:
-        """Once per request: embed the hint image [1 or B, conditioning_channels, 8h, 8w] and project the text context [B, S, D]."""
+    def bind(self, image: torch.Tensor, encoder_hidden_states: torch.Tensor, *, slot: int = 0,
+             masks: Optional[Sequence[torch.Tensor]] = None) -> None:
+        """Once per request: embed the hint image [1 or B, conditioning_channels, 8h, 8w] and project the text context [B, S, D] into
+        bind slot ``slot``.  masks: one [1 or B, 1, h_k, w_k] tensor per residual (residual_shapes), copied into the model; every
+        residual of this slot is multiplied by its mask on the way out."""
         c = self.config
+        slot = self._check_slot(slot)
         if image.ndim != 4 or image.shape[1] != c.conditioning_channels:
             raise ValueError(f"expected a hint image [B,{c.conditioning_channels},H,W], got {tuple(image.shape)}")
         ctx = encoder_hidden_states
@@ -154,16 +170,37 @@ class GyreHipControlNet(_NativeModule):
         _lib.require_gpu_tensor(x, "hint image")
         _lib.require_gpu_tensor(ctx, "encoder_hidden_states")
         L = self._L()
-        self._bound = None
+        marr = hw = None
+        n = mB = 0
+        if masks is not None:
+            shapes = self.residual_shapes(H // 8, W // 8)
+            if len(masks) != len(shapes):
+                raise ValueError(f"{len(shapes)} residual masks expected, got {len(masks)}")
+            mB = masks[0].shape[0]
+            for m, (_, rh, rw) in zip(masks, shapes):
+                if m.ndim != 4 or tuple(m.shape) != (mB, 1, rh, rw) or mB not in (1, B):
+                    raise ValueError(f"a residual mask must be [1 or {B}, 1, {rh}, {rw}], got {tuple(m.shape)}")
+            masks = [m.to(dev, torch.float32).contiguous() for m in masks]
+            for m in masks:
+                _lib.require_gpu_tensor(m, "residual mask")
+            n = len(masks)
+            marr = (C.c_void_p * n)(*[m.data_ptr() for m in masks])
+            hw = (C.c_int32 * (2 * n))(*[v for m in masks for v in m.shape[-2:]])
+        self._bound.pop(slot, None)
         with torch.cuda.device(dev):
-            need = L.gyre_ctrl_bind_workspace_bytes(C.c_void_p(h), Bi, H, W, B)
+            need = L.gyre_ctrl_bind_slot_workspace_bytes(C.c_void_p(h), slot, Bi, H, W, B)
             if need == 0:
                 _lib.check(-1, L)
             ws = self._workspace(need, dev)
             wp = (ws.data_ptr() + 255) & ~255
-            _lib.check(L.gyre_ctrl_bind(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()), _lib.dtype_code(x),
-                                        Bi, H, W, C.c_void_p(ctx.data_ptr()), _lib.dtype_code(ctx), B, S, C.c_void_p(wp), need), L)
-        self._bound = (h, B, H, W, S)
+            if slot == 0 and masks is None:            # the entry point every request used before there were slots
+                _lib.check(L.gyre_ctrl_bind(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()), _lib.dtype_code(x),
+                                            Bi, H, W, C.c_void_p(ctx.data_ptr()), _lib.dtype_code(ctx), B, S, C.c_void_p(wp), need), L)
+            else:
+                _lib.check(L.gyre_ctrl_bind_slot(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), slot, C.c_void_p(x.data_ptr()),
+                                                 _lib.dtype_code(x), Bi, H, W, C.c_void_p(ctx.data_ptr()), _lib.dtype_code(ctx), B, S, marr, hw, n,
+                                                 mB, C.c_void_p(wp), need), L)
+        self._bound[slot] = (h, B, H, W, S)
         self._outs = None
 
     def new_outputs(self, B: int, H: int, W: int, device, dtype=None) -> List[torch.Tensor]:
@@ -172,19 +209,23 @@ class GyreHipControlNet(_NativeModule):
 
     @torch.no_grad()
     def forward(self, latents: torch.Tensor, t, *, scales: Optional[Sequence[float]] = None, out: Optional[List[torch.Tensor]] = None,
-                accumulate: bool = False, out_batch: Optional[int] = None, out_offset: int = 0) -> List[torch.Tensor]:
+                accumulate: bool = False, out_batch: Optional[int] = None, out_offset: int = 0, slot: int = 0,
+                x_mask: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """The N + 1 residuals of one step (N down residuals, then the mid one), each times its scale, written to samples
         [out_offset, out_offset + B) of ``out`` (batch ``out_batch``; default: B, offset 0).  Without ``out`` the buffers are the
-        module's own, allocated at the first step of a request and reused by every later one."""
+        module's own, allocated at the first step of a request and reused by every later one.  slot: the bind this step runs on.
+        x_mask: [1 or B, 1, H, W]; the model sees latents * x_mask (the product in fp32, one rounding to the model's storage)."""
         c = self.config
+        slot = self._check_slot(slot)
         if latents.ndim != 4 or latents.shape[1] != c.in_channels:
             raise ValueError(f"expected latents [B,{c.in_channels},H,W], got {tuple(latents.shape)}")
         B, _, H, W = latents.shape
         dev = latents.device
         h = self._sync(dev)
-        if self._bound is None or self._bound[0] != h:
+        bound = self._bound.get(slot)
+        if bound is None or bound[0] != h:
             raise ValueError("GyreHipControlNet.forward needs a bind(image, encoder_hidden_states) call first")
-        _, bB, bH, bW, S = self._bound
+        _, bB, bH, bW, S = bound
         if B != bB or H * 8 != bH or W * 8 != bW:
             raise ValueError(f"latents {B} x {H} x {W} do not match the bound request (batch {bB}, hint image {bH} x {bW})")
         shapes = self.residual_shapes(H, W)
@@ -218,6 +259,13 @@ class GyreHipControlNet(_NativeModule):
         tt = tt.contiguous()
         x = latents.contiguous()
         _lib.require_gpu_tensor(x, "latents")
+        xm, xmB = None, 0
+        if x_mask is not None:
+            if x_mask.ndim != 4 or x_mask.shape[0] not in (1, B) or tuple(x_mask.shape[1:]) != (1, H, W):
+                raise ValueError(f"x_mask must be [1 or {B}, 1, {H}, {W}], got {tuple(x_mask.shape)}")
+            xm = x_mask.to(dev, torch.float32).contiguous()
+            _lib.require_gpu_tensor(xm, "x_mask")
+            xmB = xm.shape[0]
         L = self._L()
         with torch.cuda.device(dev):
             need = L.gyre_ctrl_workspace_bytes(C.c_void_p(h), B, H, W, S)
@@ -226,7 +274,13 @@ class GyreHipControlNet(_NativeModule):
             ws = self._workspace(need, dev)
             wp = (ws.data_ptr() + 255) & ~255
             arr = (C.c_void_p * n)(*[o.data_ptr() for o in out])
-            _lib.check(L.gyre_ctrl_forward(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()), _lib.dtype_code(x),
-                                           C.c_void_p(tt.data_ptr()), B, H, W, C.c_void_p(wp), need, (C.c_float * n)(*sc),
-                                           1 if accumulate else 0, out_batch, out_offset, arr, n, _lib.dtype_code(out[0])), L)
+            if slot == 0 and xm is None:
+                _lib.check(L.gyre_ctrl_forward(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(x.data_ptr()), _lib.dtype_code(x),
+                                               C.c_void_p(tt.data_ptr()), B, H, W, C.c_void_p(wp), need, (C.c_float * n)(*sc),
+                                               1 if accumulate else 0, out_batch, out_offset, arr, n, _lib.dtype_code(out[0])), L)
+            else:
+                _lib.check(L.gyre_ctrl_forward_slot(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), slot, C.c_void_p(x.data_ptr()),
+                                                    _lib.dtype_code(x), None if xm is None else C.c_void_p(xm.data_ptr()), xmB,
+                                                    C.c_void_p(tt.data_ptr()), B, H, W, C.c_void_p(wp), need, (C.c_float * n)(*sc),
+                                                    1 if accumulate else 0, out_batch, out_offset, arr, n, _lib.dtype_code(out[0])), L)
         return out

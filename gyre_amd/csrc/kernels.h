@@ -5,6 +5,9 @@
 
 // ---- layout / small ops (kernels_elem.hip) ----------------------------------
 int launch_nchw_to_nhwc(hipStream_t st, const void* x, int dtype, int B, int C, int HW, int Cpad, bf16_t* y);
+// y[b][p][c] = rnd(x[b][c][p] * mask[mask_B == 1 ? 0 : b][p]): the product in fp32 from the source dtype, one rounding to storage
+int launch_nchw_to_nhwc_masked(hipStream_t st, const void* x, int dtype, int B, int C, int HW, int Cpad, const float* mask, int mask_B,
+                               bf16_t* y);
 int launch_add_nchw_into_nhwc(hipStream_t st, const void* r, int dtype, int B, int C, int HW, int Cpad, bf16_t* y);
 int launch_ctx_to_bf16(hipStream_t st, const void* x, int dtype, size_t n, bf16_t* y);
 // dst[o][0:inner] = dst[o][inner:2*inner] = src[o][0:inner] (bytes, multiples of 16), o < outer
@@ -306,6 +309,10 @@ int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x 
 // accumulate == 0 assigns and writes every other sample of `out` as zero, accumulate == 1 adds and leaves the others alone
 int launch_ctrl_emit(hipStream_t st, const bf16_t* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
                      int out_dtype, int out_B, int out_b0);
+// the same with every product times mask[mask_B == 1 ? 0 : b][p] (fp32 [mask_B][HW]): out = rnd(fl(fl(scale f) m) [+ old]); mask ==
+// nullptr is launch_ctrl_emit
+int launch_ctrl_emit_masked(hipStream_t st, const bf16_t* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
+                            int out_dtype, int out_B, int out_b0, const float* mask, int mask_B);
 
 // ---- MFMA GEMM / implicit-GEMM conv (kernels_gemm.hip) -------------------------
 enum { GEMM_LINEAR = 0, GEMM_CONV3 = 1 };

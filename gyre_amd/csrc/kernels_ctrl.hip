@@ -1,6 +1,6 @@
 // Element-wise kernels of the ControlNet graph (model_ctrl.hip): the SiLU between the convolutions of the hint-image embedding (the
 // library has SiLU only fused into GroupNorm) and the hand-off of one zero-convolution output to the UNet's residual inputs - a scaled,
-// optionally accumulating NHWC -> NCHW copy into a batch window of the caller's buffer.  Everything else of the graph runs on the
+// optionally accumulating, optionally masked NHWC -> NCHW copy into a batch window of the caller's buffer.  Everything else of the graph runs on the
 // kernels the UNet already uses.  Both are streaming passes with 16-byte accesses on the storage side.
 #include "kernels.h"
 #include "../../include/gyre_hip.h"
@@ -32,8 +32,12 @@ int launch_silu(hipStream_t st, bf16_t* x, size_t n) {
 #define CE_TP 64
 #define CE_TC 64
 #define CE_LD (CE_TC / 2 + 1)
-__global__ __launch_bounds__(256) void k_ctrl_emit(const bf16_t* __restrict__ f, int B, int C, int HW, int Cpad, float scale, int accumulate,
-                                                   void* __restrict__ out, int dtype, int b0) {
+// MASKED: the store-phase lane (one pixel) reads m = mask[mb][p] once - a wave reads 64 consecutive floats, 256 B - and reuses it for
+// its 16 channels: out = rnd(fl(fl(scale f) m) [+ old]).  m == 0 gives +-0 for a finite f, NaN stays NaN.  The unmasked instantiation
+// is the kernel as it was: no mask argument is read and no instruction is added.
+template <bool MASKED>
+__device__ __forceinline__ void ctrl_emit_body(const bf16_t* __restrict__ f, int B, int C, int HW, int Cpad, float scale, int accumulate,
+                                               void* __restrict__ out, int dtype, int b0, const float* __restrict__ mask, int mask_B) {
     __shared__ uint32_t tile[CE_TP * CE_LD];
     const int tid = threadIdx.x;
     const int p0 = blockIdx.x * CE_TP, c0 = blockIdx.y * CE_TC;
@@ -52,6 +56,8 @@ __global__ __launch_bounds__(256) void k_ctrl_emit(const bf16_t* __restrict__ f,
     __syncthreads();
     const int pl = tid & 63, cw = (tid >> 6) * 16, p = p0 + pl;
     if (p >= HW) return;
+    float m = 1.f;
+    if (MASKED) m = live ? mask[(size_t)(mask_B == 1 ? 0 : b) * HW + p] : 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const uint32_t w = tile[pl * CE_LD + (cw >> 1) + j];
@@ -62,20 +68,40 @@ __global__ __launch_bounds__(256) void k_ctrl_emit(const bf16_t* __restrict__ f,
             if (c >= C) continue;
             const size_t o = ((size_t)ob * C + c) * HW + p;
             float val = live ? __fmul_rn(scale, v2[h]) : 0.f;
+            if (MASKED) val = live ? __fmul_rn(val, m) : 0.f;
             if (accumulate) val = __fadd_rn(load_as_f32(out, dtype, o), val);
             store_from_f32(out, dtype, o, val);
         }
     }
 }
-int launch_ctrl_emit(hipStream_t st, const bf16_t* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
-                     int out_dtype, int out_B, int out_b0) {
+__global__ __launch_bounds__(256) void k_ctrl_emit(const bf16_t* __restrict__ f, int B, int C, int HW, int Cpad, float scale, int accumulate,
+                                                   void* __restrict__ out, int dtype, int b0) {
+    ctrl_emit_body<false>(f, B, C, HW, Cpad, scale, accumulate, out, dtype, b0, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void k_ctrl_emit_masked(const bf16_t* __restrict__ f, int B, int C, int HW, int Cpad, float scale,
+                                                          int accumulate, void* __restrict__ out, int dtype, int b0,
+                                                          const float* __restrict__ mask, int mask_B) {
+    ctrl_emit_body<true>(f, B, C, HW, Cpad, scale, accumulate, out, dtype, b0, mask, mask_B);
+}
+// mask == nullptr: the unmasked kernel; otherwise fp32 [mask_B][HW] with mask_B == 1 (one mask for every sample) or B
+int launch_ctrl_emit_masked(hipStream_t st, const bf16_t* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
+                            int out_dtype, int out_B, int out_b0, const float* mask, int mask_B) {
     if (out_dtype < 0 || out_dtype > 2) GYRE_FAIL(GYRE_ERR_INVALID, "bad dtype");
     if (B < 1 || C < 1 || HW < 1 || Cpad < C || (Cpad & 7)) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl_emit: needs B, C, HW >= 1 and Cpad >= C a multiple of 8");
     if (out_b0 < 0 || out_B < 1 || out_b0 + B > out_B) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl_emit: the samples [out_b0, out_b0 + B) must lie inside the output batch");
+    if (mask && mask_B != 1 && mask_B != B) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl_emit: the mask needs batch 1 or B");
     const int nz = accumulate ? B : out_B;
     if (nz > 65535 || (C + CE_TC - 1) / CE_TC > 65535) GYRE_FAIL(GYRE_ERR_INVALID, "ctrl_emit: batch or channel count beyond the grid");
     const dim3 grid((unsigned)((HW + CE_TP - 1) / CE_TP), (unsigned)((C + CE_TC - 1) / CE_TC), (unsigned)nz);
-    hipLaunchKernelGGL(k_ctrl_emit, grid, dim3(256), 0, st, f, B, C, HW, Cpad, scale, accumulate ? 1 : 0, out, out_dtype, out_b0);
+    if (mask)
+        hipLaunchKernelGGL(k_ctrl_emit_masked, grid, dim3(256), 0, st, f, B, C, HW, Cpad, scale, accumulate ? 1 : 0, out, out_dtype, out_b0,
+                           mask, mask_B);
+    else
+        hipLaunchKernelGGL(k_ctrl_emit, grid, dim3(256), 0, st, f, B, C, HW, Cpad, scale, accumulate ? 1 : 0, out, out_dtype, out_b0);
     GYRE_LAUNCH_CHECK();
     return 0;
+}
+int launch_ctrl_emit(hipStream_t st, const bf16_t* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
+                     int out_dtype, int out_B, int out_b0) {
+    return launch_ctrl_emit_masked(st, f, B, C, HW, Cpad, scale, accumulate, out, out_dtype, out_B, out_b0, nullptr, 0);
 }

@@ -72,6 +72,39 @@ int launch_nchw_to_nhwc(hipStream_t st, const void* x, int dtype, int B, int C, 
     return 0;
 }
 
+// The same pass with every value times a per-pixel mask (fp32 [mask_B][HW], mask_B == 1 or B): the latents a ControlNet sees next to
+// a 9-channel inpaint UNet are latents[:, 0:4] * latents[:, [4]].  One lane per pixel reads its mask value once (a wave reads 64
+// consecutive floats) and reuses it for every channel; the product is fp32 from the source dtype with one rounding to storage.
+__global__ void k_nchw_to_nhwc_masked(const void* __restrict__ x, int dtype, int C, int HW, int Cpad, const float* __restrict__ mask,
+                                      int mask_B, bf16_t* __restrict__ y, size_t total_pix) {
+    size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // over B*HW
+    if (pix >= total_pix) return;
+    size_t n = pix / HW, p = pix % HW;
+    const size_t base = n * (size_t)C * HW + p;
+    const float m = mask[(mask_B == 1 ? 0 : n) * (size_t)HW + p];
+    for (int c0 = 0; c0 < Cpad; c0 += 8) {
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            int c = c0 + j;
+            f[j] = c < C ? __fmul_rn(load_as_f32(x, dtype, base + (size_t)c * HW), m) : 0.0f;
+        }
+        *(uint4*)(y + pix * Cpad + c0) = pack8(f);
+    }
+}
+int launch_nchw_to_nhwc_masked(hipStream_t st, const void* x, int dtype, int B, int C, int HW, int Cpad, const float* mask, int mask_B,
+                               bf16_t* y) {
+    if (!mask) return launch_nchw_to_nhwc(st, x, dtype, B, C, HW, Cpad, y);
+    if (dtype < 0 || dtype > 2) GYRE_FAIL(-1, "bad dtype");
+    if (B < 1 || C < 1 || HW < 1 || Cpad < C || (Cpad & 7)) GYRE_FAIL(-1, "nchw_to_nhwc_masked: needs B, C, HW >= 1 and Cpad >= C a multiple of 8");
+    if (mask_B != 1 && mask_B != B) GYRE_FAIL(-1, "nchw_to_nhwc_masked: the mask needs batch 1 or B");
+    size_t total = (size_t)B * HW;
+    hipLaunchKernelGGL(k_nchw_to_nhwc_masked, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, dtype, C, HW, Cpad, mask, mask_B,
+                       y, total);
+    GYRE_LAUNCH_CHECK();
+    return 0;
+}
+
 // dst[o][0 : inner] = dst[o][inner : 2 inner] = src[o][0 : inner] for o < outer (inner in 16-byte vectors): a half batch
 // written twice - the two halves of a CFG-parallel call share every activation up to the first cross-attention
 __global__ __launch_bounds__(256) void k_dup_batch(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t inner, size_t total) {

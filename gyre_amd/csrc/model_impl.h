@@ -1235,6 +1235,9 @@ struct UNetTrunk {
     std::vector<Level> down;
     ResW mid0, mid1; TransW mid_attn;
     std::vector<int> skip_ch;            // channels of the skip connections in the order they are produced, conv_in first
+    // per-call: a mask fp32 [xin_mask_B == 1 or Bx][H][W] the entry pass of time_embed multiplies the latents by (the ControlNet next to
+    // a 9-channel inpaint UNet; nullptr everywhere else)
+    const float* xin_mask = nullptr; int xin_mask_B = 0;
 
     template <typename F> void for_each_cross_attn(F f) {
         for (auto& lv : down) for (auto& t : lv.attn) for (auto& b : t.blocks) f(b.a2);
@@ -1335,7 +1338,8 @@ struct UNetTrunk {
         TRY(e.alloc(t2, B, 1, 1, temb_dim, 4));
         TRY(e.alloc(tp, B, 1, 1, temb_cols, 4));
         if (!e.dry()) {
-            TRY(launch_nchw_to_nhwc(st, x, xdt, Bx, c.in_channels, H * W, xin.C, xin.p));
+            if (xin_mask) TRY(launch_nchw_to_nhwc_masked(st, x, xdt, Bx, c.in_channels, H * W, xin.C, xin_mask, xin_mask_B, xin.p));
+            else TRY(launch_nchw_to_nhwc(st, x, xdt, Bx, c.in_channels, H * W, xin.C, xin.p));
             if (cx_S) TRY(launch_ctx_to_bf16(st, ctx, cdt, (size_t)B * cx_S * D, cx.p));
             TRY(launch_timestep_linear(st, t, Bt, c0, c.flip_sin_to_cos, c.freq_shift, (float*)emb.p, te1w, te1b, temb_dim, (float*)t1.p,
                                        temb_dim));

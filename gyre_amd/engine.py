@@ -30,9 +30,13 @@ the adapter once per request, its states added inside the UNet on every step (gy
 their fuser likewise (GyreHipT2IStyleAdapter / GyreHipT2IFuser: style tokens extend the text context once per request).  Hint images handled by a ControlNet
 (gyre_amd/controlnet.py GyreHipControlNet) run natively as well: the hint image and the text context are bound once per request, the
 control model runs once per UNet evaluation and its residuals go to the UNet's residual inputs (schedulers.UNetWithControlnet).
+ControlNet hints also run under hires fix (on by default: every leaf of the tree has its own copy of the hint on its own bind slot of
+the control model), with an alpha plane as their mask, and in an inpaint request (``mask_image``): with a grafted inpaint pair
+and next to a 9-channel inpaint UNet, where the control model sees latents x mask channel (unified_pipeline.py:1016-1024).  As in the
+reference (for_model(mask=None), :2026) the request's ``mask_image`` is not the hint's mask.
 Features outside the native hot path raise NotImplementedError (-> gRPC UNIMPLEMENTED, services/exception_to_grpc.py): depth maps /
-depth UNets, foreign hint handlers, masked hints, hints together with hires fix / grafted inpaint /
-CLIP guidance / shard_devices, ControlNet hints with a 9-channel inpaint UNet.  CLIP guidance
+depth UNets, foreign hint handlers, masked T2I hints, T2I hints together with hires fix / grafted inpaint, any hint together
+with CLIP guidance / shard_devices.  CLIP guidance
 is implemented (gyre_amd/clipguided.py over the native input-gradient sweeps).  ``lora=`` takes LoRA files (kohya-ss, diffusers) and,
 as the reference routes them (unified_pipeline.py:2210-2233: what ``detect_lora_type`` refuses goes to ``apply_lycoris``), LyCORIS files
 (LoCon, LoHa, LoKr, full diff; gyre_amd/lycoris.py): one attach for the whole request, every touched weight repacked once on the
@@ -399,12 +403,15 @@ class GyreUnifiedPipeline:
                 TA.attach(te, [(self._text_factors(te, t), TA.text_scale(w)) for t, w in text_specs])
         return tokenizer
 
-    def _hints(self, hint_images, mask_image) -> list:
+    def _hints(self, hint_images, mask_image, inpaint_request: bool = False) -> list:
         """The reference's hint loop (unified_pipeline.py:1994-2047) for what is native: every hint image needs exactly one model
         from the hintset manager and that model must be a GyreHipT2IAdapter (-> hints.T2IHint, or hints.CoAdapterHint with the
         hintset's fuser when it was loaded as a co-adapter), a GyreHipT2IStyleAdapter (-> hints.StyleHint with the hintset's clip_model,
         feature_extractor, fuser and the hint's clip_layer) or a GyreHipControlNet (-> hints.ControlNetHint; same priority and weight mapping).  Depth hints routed to a depth UNet and foreign handlers stay
-        NotImplementedError; a hint type nobody handles is the reference's EnvironmentError."""
+        NotImplementedError; a hint type nobody handles is the reference's EnvironmentError.  inpaint_request: the caller hands
+        ``mask_image`` on to a pipeline that serves ControlNet hints next to it (``__call__`` does); as in the reference
+        (for_model(mask=None), unified_pipeline.py:2026) the request's mask is never the hint's own mask.  Without it a ControlNet
+        hint together with a mask keeps raising, as it did before the pipeline could."""
         from .controlnet import GyreHipControlNet
         from .hints import CoAdapterHint, ControlNetHint, StyleHint, T2IHint
         from .t2i import GyreHipT2IAdapter, GyreHipT2IStyleAdapter
@@ -424,8 +431,8 @@ class GyreUnifiedPipeline:
                 raise ValueError(f"Unknown set of hint models: {models.keys()}")
             _, model = models.popitem()
             if isinstance(model, GyreHipControlNet):
-                if mask_image is not None:
-                    raise NotImplementedError("ControlNet hints together with a mask (the reference resizes it for the hint with an unpinned lanczos)")
+                if mask_image is not None and not inpaint_request:
+                    raise NotImplementedError("ControlNet hints together with a mask need a caller that serves them (inpaint_request=True)")
                 hints.append(ControlNetHint(model, hint_image.image, mask=None, weight=weight, soft_injection=priority != "balanced",
                                             cfg_only=priority == "hint"))
                 continue
@@ -463,7 +470,7 @@ class GyreUnifiedPipeline:
         if depth_map is not None:
             raise NotImplementedError("depth-map conditioning (depth UNet) is outside the native hot path")
         from .hints import ControlNetHint
-        all_hints = self._hints(hint_images, mask_image)
+        all_hints = self._hints(hint_images, mask_image, inpaint_request=True)
         t2i_hints = [h for h in all_hints if not isinstance(h, ControlNetHint)]
         controlnet_hints = [h for h in all_hints if isinstance(h, ControlNetHint)]
         if all_hints and len(self._shard_devices) > 1:

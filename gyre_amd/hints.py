@@ -7,13 +7,19 @@
 
 The adapter itself runs natively (gyre_amd/t2i.py); what is here is the per-level weighting of its states and the sums the CFG
 wrappers receive.  T2IHint and combine_t2i_states refuse style adapters and co-adapters; those enter through StyleHint, CoAdapterHint
-and build_t2i_conditioning at the end of this file (gyre_amd/pipeline.py calls them once per request, engine._hints builds them).  Masked hints
-(the mask resize is an unpinned lanczos3) raise NotImplementedError.  The ControlNet itself runs natively too (gyre_amd/controlnet.py): its hint only decides the per-residual scales,
-which half of a CFG call the model sees and where in the shared residual buffers its outputs land; masked ControlNet hints raise for
-the same reason.
+and build_t2i_conditioning at the end of this file (gyre_amd/pipeline.py calls them once per request, engine._hints builds them).  Masked T2I
+hints raise NotImplementedError.  The ControlNet itself runs natively too (gyre_amd/controlnet.py): its hint decides the per-residual
+scales, which half of a CFG call the model sees, where in the shared residual buffers its outputs land and which of the model's bind
+slots it runs on (the leaves of a hires-fix or graft tree alternate on one model every step, each leaf with its own copy of the hint).
+A ControlNet hint may carry a mask - explicit, or the alpha plane of an RGBA image: ``resized_mask`` (UnifiedPipelineHint.resized_mask,
+unified_pipeline.py:810-828, over gyre_amd.images.resize) brings it to every residual's resolution once per bind and the model
+multiplies it in on the device.  Next to a 9-channel inpaint UNet the control model sees latents x mask channel and the hint image x
+that mask at image resolution (unified_pipeline.py:1016-1024), computed once per leaf.  ``extend`` on every hint class is
+UnifiedPipelineHint.extend (:799-808): a new hint from the stored constructor arguments, updated.
 """
 from __future__ import annotations
 
+import inspect
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -31,7 +37,35 @@ def normalise_tensor(t: Tensor, channels: int) -> Tensor:
     raise ValueError(f"Unknown number of channels {channels}")
 
 
-class T2IHint:
+def resized_mask(state_shape, mask: Tensor) -> Tensor:
+    """UnifiedPipelineHint.resized_mask for a mask that is there: images.resize(mask, (h_state / h_mask, w_state / w_mask)), lanczos3
+    with antialiasing, clamped to [0, 1].  state_shape: anything whose last two entries are the state's height and width.  The size of
+    one must be a whole multiple of the other's (the reference's two asserts)."""
+    from .images import resize
+    hs, ws = int(state_shape[-2]), int(state_shape[-1])
+    hm, wm = int(mask.shape[-2]), int(mask.shape[-1])
+    if max(hm, hs) % min(hm, hs) or max(wm, ws) % min(wm, ws):
+        raise ValueError(f"a hint mask of {hm} x {wm} cannot be resized to a state of {hs} x {ws}: one size must be a whole multiple of the other")
+    for have, want in ((hm, hs), (wm, ws)):
+        if want < have and 3 * (have // want) > have - 1:                 # the stretched lanczos3 reaches 3 x the factor past each edge
+            raise ValueError(f"a hint mask of {hm} x {wm} cannot be resized to a state of {hs} x {ws}: lanczos3 over reflect padding needs "
+                             "the smaller size to be at least 4 (a hint image of at least 256 pixels a side for an SD control model)")
+    return resize(mask, (hs / hm, ws / wm))
+
+
+class _Extendable:
+    def extend(self, callback=None, **kwargs):
+        """UnifiedPipelineHint.extend: a new hint of the same class from the constructor arguments this one holds, updated with
+        ``kwargs`` and then with what ``callback(**arguments)`` returns.  The new hint shares nothing per-request with this one."""
+        keys = [k for k in inspect.signature(self.__init__).parameters if k != "self"]
+        cargs = {k: getattr(self, k) for k in keys}
+        cargs.update(kwargs)
+        if callback is not None:
+            cargs.update(callback(**cargs))
+        return self.__class__(**cargs)
+
+
+class T2IHint(_Extendable):
     """One hint image bound to its adapter.  Calling it runs the adapter and returns the weighted per-level states."""
 
     def __init__(self, model, image: Tensor, mask: Optional[Tensor] = None, weight: float = 1.0, soft_injection: bool = False,
@@ -50,9 +84,9 @@ class T2IHint:
             if mask.mean() == 1.0 and mask.std() == 0.0:      # pure ones: the reference discards it
                 mask = None
         if mask is not None:
-            raise NotImplementedError("masked T2I hints (the reference resizes the mask with an unpinned lanczos3)")
+            raise NotImplementedError("masked T2I hints (the per-state multiply by the resized mask is not built)")
         channels = model.config.cin // 64 if "cin" in model.config else 3
-        self.model, self.image = model, normalise_tensor(normalise_tensor(image, 3), channels)
+        self.model, self.image, self.mask = model, normalise_tensor(normalise_tensor(image, 3), channels), None
         self.weight, self.soft_injection, self.cfg_only = weight, soft_injection, cfg_only
 
     def layer_weights(self):
@@ -94,7 +128,22 @@ def combine_t2i_states(hints: Sequence) -> Optional[Dict[str, List[Tensor]]]:
     return out
 
 
-class ControlNetHint:
+REBIND_EVERY_CALL = False      # private switch for tests and timing: no bind slots, every call binds slot 0 again
+
+
+def has_bind_slots(model) -> bool:
+    """Does this control-model shell keep bind slots, residual masks and a latent mask (GyreHipControlNet: ``SLOTS`` binds,
+    ``bind(..., slot=, masks=)``, ``forward(..., slot=, x_mask=)``)?  A shell with the older surface - ``bind(image, ctx)`` alone - can
+    serve neither a masked hint nor the leaves of a hires-fix / graft tree, and keeps raising NotImplementedError for them."""
+    return int(getattr(model, "SLOTS", 0) or 0) > 0
+
+
+def _is_bound(model, slot: int) -> bool:
+    bound = getattr(model, "_bound", None)
+    return slot in bound if isinstance(bound, dict) else bound is not None
+
+
+class ControlNetHint(_Extendable):
     """One hint image bound to its ControlNet.  ``run`` is called once per UNet evaluation by schedulers.UNetWithControlnet with the
     CFG side of the calling stack: "g" (guided), "u" (unconditional) or "f" (one call over cat[unconditional, guided])."""
 
@@ -111,12 +160,16 @@ class ControlNetHint:
             mask = normalise_tensor(mask, 1)
             if mask.mean() == 1.0 and mask.std() == 0.0:              # pure ones: the reference discards it
                 mask = None
-        if mask is not None:
-            raise NotImplementedError("masked ControlNet hints (the reference resizes the mask with an unpinned lanczos3)")
+        if mask is not None and not has_bind_slots(model):
+            raise NotImplementedError("masked ControlNet hints need a control model that takes residual masks (bind(..., masks=))")
         self.model, self.image = model, normalise_tensor(image, model.config.get("conditioning_channels", 3))
+        self.mask = mask
         self.weight, self.soft_injection, self.cfg_only = weight, soft_injection, cfg_only
-        self._token = object()                                        # who bound the model last: (token, side)
+        self._token = object()                                        # who bound a slot of the model last: (token, side, ...)
         self._ctx = {}                                                # side -> (the stack's context, the context the model sees)
+        self._slots = {}                                              # side -> bind slot of the model (reserve); 0 where not reserved
+        self._pyramid = None                                          # the mask at every residual's resolution, built at the first bind
+        self._inpaint = {}                                            # side -> what a 9-channel leaf binds (_inpaint_state)
 
     def scales(self):
         """weight x logspace(-1, 0, N + 1)[k] for down residual k and the last point for the mid residual; the weight alone without
@@ -128,35 +181,107 @@ class ControlNetHint:
 
     def to(self, device=None, dtype=None):
         self.image = self.image.to(device, dtype)
+        if self.mask is not None:
+            self.mask = self.mask.to(device, dtype)
+        self._pyramid, self._inpaint = None, {}
         return self
 
-    def _bind(self, side, ctx):
-        """The embedding of the image and the projected context live in the model, one request at a time: bind again only when
-        another hint, another side (sequential CFG alternates two contexts on one model) or another request used it last."""
+    def sides(self, cfg: bool, sequential: bool):
+        """the CFG sides this hint runs on in a request"""
+        if not cfg:
+            return ("g",)
+        if not sequential:
+            return ("f",)
+        return ("g",) if self.cfg_only else ("g", "u")
+
+    def reserve(self, plan: dict, sides: Sequence[str]) -> None:
+        """Take one bind slot of the model per side, from ``plan`` ({id(model): slots taken so far}, one plan per request)."""
+        limit = getattr(self.model, "SLOTS", 4)
+        for side in sides:
+            n = plan.get(id(self.model), 0)
+            if n >= limit:
+                raise NotImplementedError(f"more than {limit} binds on one control model (GYRE_CTRL_SLOTS = {limit}: one per hint, leaf of "
+                                          "the hires-fix / graft tree and sequential CFG side)")
+            plan[id(self.model)] = n + 1
+            self._slots[side] = n
+
+    def mask_pyramid(self, mask: Tensor) -> List[Tensor]:
+        """``mask`` (image resolution) at the resolution of each of the N + 1 residuals"""
+        H, W = self.image.shape[-2:]
+        return [resized_mask((rh, rw), mask) for _, rh, rw in self.model.residual_shapes(H // 8, W // 8)]
+
+    def _inpaint_state(self, side, extra: Tensor, batch: int):
+        """What a 9-channel inpaint leaf binds and runs with (unified_pipeline.py:1016-1024): the latent mask the control model's latents
+        are multiplied by, the hint image times that mask at image resolution (times the hint's own mask) and the residual masks made
+        from the combined mask.  The mask channel is constant over a request: computed once per side, keyed on the identity of the leaf's
+        extra-channels tensor."""
+        kept = self._inpaint.get(side)
+        if kept is None or kept[0] is not extra or kept[1] != batch:
+            m = extra[:, [0]].to(self.image.device, torch.float32)
+            if m.shape[0] != batch:
+                m = m.repeat(batch // m.shape[0], 1, 1, 1)
+            combined = resized_mask(self.image.shape, m).to(self.image.dtype)
+            if self.mask is not None:
+                combined = combined * self.mask
+            kept = self._inpaint[side] = (extra, batch, m.contiguous(), (self.image * combined).contiguous(), self.mask_pyramid(combined))
+        return kept[2:]
+
+    def _bind(self, side, ctx, image=None, masks=None):
+        """The embedding of the image and the projected context live in a bind slot of the model, one request at a time: bind again
+        only when another hint, another side (without reserved slots sequential CFG alternates two contexts on slot 0) or another
+        request used the slot last."""
         kept = self._ctx.get(side)
         if kept is None or kept[0] is not ctx:
             seen = ctx.chunk(2)[-1].contiguous() if (self.cfg_only and side == "f") else ctx
             kept = self._ctx[side] = (ctx, seen)
-        owner = getattr(self.model, "_bind_owner", None)
-        if owner is None or owner[0] is not self._token or owner[1] != side or owner[2] is not kept[1] or self.model._bound is None:
-            self.model.bind(self.image, kept[1])
-            self.model._bind_owner = (self._token, side, kept[1])
+        if image is None:
+            image = self.image
+            if self.mask is not None:
+                if self._pyramid is None:
+                    self._pyramid = self.mask_pyramid(self.mask)
+                masks = self._pyramid
+        slot = 0 if REBIND_EVERY_CALL else self._slots.get(side, 0)
+        owners = self.model.__dict__.setdefault("_bind_owners", {})
+        owner = owners.get(slot)
+        if (REBIND_EVERY_CALL or owner is None or owner[0] is not self._token or owner[1] != side or owner[2] is not kept[1]
+                or owner[3] is not image or not _is_bound(self.model, slot)):
+            kw = {}
+            if slot:
+                kw["slot"] = slot
+            if masks is not None:
+                kw["masks"] = masks
+            self.model.bind(image, kept[1], **kw)
+            owners[slot] = (self._token, side, kept[1], image)
+        return slot
 
-    def run(self, side: str, latents: Tensor, t, encoder_hidden_states: Tensor, out, accumulate: bool):
+    def run(self, side: str, latents: Tensor, t, encoder_hidden_states: Tensor, out, accumulate: bool, extra: Optional[Tensor] = None):
         """Adds (accumulate) or assigns this hint's residuals for one UNet call into ``out`` (N + 1 NCHW buffers at the batch of
-        ``latents``).  False when the hint contributes nothing on this side (cfg_only on "u")."""
-        if latents.shape[1] == 9:
-            raise NotImplementedError("ControlNet hints with a 9-channel inpaint UNet (the reference resizes its mask with an unpinned lanczos)")
+        ``latents``).  False when the hint contributes nothing on this side (cfg_only on "u").  extra: the extra channels of a
+        9-channel inpaint leaf (mask, masked-image latents), the tensor the leaf keeps for the whole request."""
         x, B = latents[:, 0:4], latents.shape[0]
         if self.cfg_only and side == "u":
             return False
-        self._bind(side, encoder_hidden_states)
-        if self.cfg_only and side == "f":                             # the guided half only, into the upper half; the lower half is zero
+        half = self.cfg_only and side == "f"                          # the guided half only, into the upper half; the lower half is zero
+        if half:
             x = x.chunk(2)[-1]
             t = t.chunk(2)[-1] if isinstance(t, torch.Tensor) and t.ndim > 0 and t.numel() > 1 else t
-            self.model(x, t, scales=self.scales(), out=out, accumulate=accumulate, out_batch=B, out_offset=B - x.shape[0])
+        kw = {}
+        if latents.shape[1] == 9:
+            if not has_bind_slots(self.model):
+                raise NotImplementedError("ControlNet hints with a 9-channel inpaint UNet need a control model that takes a latent mask "
+                                          "(forward(..., x_mask=))")
+            if extra is None:
+                raise ValueError("a ControlNet hint next to a 9-channel inpaint UNet needs the leaf's extra channels (extra=...)")
+            x_mask, image, masks = self._inpaint_state(side, extra, x.shape[0])
+            slot = self._bind(side, encoder_hidden_states, image, masks)
+            kw["x_mask"] = x_mask
         else:
-            self.model(x, t, scales=self.scales(), out=out, accumulate=accumulate)
+            slot = self._bind(side, encoder_hidden_states)
+        if slot:
+            kw["slot"] = slot
+        if half:
+            kw.update(out_batch=B, out_offset=B - x.shape[0])
+        self.model(x, t, scales=self.scales(), out=out, accumulate=accumulate, **kw)
         return True
 
 
@@ -198,7 +323,7 @@ class CoAdapterHint(T2IHint):
         return getattr(self.model, "_coadapter_type", False)
 
 
-class StyleHint:
+class StyleHint(_Extendable):
     """One style image bound to its style adapter, the host CLIP model and its feature extractor.  Calling it returns the weighted
     style tokens [N, num_token, context_dim].  With a model loaded as a co-adapter it needs the ``fuser`` as well."""
 
@@ -214,7 +339,7 @@ class StyleHint:
         if image.ndim == 3:
             image = image[None]
         self.model, self.image = model, normalise_tensor(image, 3)          # (an alpha plane would be the ignored mask)
-        self.weight, self.soft_injection, self.cfg_only = weight, False, cfg_only
+        self.weight, self.soft_injection, self.cfg_only, self.mask = weight, False, cfg_only, None
         self.clip_model, self.feature_extractor, self.fuser, self.clip_layer = clip_model, feature_extractor, fuser, clip_layer
         if self.coadapter_type() and fuser is None:
             raise ValueError("T2i Coadapter model needs a fuser model")

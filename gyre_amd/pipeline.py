@@ -266,12 +266,12 @@ class GyrePipeline:
         """UNet stack of one leaf: embeddings (+ T2I-adapter states) -> extra channels -> CFG (unified_pipeline.py:2235-2337,
         2408-2430).  t2i_states: combine_t2i_states' {"g", "u", "f"} at batch B / B / 2B (reference UNetWithT2I, unet/core.py:96-218:
         "g" to the conditional side, "u" to the unconditional one, "f" to the CFG-parallel call).  controlnet_hints: the request's
-        hints.ControlNetHint objects; each side gets its own UNetWithControlnet (and residual buffers) between the embeddings and the
+        hints.ControlNetHint objects of this leaf; each side gets its own UNetWithControlnet (and residual buffers) between the embeddings and the
         UNet, told which side it is (the reference's cfg_meta)."""
         st = t2i_states or {}
 
         def bind(emb, added=None, states=None, side=None):
-            unet = S.UNetWithControlnet(leaf.unet, controlnet_hints, side) if (controlnet_hints and side) else leaf.unet
+            unet = S.UNetWithControlnet(leaf.unet, controlnet_hints, side, extra=leaf.extra) if (controlnet_hints and side) else leaf.unet
             u = S.UNetWithEmbeddings(unet, emb, added) if states is None else S.UNetWithEmbeddings(unet, emb, added, states)
             return S.UnetWithExtraChannels(u, leaf.extra) if leaf.extra is not None else u
 
@@ -345,17 +345,24 @@ class GyrePipeline:
         they are refused (NotImplementedError) before any device work.
         controlnet_hints: gyre_amd.hints.ControlNetHint objects (hint image bound to its native ControlNet).  Each model runs once per
         UNet evaluation on the latents, the timestep and the text context of that evaluation; the hint image and the context are bound
-        once per request.  Refused (NotImplementedError) together with a mask, a 9-channel inpaint UNet, hires fix, a grafted inpaint
-        pair or CLIP guidance."""
+        once per request.  Under hires fix the natural-size leaf gets hint.extend(image=image_to_natural(image), mask=...) and the
+        full-size leaf hint.extend(soft_injection=True) (unified_pipeline.py:2148-2168); every leaf of a hires-fix / graft tree has
+        its own copy of each hint on its own bind slot of the control model (more binds on one model than it has slots:
+        NotImplementedError).  Next to a 9-channel inpaint UNet the control model sees latents x mask channel and the hint image x that
+        mask (:1016-1024).  Refused (NotImplementedError) together with CLIP guidance; a control-model shell without bind slots
+        (hints.has_bind_slots) is refused with a mask, a 9-channel UNet, hires fix and a grafted pair as well."""
         if controlnet_hints:
             if clip_guidance_scale and self.clip_model is not None and self.feature_extractor is not None:
                 raise NotImplementedError("ControlNet hints together with CLIP guidance (no input gradients through the control model)")
-            if mask_image is not None:
-                why = "grafted inpaint" if (self.inpaint_unet is not None and self.inpaint_unet is not self.unet and self.grafted_inpaint) \
-                    else "a mask (the reference resizes it for the hint with an unpinned lanczos)"
-                raise NotImplementedError(f"ControlNet hints together with {why}")
-            if self.unet.config.in_channels == 9:
-                raise NotImplementedError("ControlNet hints with a 9-channel inpaint UNet (the reference resizes its mask with an unpinned lanczos)")
+            from .hints import has_bind_slots
+            if not all(has_bind_slots(h.model) for h in controlnet_hints):
+                # a control-model shell without bind slots, residual masks and a latent mask: one bind, one leaf, no inpaint engine
+                if mask_image is not None:
+                    why = "grafted inpaint" if (self.inpaint_unet is not None and self.inpaint_unet is not self.unet and self.grafted_inpaint) \
+                        else "a mask"
+                    raise NotImplementedError(f"ControlNet hints together with {why} need a control model with bind slots")
+                if self.unet.config.in_channels == 9:
+                    raise NotImplementedError("ControlNet hints with a 9-channel inpaint UNet need a control model that takes a latent mask")
         if t2i_hints:
             if clip_guidance_scale and self.clip_model is not None and self.feature_extractor is not None:
                 raise NotImplementedError("T2I hints together with CLIP guidance (no input gradients through adapter states)")
@@ -474,7 +481,9 @@ class GyrePipeline:
         if use_hires and t2i_hints:
             raise NotImplementedError("T2I hints together with hires fix (the natural-size leaf needs its own resized hint states)")
         if use_hires and controlnet_hints:
-            raise NotImplementedError("ControlNet hints together with hires fix (the natural-size leaf needs its own resized hint image)")
+            from .hints import has_bind_slots
+            if not all(has_bind_slots(h.model) for h in controlnet_hints):
+                raise NotImplementedError("ControlNet hints together with hires fix need a control model with bind slots (one per leaf)")
         if use_hires and not is_k:
             raise ValueError("Can't use Diffuser schedulers with Hires fix. "
                              "Either use a K-Diffusion scheduler or disable Hires fix.")
@@ -483,8 +492,9 @@ class GyrePipeline:
                                                                          hires_oos_fraction)
             nat_image, nat_mask = to_nat(image), to_nat(mask_image)
             natural = self._map_leaves(tree, lambda l: self._Leaf(**{**l.__dict__, "height": natural_px, "width": natural_px,
-                                                                     "image": nat_image, "mask_image": nat_mask}))
-            tree = (natural, tree, H.HiresUnetWrapper,
+                                                                     "image": nat_image, "mask_image": nat_mask, "hires": "natural"}))
+            full = self._map_leaves(tree, lambda l: self._Leaf(**{**l.__dict__, "hires": "full"}))
+            tree = (natural, full, H.HiresUnetWrapper,
                     {"natural_size": [sample_size, sample_size], "oos_fraction": hires_oos_fraction})
         leaves = self._leaves(tree)
         if not is_k and len(leaves) > 1 and use_hires:
@@ -525,6 +535,27 @@ class GyrePipeline:
                 h.to(dev)
                 if h.image.shape[0] not in (1, B) or h.image.shape[-2:] != (height, width):
                     raise ValueError(f"a ControlNet hint image must be [1 or {B}, C, {height}, {width}], got {tuple(h.image.shape)}")
+            if len(leaves) == 1:
+                leaves[0].controlnet_hints = list(controlnet_hints)
+            else:
+                # The leaves of a hires-fix / graft tree alternate on the same control models every step: each leaf gets its own copy
+                # of every hint (ModeTreeRoot.wrap, unified_pipeline.py:1080-1097 with the callbacks of :2148-2168) and each copy its
+                # own bind slots, so that no leaf embeds its hint image or projects its context more than once per request.
+                plan = {}
+                for leaf in leaves:
+                    how = getattr(leaf, "hires", None)
+                    copies = []
+                    for h in controlnet_hints:
+                        if how == "natural":
+                            c = h.extend(image=to_nat(h.image), mask=to_nat(h.mask) if h.mask is not None else None)
+                        elif how == "full":
+                            c = h.extend(soft_injection=True)
+                        else:
+                            c = h.extend()
+                        c.to(dev)
+                        c.reserve(plan, c.sides(do_cfg, cfg_execution == "sequential"))
+                        copies.append(c)
+                    leaf.controlnet_hints = copies
         shared = {}
         for leaf in leaves:
             clip_mode = None
@@ -539,7 +570,7 @@ class GyrePipeline:
             self._bind_leaf(leaf, text_embeddings=text_embeddings, uncond_embeddings=uncond_embeddings,
                             guidance_scale=guidance_scale, cfg_execution=cfg_execution, B=B, added_cond=added_cond,
                             uncond_added_cond=uncond_added_cond, cfg_embeddings=shared, clip_mode=clip_mode, t2i_states=t2i_states,
-                            controlnet_hints=controlnet_hints)
+                            controlnet_hints=getattr(leaf, "controlnet_hints", None))
         sched.set_eps_unets([l.eps_unet for l in leaves])
         sched.set_timesteps(num_inference_steps, strength=strength if image is not None else None,
                             config=S.SchedulerConfig(eta=eta, karras_rho=karras_rho, churn=churn, churn_tmin=churn_tmin,

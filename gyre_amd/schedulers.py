@@ -178,10 +178,12 @@ class UNetWithControlnet:
     """Runs the ControlNet hints of a request before every UNet call and hands their summed residuals on (reference
     unet/core.py:40-64).  It sits inside UNetWithEmbeddings, so it sees encoder_hidden_states; ``side`` is the CFG side of the stack
     ("g", "u" or "f" - the reference's cfg_meta).  Every hint writes into the same N + 1 buffers, allocated at the first call and
-    reused by every step: the first hint that contributes assigns, the later ones accumulate (hints.ControlNetHint.run)."""
+    reused by every step: the first hint that contributes assigns, the later ones accumulate (hints.ControlNetHint.run).  ``extra``:
+    the extra channels of a 9-channel inpaint leaf (UnetWithExtraChannels sits outside and concatenates them every step); the hints
+    key what they derive from the mask channel on this one tensor."""
 
-    def __init__(self, unet, hints, side: str):
-        self.unet, self.hints, self.side = unet, list(hints), side
+    def __init__(self, unet, hints, side: str, extra: Optional[Tensor] = None):
+        self.unet, self.hints, self.side, self.extra = unet, list(hints), side, extra
         self._bufs = None
 
     @property
@@ -196,7 +198,10 @@ class UNetWithControlnet:
             self._bufs = (key, self.hints[0].model.new_outputs(B, H, W, latents.device))
         bufs, wrote = self._bufs[1], False
         for hint in self.hints:
-            wrote = hint.run(self.side, latents, t, ctx, bufs, wrote) or wrote
+            if self.extra is not None and latents.shape[1] == 9:
+                wrote = hint.run(self.side, latents, t, ctx, bufs, wrote, extra=self.extra) or wrote
+            else:
+                wrote = hint.run(self.side, latents, t, ctx, bufs, wrote) or wrote
         if not wrote:                                                  # only cfg_only hints, on the unconditional side
             return self.unet(latents, t, **kwargs)
         return self.unet(latents, t, **kwargs, down_block_additional_residuals=bufs[:-1], mid_block_additional_residual=bufs[-1])

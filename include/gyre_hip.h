@@ -638,7 +638,22 @@ int gyre_hed_geometry(int n, int32_t* sizes, int32_t* offsets);
  *     [out_b0, out_b0 + B) of outs[k] [out_B, C_k, H_k, W_k] NCHW of out_dtype: accumulate == 0 assigns and writes every other
  *     sample of outs[k] as zero (the unconditional half of a cfg_only hint), accumulate == 1 adds (one fp32 add, one rounding) and
  *     leaves the other samples alone (the sum over several control models).
- * forward before bind, a batch other than the bound one, and an H x W other than the bound image's size / 8: GYRE_ERR_INVALID. */
+ * forward before bind, a batch other than the bound one, and an H x W other than the bound image's size / 8: GYRE_ERR_INVALID.
+ *
+ * Bind slots.  The handle keeps GYRE_CTRL_SLOTS independent binds: the leaves of a hires-fix / graft tree alternate on one control
+ * model every step, each with its own hint image, context and size, and re-embedding the image per call would cost more than the
+ * step.  gyre_ctrl_bind / gyre_ctrl_forward are slot 0, unmasked, and behave exactly as before.  A slot owns its conditioning
+ * embedding, its projected K / V, its geometry (batch, image H x W, S) and, optionally, its residual masks: res_masks[k] (k < n_masks
+ * == N + 1, device pointers) is fp32 [mask_B, 1, h_k, w_k] with mask_B == 1 or B and mask_hw[2k], mask_hw[2k + 1] == the size of
+ * residual k; they are copied into buffers the handle owns during the bind.  res_masks == NULL or all entries NULL: unmasked.  With
+ * masks residual k is  rnd(fl(fl(scales[k] r) m) [+ old])  - fp32 products, the accumulate add, one rounding to out_dtype; m == 0 gives
+ * +-0 for a finite r, NaN stays NaN.
+ * gyre_ctrl_forward_slot takes, optionally, x_mask fp32 [x_mask_B, 1, H, W] (x_mask_B == 1 or B; NULL: none): the entry pass
+ * multiplies x[b, c, p] by x_mask[b or 0, 0, p] in fp32 from the source dtype with one rounding to storage (next to a 9-channel inpaint
+ * UNet the reference feeds the control model latents[:, 0:4] * latents[:, [4]]).
+ * gyre_ctrl_set_weight drops every slot.  GYRE_ERR_INVALID: forward on an unbound slot, a slot outside [0, GYRE_CTRL_SLOTS), a
+ * geometry other than the slot's, masks that are partly NULL, and a mask whose size is not its residual's. */
+#define GYRE_CTRL_SLOTS 4
 int gyre_ctrl_create(const gyre_ctrl_cfg* cfg, int device, gyre_ctrl** out);
 void gyre_ctrl_destroy(gyre_ctrl* h);
 int gyre_ctrl_num_params(const gyre_ctrl* h);
@@ -652,6 +667,13 @@ size_t gyre_ctrl_workspace_bytes(gyre_ctrl* h, int B, int H, int W, int S);
 int gyre_ctrl_forward(gyre_ctrl* h, void* stream, const void* x_nchw, int x_dtype, const int64_t* t, int B, int H, int W,
                       void* workspace, size_t workspace_bytes, const float* scales, int accumulate, int out_B, int out_b0,
                       void* const* outs_nchw, int n_outs, int out_dtype);
+size_t gyre_ctrl_bind_slot_workspace_bytes(gyre_ctrl* h, int slot, int image_B, int image_H, int image_W, int B);
+int gyre_ctrl_bind_slot(gyre_ctrl* h, void* stream, int slot, const void* image_nchw, int image_dtype, int image_B, int image_H,
+                        int image_W, const void* context, int ctx_dtype, int B, int S, const float* const* res_masks,
+                        const int32_t* mask_hw, int n_masks, int mask_B, void* workspace, size_t workspace_bytes);
+int gyre_ctrl_forward_slot(gyre_ctrl* h, void* stream, int slot, const void* x_nchw, int x_dtype, const float* x_mask, int x_mask_B,
+                           const int64_t* t, int B, int H, int W, void* workspace, size_t workspace_bytes, const float* scales,
+                           int accumulate, int out_B, int out_b0, void* const* outs_nchw, int n_outs, int out_dtype);
 
 /* ---- per-launch timing with HIP events on the launch stream (bench.py roofline leg) ----
  * mask: bit k enables kernel class k (names from gyre_prof_class_name; they equal the prefix of the
@@ -1019,6 +1041,13 @@ int gyre_op_relu(void* stream, void* x, size_t n);
 int gyre_op_silu(void* stream, void* x, size_t n);
 int gyre_op_ctrl_emit(void* stream, const void* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
                       int out_dtype, int out_B, int out_b0);
+/* The masked forms behind gyre_ctrl_bind_slot / gyre_ctrl_forward_slot, mask fp32 [mask_B][HW] with mask_B == 1 or B.
+ * ctrl_emit_masked: out = rnd(fl(fl(scale f) mask[b or 0][p]) [+ old]).  nchw_to_nhwc_masked: y NHWC storage [B][HW][Cpad] =
+ * rnd(x[b][c][p] mask[b or 0][p]) from x NCHW of a runtime dtype, pad channels zero. */
+int gyre_op_ctrl_emit_masked(void* stream, const void* f, int B, int C, int HW, int Cpad, float scale, int accumulate, void* out,
+                             int out_dtype, int out_B, int out_b0, const float* mask, int mask_B);
+int gyre_op_nchw_to_nhwc_masked(void* stream, const void* x, int dtype, int B, int C, int HW, int Cpad, const float* mask, int mask_B,
+                                void* y);
 /* The kernels of the RRDBNet upscaler (kernels_rdb.hip).  rdb_tile: the output tile (pixels) of the dense-block convolution.
  * rdb_conv: one launch of it; GYRE_ERR_UNSUPPORTED outside its domain (NT other than 32 / 64, Cin % 32, strides or c0 not multiples of
  * 8, unaligned buffers, grid limits) and GYRE_ERR_INVALID for bad arguments, nothing written either way.  rdb_epilogue: the same
