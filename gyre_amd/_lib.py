@@ -118,6 +118,17 @@ class HedCfg(C.Structure):
     _fields_ = [("reserved", C.c_int32)]
 
 
+class MlsdCfg(C.Structure):
+    """gyre_mlsd_cfg (include/gyre_hip.h): the network has no constructor arguments."""
+    _fields_ = [("reserved", C.c_int32)]
+
+
+class MlsdFoldArgs(C.Structure):
+    """gyre_mlsd_fold_args (include/gyre_hip.h): one launch of the BatchNorm fold, for tests."""
+    _fields_ = [(n, C.c_void_p) for n in ("w", "conv_bias", "gamma", "beta", "mean", "var", "out", "bias")] + \
+               [(n, C.c_int32) for n in ("kind", "O", "I", "taps", "o_pad", "i_pad")]
+
+
 class HedFuseArgs(C.Structure):
     """gyre_hed_fuse_args (include/gyre_hip.h): one launch of the HED fuse kernel, for tests."""
     _fields_ = [("so", C.c_void_p * 5)] + [(n, C.c_int32 * 5) for n in ("Hk", "Wk", "oy", "ox")] + \
@@ -358,14 +369,23 @@ _SIGS = {
     "gyre_op_hed_entry": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "gyre_op_hed_tail": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gyre_op_hed_fuse": (_i, [_vp, C.POINTER(HedFuseArgs)]),
+    "gyre_op_mlsd_fold": (_i, [_vp, C.POINTER(MlsdFoldArgs)]),
+    "gyre_op_mlsd_entry": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gyre_op_dwconv3": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "gyre_op_upsample2_ac": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
+    "gyre_op_dconv3_d5": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gyre_op_mlsd_act": (_i, [_vp, _vp, _sz, _i, _i, _i]),
+    "gyre_op_mlsd_relu_add": (_i, [_vp, _vp, _vp, _sz]),
+    "gyre_op_mlsd_exit": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "gyre_op_seq_attn_max_len": (_i, [_i]),
     "gyre_op_seq_attn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
     "gyre_op_quick_gelu": (_i, [_vp, _vp, _sz]),
     "gyre_op_fuser_pool": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i]),
     "gyre_op_fuser_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _vp, _i]),
 }
-# the handle surface of the three upscaler families and of the two hinters: image in, image out
-for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg), ("hed", HedCfg)):
+# the handle surface of the three upscaler families and of the three hinters: image in, image out
+for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg), ("hed", HedCfg),
+                    ("mlsd", MlsdCfg)):
     _SIGS.update({f"gyre_{_kind}_create": (_i, [C.POINTER(_cfg), _i, C.POINTER(_vp)]),
                   f"gyre_{_kind}_destroy": (None, [_vp]),
                   f"gyre_{_kind}_num_params": (_i, [_vp]),

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgyre_hip.so")
 LIB_F16 = os.path.join(HERE, "libgyre_hip_f16.so")
-SOURCES = ["kernels_elem.hip", "kernels_gemm.hip", "kernels_gemm4s.hip", "kernels_gemm_ar.hip", "kernels_gemm_sm.hip", "kernels_conv_out.hip", "kernels_attn.hip", "kernels_xattn.hip", "kernels_tome.hip", "kernels_bwd.hip", "kernels_t2i.hip", "kernels_ctrl.hip", "kernels_lyco.hip", "kernels_rdb.hip", "kernels_swin.hip", "kernels_hat.hip", "kernels_inorm.hip", "kernels_hed.hip", "kernels_seq.hip", "model.hip", "model_vjp.hip", "model_t2i.hip", "model_ctrl.hip", "model_rrdb.hip", "model_swinir.hip", "model_hat.hip", "model_lineart.hip", "model_hed.hip", "model_t2i_seq.hip"]
+SOURCES = ["kernels_elem.hip", "kernels_gemm.hip", "kernels_gemm4s.hip", "kernels_gemm_ar.hip", "kernels_gemm_sm.hip", "kernels_conv_out.hip", "kernels_attn.hip", "kernels_xattn.hip", "kernels_tome.hip", "kernels_bwd.hip", "kernels_t2i.hip", "kernels_ctrl.hip", "kernels_lyco.hip", "kernels_rdb.hip", "kernels_swin.hip", "kernels_hat.hip", "kernels_inorm.hip", "kernels_hed.hip", "kernels_mlsd.hip", "kernels_seq.hip", "model.hip", "model_vjp.hip", "model_t2i.hip", "model_ctrl.hip", "model_rrdb.hip", "model_swinir.hip", "model_hat.hip", "model_lineart.hip", "model_hed.hip", "model_mlsd.hip", "model_t2i_seq.hip"]
 HEADERS = ["common.h", "kernels.h", "gemm_shared.h", "model_impl.h", "model_upscaler.h", os.path.join("..", "..", "include", "gyre_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5",
          "-Wno-unused-result", "-fno-gpu-rdc",

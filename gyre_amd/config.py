@@ -290,6 +290,28 @@ def hed_config(**kw) -> HedConfig:
     return HedConfig(input_nc=3)
 
 
+class MlsdConfig(_AttrDict):
+    """Configuration of the MLSD line detector: the reference's ``MobileV2_MLSD_Large`` (gyre/pipeline/hinters/models/
+    mbv2_mlsd_large.py) takes no constructor arguments, so the mapping holds the one fact its shell asks for - the four input channels
+    (RGB and a constant plane)."""
+
+
+def mlsd_config(**kw) -> MlsdConfig:
+    if kw:
+        raise NotImplementedError(f"MobileV2_MLSD_Large: {sorted(kw)} are not arguments of its constructor, which has none "
+                                  f"(a configuration of another model family?)")
+    return MlsdConfig(input_nc=4)
+
+
+# the MobileNetV2 trunk of MLSD, cut after features[13]: (t, c, n, s) = expansion, width, repeats, stride of the first repeat
+MLSD_SETTING = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1))
+
+
+def mlsd_size_ok(n: int) -> bool:
+    """the image sides the network takes: those at which the reference's own concatenations line up"""
+    return n >= 16 and (n // 2) % 8 == 0
+
+
 # the VGG trunk of HED: convolutions per stage and their width
 HED_STAGES = ((2, 64), (2, 128), (3, 256), (3, 512), (3, 512))
 HED_BORDER = 34                    # conv1_1's padding 35, less the ordinary 1

@@ -303,6 +303,37 @@ struct HedFuse {
 int hed_fuse_check(const HedFuse& a);                    // the launch's argument checks alone (no device call)
 int launch_hed_fuse(hipStream_t st, const HedFuse& a);
 
+// ---- MLSD line-detector kernels (kernels_mlsd.hip) ----------------------------------
+// BatchNorm (eval, eps 1e-5) folded into a convolution in fp32: out = storage(w gamma / sqrt(var + eps)), bias = beta + (conv_bias - mean)
+// gamma / sqrt(var + eps).  w: the PyTorch weight [O][I][k][k] as fp32 (depthwise: [O][1][3][3]); conv_bias may be null.  Destination:
+//   DENSE      [o_pad][taps][i_pad], taps 1 or 9 (the planner's order), zero in the padding
+//   DEPTHWISE  [9][o_pad]
+//   ENTRY      [9][I][o_pad]
+// bias [o_pad] fp32, zero in the padding
+enum { MLSD_FOLD_DENSE = 0, MLSD_FOLD_DEPTHWISE = 1, MLSD_FOLD_ENTRY = 2 };
+struct MlsdFold {
+    const float *w = nullptr, *conv_bias = nullptr, *gamma = nullptr, *beta = nullptr, *mean = nullptr, *var = nullptr;
+    bf16_t* out = nullptr; float* bias = nullptr;
+    int kind = 0, O = 0, I = 0, taps = 1, o_pad = 0, i_pad = 0;
+};
+int launch_mlsd_fold(hipStream_t st, const MlsdFold& a);
+// y [B][H / 2][W / 2][32] = relu6(conv3x3 stride 2 (x NCHW [B][4][H][W] of dtype) + bias), zero padding on the right / bottom only;
+// w [9][4][32] storage
+int launch_mlsd_entry(hipStream_t st, const void* x, int dtype, int B, int H, int W, const bf16_t* w, const float* bias, bf16_t* y);
+// y = relu6(depthwise3x3(x) + bias) over NHWC [B][H][W][C], C % 8 == 0, w [9][C] storage, bias [C]: stride 1 / zero padding 1 ->
+// [B][H][W][C], stride 2 / right-bottom padding -> [B][H / 2][W / 2][C].  relu6_in: relu6 is applied to x as it is read
+int launch_mlsd_dw(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, const bf16_t* w, const float* bias, int stride, int relu6_in,
+                   bf16_t* y);
+// y[b][oy][ox][0 .. C) (pixel stride ldy) = bilinear x2, align_corners=True, of x [B][H][W] (pixel stride ldx); relu_in: relu on the reads
+int launch_mlsd_up2(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, int ldx, int relu_in, bf16_t* y, int ldy);
+// y = relu(conv3x3 dilation 5 / zero padding 5 (x) + bias), NHWC [B][H][W][64] -> the same, w [64][9][64] storage
+int launch_mlsd_dconv(hipStream_t st, const bf16_t* x, int B, int H, int W, const bf16_t* w, const float* bias, bf16_t* y);
+// in place: relu (relu6) over the first C channels of `rows` rows of pitch ld; y = relu(y) + x over n contiguous elements
+int launch_mlsd_act(hipStream_t st, bf16_t* x, size_t rows, int C, int ld, int relu6);
+int launch_mlsd_relu_add(hipStream_t st, bf16_t* y, const bf16_t* x, size_t n);
+// out NCHW [B][9][H][W] of out_dtype = channels 7 .. 15 of x NHWC [B][H][W][16]
+int launch_mlsd_exit(hipStream_t st, const bf16_t* x, int B, int H, int W, void* out, int out_dtype);
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

@@ -403,6 +403,58 @@ def hed_param_shapes(cfg=None) -> Shapes:
     return s
 
 
+MLSD_BUFFERS = ("running_mean", "running_var", "num_batches_tracked")
+
+
+def mlsd_is_buffer(key: str) -> bool:
+    return key.endswith(MLSD_BUFFERS)
+
+
+def mlsd_param_shapes(cfg=None) -> Shapes:
+    """State-dict keys and shapes of the reference's ``MobileV2_MLSD_Large`` (gyre/pipeline/hinters/models/mbv2_mlsd_large.py) in
+    state_dict() order, 362 entries: the bias-free backbone convolutions, the biased decoder convolutions, and per BatchNorm its weight,
+    bias, running_mean, running_var and the scalar num_batches_tracked (accepted by a strict load, never uploaded).  The network has no
+    configuration (cfg is accepted and ignored, for the shells that pass theirs)."""
+    from .config import MLSD_SETTING
+    s: Shapes = OrderedDict()
+
+    def bn(p, c):
+        s[p + ".weight"] = (c,)
+        s[p + ".bias"] = (c,)
+        s[p + ".running_mean"] = (c,)
+        s[p + ".running_var"] = (c,)
+        s[p + ".num_batches_tracked"] = ()
+
+    def conv_bn(conv, norm, o, i, k, bias):
+        s[conv + ".weight"] = (o, i, k, k)
+        if bias:
+            s[conv + ".bias"] = (o,)
+        bn(norm, o)
+
+    conv_bn("backbone.features.0.0", "backbone.features.0.1", 32, 4, 3, False)
+    cin, f = 32, 1
+    for t, c, n, _ in MLSD_SETTING:
+        for _ in range(n):
+            p, hid, j = f"backbone.features.{f}.conv", t * cin, 0
+            if t != 1:
+                conv_bn(f"{p}.0.0", f"{p}.0.1", hid, cin, 1, False)
+                j = 1
+            conv_bn(f"{p}.{j}.0", f"{p}.{j}.1", hid, 1, 3, False)          # depthwise
+            conv_bn(f"{p}.{j + 1}", f"{p}.{j + 2}", c, hid, 1, False)
+            cin, f = c, f + 1
+    for k, (in_c1, in_c2) in enumerate(((64, 96), (32, 64), (24, 64), (16, 64))):
+        a, b = f"block{15 + 2 * k}", f"block{16 + 2 * k}"
+        conv_bn(a + ".conv1.0", a + ".conv1.1", 64, in_c2, 1, True)
+        conv_bn(a + ".conv2.0", a + ".conv2.1", 64, in_c1, 1, True)
+        conv_bn(b + ".conv1.0", b + ".conv1.1", 128, 128, 3, True)
+        conv_bn(b + ".conv2.0", b + ".conv2.1", 64, 128, 3, True)
+    conv_bn("block23.conv1.0", "block23.conv1.1", 64, 64, 3, True)
+    conv_bn("block23.conv2.0", "block23.conv2.1", 64, 64, 3, True)
+    s["block23.conv3.weight"] = (16, 64, 1, 1)
+    s["block23.conv3.bias"] = (16,)
+    return s
+
+
 class _WindowShapes:
     """The entries the SwinIR and HAT state dicts are made of, appended to ``s`` in call order: cfg gives the width and the MLP ratio."""
 

@@ -250,8 +250,25 @@ typedef struct {
     int32_t B, H, W;
 } gyre_hed_fuse_args;
 
+/* MLSD line detector (the reference's gyre/pipeline/hinters/models/mbv2_mlsd_large.py, MobileV2_MLSD_Large).  The network has no
+ * constructor arguments. */
+typedef struct {
+    int32_t reserved;                /* 0 */
+} gyre_mlsd_cfg;
+
+/* One launch of the BatchNorm fold (kernels_mlsd.hip), for tests: out = storage(w gamma / sqrt(var + 1e-5)), bias = beta + (conv_bias -
+ * mean) gamma / sqrt(var + 1e-5) in fp32.  w: the PyTorch weight [O][I][k][k] as fp32 (kind 1, depthwise: [O][1][3][3]); conv_bias may
+ * be null.  kind 0: out [o_pad][taps][i_pad], taps 1 or 9; kind 1: out [9][o_pad]; kind 2 (the entry convolution): out [9][I][o_pad].
+ * bias [o_pad]; padding entries are zero. */
+typedef struct {
+    const float* w; const float* conv_bias; const float* gamma; const float* beta; const float* mean; const float* var;
+    void* out; float* bias;
+    int32_t kind, O, I, taps, o_pad, i_pad;
+} gyre_mlsd_fold_args;
+
 typedef struct gyre_unet gyre_unet;
 typedef struct gyre_hed gyre_hed;
+typedef struct gyre_mlsd gyre_mlsd;
 typedef struct gyre_swinir gyre_swinir;
 typedef struct gyre_hat gyre_hat;
 typedef struct gyre_lineart gyre_lineart;
@@ -624,6 +641,26 @@ int gyre_hed_forward(gyre_hed* h, void* stream, const void* image_nchw, int in_d
 /* The geometry of an image side n: sizes[5] = n + 68 and its ceil halves, offsets[5] = the crop offsets int(round(d / 2.)) of the five
  * maps, halves to even as Python rounds. */
 int gyre_hed_geometry(int n, int32_t* sizes, int32_t* offsets);
+
+/* ---- MLSD line detector ----------------------------------------------------
+ * The reference vendors the network (MobileV2_MLSD_Large) whose output the straight-line hint of the controlnet/mlsd hintsets is decoded
+ * from.  Weight keys, in the reference's state-dict order: backbone.features.0.{0.weight, 1.*}, backbone.features.1 .. 13.conv.*,
+ * block15 .. block22.{conv1, conv2}.{0.weight, 0.bias, 1.*}, block23.{conv1, conv2}.*, block23.conv3.{weight, bias}, where 1.* of a
+ * BatchNorm is weight, bias, running_mean, running_var: 305 entries, the reference's 362 less the 57 num_batches_tracked counters,
+ * which are not keys.  set_weight stages the raw parameters in fp32; finalize folds every BatchNorm (eval mode, eps 1e-5) into its
+ * convolution in fp32 and rounds the result once to storage.  Same workspace and dry-run sizing rules as the other handles. */
+int gyre_mlsd_create(const gyre_mlsd_cfg* cfg, int device, gyre_mlsd** out);
+void gyre_mlsd_destroy(gyre_mlsd* h);
+int gyre_mlsd_num_params(const gyre_mlsd* h);
+const char* gyre_mlsd_param_key(const gyre_mlsd* h, int i);
+int gyre_mlsd_set_weight(gyre_mlsd* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_mlsd_finalize(gyre_mlsd* h, void* stream);
+size_t gyre_mlsd_workspace_bytes(gyre_mlsd* h, int B, int H, int W);
+/* out[B][9][H / 2][W / 2] = MobileV2_MLSD_Large(image[B, 4, H, W]), channels 7 .. 15 of the network's 16-channel map.  H and W: at least
+ * 16 with (H / 2) % 8 == 0, the sizes at which the reference's concatenations line up (GYRE_ERR_INVALID otherwise, before any launch).
+ * A sample's result does not depend on the batch it runs in. */
+int gyre_mlsd_forward(gyre_mlsd* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                      void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -1117,6 +1154,25 @@ int gyre_op_conv7_out(void* stream, const void* xp, int B, int Ho, int Wo, const
 int gyre_op_hed_entry(void* stream, const void* x, int dtype, int B, int H, int W, void* y);
 int gyre_op_hed_tail(void* stream, const void* x, int B, int Hs, int Ws, int C, const float* w, const float* bias, void* pool, float* so);
 int gyre_op_hed_fuse(void* stream, const gyre_hed_fuse_args* args);
+/* The kernels of the MLSD line detector (kernels_mlsd.hip), one launch each; activations NHWC storage, channel counts and pixel
+ * strides in multiples of 8, fp32 arithmetic in a fixed order, one rounding.
+ * mlsd_fold: see gyre_mlsd_fold_args.  mlsd_entry: x NCHW [B][4][H][W] of dtype -> y [B][H / 2][W / 2][32] = relu6(conv3x3 stride 2 +
+ * bias), zero padding on the right / bottom only (output o reads inputs 2 o .. 2 o + 2); w [9][4][32] storage.
+ * dwconv3: y = relu6(depthwise 3x3 (x) + bias), w [9][C] storage; stride 1 with zero padding 1 -> [B][H][W][C], stride 2 with the
+ * right / bottom padding -> [B][H / 2][W / 2][C]; relu6_in: relu6 is applied to x as it is read.
+ * upsample2_ac: y[..][0 .. C) (pixel stride ldy) = bilinear x2, align_corners=True, of x [B][H][W] (pixel stride ldx); relu_in: relu on
+ * the reads.  dconv3_d5: y = relu(conv3x3 with dilation 5 and zero padding 5 (x) + bias), [B][H][W][64] -> the same, w [64][9][64].
+ * mlsd_act: in place, relu (relu6 != 0: relu6) over the first C channels of rows of pitch ld.  mlsd_relu_add: y = relu(y) + x over n
+ * elements.  mlsd_exit: out NCHW [B][9][H][W] of out_dtype = channels 7 .. 15 of x [B][H][W][16]. */
+int gyre_op_mlsd_fold(void* stream, const gyre_mlsd_fold_args* args);
+int gyre_op_mlsd_entry(void* stream, const void* x, int dtype, int B, int H, int W, const void* w, const float* bias, void* y);
+int gyre_op_dwconv3(void* stream, const void* x, int B, int H, int W, int C, const void* w, const float* bias, int stride, int relu6_in,
+                    void* y);
+int gyre_op_upsample2_ac(void* stream, const void* x, int B, int H, int W, int C, int ldx, int relu_in, void* y, int ldy);
+int gyre_op_dconv3_d5(void* stream, const void* x, int B, int H, int W, const void* w, const float* bias, void* y);
+int gyre_op_mlsd_act(void* stream, void* x, size_t rows, int C, int ld, int relu6);
+int gyre_op_mlsd_relu_add(void* stream, void* y, const void* x, size_t n);
+int gyre_op_mlsd_exit(void* stream, const void* x, int B, int H, int W, void* out, int out_dtype);
 /* The kernels of the token-sequence T2I networks (StyleAdapter, CoAdapterFuser; kernels_seq.hip), one launch each.
  * seq_attn: multi-head self-attention over the packed in_proj output.  qkv [N L][ld_qkv] storage, sample-major rows (row n L + l), q / k
  * / v of head h at columns h D / heads D + h D / 2 heads D + h D; o [N L][ld_o], head h written at [h D, h D + D), every other element
