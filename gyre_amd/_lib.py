@@ -123,6 +123,12 @@ class MlsdCfg(C.Structure):
     _fields_ = [("reserved", C.c_int32)]
 
 
+class SwinBCfg(C.Structure):
+    """gyre_swinb_cfg (include/gyre_hip.h)."""
+    _fields_ = [("embed_dim", C.c_int32), ("depths", C.c_int32 * 4), ("num_heads", C.c_int32 * 4), ("window_size", C.c_int32),
+                ("ape", C.c_int32), ("patch_norm", C.c_int32), ("qkv_bias", C.c_int32)]
+
+
 class MlsdFoldArgs(C.Structure):
     """gyre_mlsd_fold_args (include/gyre_hip.h): one launch of the BatchNorm fold, for tests."""
     _fields_ = [(n, C.c_void_p) for n in ("w", "conv_bias", "gamma", "beta", "mean", "var", "out", "bias")] + \
@@ -377,15 +383,19 @@ _SIGS = {
     "gyre_op_mlsd_act": (_i, [_vp, _vp, _sz, _i, _i, _i]),
     "gyre_op_mlsd_relu_add": (_i, [_vp, _vp, _vp, _sz]),
     "gyre_op_mlsd_exit": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
+    "gyre_op_win12_bias": (_i, [_vp, _vp, _i, _vp]),
+    "gyre_op_win12_attn": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
+    "gyre_op_swinb_embed": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gyre_op_swinb_merge_ln": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gyre_op_seq_attn_max_len": (_i, [_i]),
     "gyre_op_seq_attn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
     "gyre_op_quick_gelu": (_i, [_vp, _vp, _sz]),
     "gyre_op_fuser_pool": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i]),
     "gyre_op_fuser_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _vp, _i]),
 }
-# the handle surface of the three upscaler families and of the three hinters: image in, image out
+# the handle surface of the three upscaler families, of the three hinters and of the Swin-B backbone: image in, image(s) out
 for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg), ("hed", HedCfg),
-                    ("mlsd", MlsdCfg)):
+                    ("mlsd", MlsdCfg), ("swinb", SwinBCfg)):
     _SIGS.update({f"gyre_{_kind}_create": (_i, [C.POINTER(_cfg), _i, C.POINTER(_vp)]),
                   f"gyre_{_kind}_destroy": (None, [_vp]),
                   f"gyre_{_kind}_num_params": (_i, [_vp]),

@@ -303,6 +303,45 @@ def mlsd_config(**kw) -> MlsdConfig:
     return MlsdConfig(input_nc=4)
 
 
+class SwinBConfig(_AttrDict):
+    """Configuration of the Swin-B backbone of InSPyReNet - the keyword arguments of the reference's ``SwinTransformer`` constructor
+    (gyre/pipeline/hinters/inspyrenet/backbones/SwinTransformer.py) as ``SwinB()`` sets them: a mapping that also reads as attributes."""
+
+
+# SwinTransformer.__init__'s defaults under SwinB()'s four arguments
+_SWINB_CTOR = dict(pretrain_img_size=224, patch_size=4, in_chans=3, embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32],
+                   window_size=12, mlp_ratio=4.0, qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.2,
+                   norm_layer=None, ape=False, patch_norm=True, out_indices=(0, 1, 2, 3), frozen_stages=-1, use_checkpoint=False)
+
+
+def swinb_config(**kw) -> SwinBConfig:
+    """SwinB()'s configuration under ``kw``, refused (NotImplementedError) outside what the native path builds: window 12, four stages
+    at head dim 32 with the heads doubling (embed_dim = 32 * num_heads[0], a multiple of 32 up to 256), patch 4, in_chans 3, mlp_ratio 4,
+    ape=False, patch_norm=True, qkv_bias=True, qk_scale=None, all four stages as outputs.  Swin-T / S / L are not built."""
+    unknown = sorted(set(kw) - set(_SWINB_CTOR))
+    if unknown:
+        raise NotImplementedError(f"SwinTransformer: {unknown} are not arguments of its constructor (a configuration of another model family?)")
+    cfg = SwinBConfig(**{**_SWINB_CTOR, **kw})
+    cfg["depths"], cfg["num_heads"] = [int(d) for d in cfg["depths"]], [int(h) for h in cfg["num_heads"]]
+
+    def refuse(what):
+        raise NotImplementedError(f"SwinTransformer: {what} is outside the native path")
+    if cfg["window_size"] != 12:
+        refuse(f"window_size {cfg['window_size']} (12 is built: Swin-B; Swin-T / S use 7)")
+    if cfg["patch_size"] != 4 or cfg["in_chans"] != 3:
+        refuse(f"patch_size {cfg['patch_size']} / in_chans {cfg['in_chans']} (4 / 3 are built)")
+    if cfg["ape"] or not cfg["patch_norm"] or not cfg["qkv_bias"] or cfg["qk_scale"] is not None or cfg["norm_layer"] is not None:
+        refuse("ape=True, patch_norm=False, qkv_bias=False, a qk_scale or a norm_layer")
+    if len(cfg["depths"]) != 4 or len(cfg["num_heads"]) != 4 or tuple(cfg["out_indices"]) != (0, 1, 2, 3):
+        refuse("anything but four stages, all of them outputs")
+    E, heads = int(cfg["embed_dim"]), cfg["num_heads"]
+    if E < 32 or E % 32 or E > 256 or any(h != (E // 32) << i for i, h in enumerate(heads)):
+        refuse(f"embed_dim {E} with heads {heads} (head dim 32, heads doubling per stage, embed_dim up to 256)")
+    if any(not 1 <= d <= 64 for d in cfg["depths"]) or float(cfg["mlp_ratio"]) != 4.0:
+        refuse(f"depths {cfg['depths']} / mlp_ratio {cfg['mlp_ratio']} (1 to 64 blocks per stage at ratio 4)")
+    return cfg
+
+
 # the MobileNetV2 trunk of MLSD, cut after features[13]: (t, c, n, s) = expansion, width, repeats, stride of the first repeat
 MLSD_SETTING = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1))
 

@@ -334,6 +334,28 @@ int launch_mlsd_relu_add(hipStream_t st, bf16_t* y, const bf16_t* x, size_t n);
 // out NCHW [B][9][H][W] of out_dtype = channels 7 .. 15 of x NHWC [B][H][W][16]
 int launch_mlsd_exit(hipStream_t st, const bf16_t* x, int B, int H, int W, void* out, int out_dtype);
 
+// ---- Swin-B backbone kernels (kernels_swinb.hip) -------------------------------------
+// Shifted-window attention over 12 x 12 windows, head dim 32, on the map [B][H][W] zero-padded after norm1 to multiples of 12
+// (arithmetic and layouts: header of kernels_swinb.hip).
+//   qkv [B H W][ld_qkv] token order, q / k / v of head h at columns 32 h / 32 (heads + h) / 32 (2 heads + h); qkv_bias [96 heads] fp32:
+//   a padded token's q / k / v (rounded to storage); o [B H W][ld_o], head h written at [32 h, 32 h + 32) and nothing else; bias:
+//   launch_win12_bias's output; shift 0 or 6, always honoured (also on a map of one window).
+// GYRE_ERR_UNSUPPORTED / GYRE_ERR_INVALID outside the domain, nothing written.
+int win12_attn_check(const bf16_t* qkv, int ld_qkv, const float* qkv_bias, const bf16_t* o, int ld_o, const float* bias, int B, int H, int W,
+                     int heads, int shift);
+int launch_win12_attn(hipStream_t st, const bf16_t* qkv, int ld_qkv, const float* qkv_bias, bf16_t* o, int ld_o, const float* bias, int B,
+                      int H, int W, int heads, int shift);
+// relative_position_bias_table [529][heads] fp32 -> the expanded bias [heads][144 x 144] fp32 in the kernel's register order
+int launch_win12_bias(hipStream_t st, const float* table, int heads, float* out);
+// y [B][ceil(H / 4)][ceil(W / 4)][C] = LayerNorm(conv4x4 stride 4 (x NCHW [B][3][H][W] of dtype, zero-padded right / bottom) + bias);
+// w [C][48] fp32 in the PyTorch order (c, ky, kx), rounded to storage as it is staged; C % 32 == 0, C <= 256
+int launch_swinb_embed(hipStream_t st, const void* x, int dtype, int B, int H, int W, int C, const float* w, const float* bias,
+                       const float* gamma, const float* beta, float eps, bf16_t* y);
+// y [B][ceil(H / 2)][ceil(W / 2)][4 C] = LayerNorm over (x(2i, 2j) | x(2i + 1, 2j) | x(2i, 2j + 1) | x(2i + 1, 2j + 1)) of x [B][H][W][C],
+// zeros past the last row / column; C % 8 == 0, 4 C <= 2048
+int launch_swinb_merge_ln(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, const float* gamma, const float* beta, float eps,
+                          bf16_t* y);
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

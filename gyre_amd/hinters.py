@@ -1,5 +1,5 @@
 """The hinters on the native path: model shells and pipelines of the line-art generator, of the HED edge detector and of the MLSD line
-detector.
+detector, and the Swin-B backbone of the InSPyReNet background remover.
 
 The reference serves ``task: edge_detection`` engines (gyre/config/models/hinters.yaml) that turn a photo into the hint image a
 ControlNet or T2I adapter conditions on.  Three of them - ``hinters-lineart-anime``, ``-contour`` and ``-opensketch`` - are the
@@ -18,21 +18,25 @@ of its ``controlnet/mlsd`` hintsets:
                                                                                          decoder, 4 -> 9 channels at half the size
   ``GyreMlsdPipeline``             (an extension: the reference wires no pipeline for it)  the upstream M-LSD decode, restated: resample,
                                                                                          module, centre map, top-k, segments, raster
+  ``SwinB``                        gyre/pipeline/hinters/inspyrenet/backbones/             the backbone ``InSPyReNet`` takes as a module
+                                   SwinTransformer.py                                     (``task: background-removal``): 12 x 12 shifted
+                                                                                         windows, five feature maps; its PAA / SICA head
+                                                                                         stays the host module it is
 
 The modules' parameters carry the reference's state-dict names, so its checkpoints load strictly; all compute happens in the HIP
-library (gyre_lineart_forward, gyre_hed_forward, gyre_mlsd_forward) - there is no PyTorch fallback.  The other hinters (DexiNed, MiDaS / ZoeDepth, the
-segmenters, ...) are not built and stay host models.
+library (gyre_lineart_forward, gyre_hed_forward, gyre_mlsd_forward, gyre_swinb_forward) - there is no PyTorch fallback.  The other
+hinters (DexiNed, MiDaS / ZoeDepth, the segmenters, ...) and the InSPyReNet head are not built and stay host models.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
-from .config import hed_config, lineart_config, mlsd_config, mlsd_size_ok
+from .config import hed_config, lineart_config, mlsd_config, mlsd_size_ok, swinb_config
 from .hints import normalise_tensor
 from .modules import _NativeModule
 from .upscaler import MODELS_PATTERN, _NativeUpscaler, _only_match, _read_state_dict
-from .weights import hed_param_shapes, lineart_param_shapes, mlsd_is_buffer, mlsd_param_shapes
+from .weights import hed_param_shapes, lineart_param_shapes, mlsd_is_buffer, mlsd_param_shapes, swinb_is_buffer, swinb_param_shapes
 
 
 class GyreHipDrawingGenerator(_NativeUpscaler):
@@ -310,3 +314,71 @@ class GyreMlsdPipeline:
         H, W = tensor.shape[2:]
         result = torch.stack([mlsd_rasterise(l, H, W) for l in lines])[:, None]
         return result.to(tensor.device, tensor.dtype)
+
+
+# ---- Swin-B backbone of InSPyReNet ------------------------------------------------------------------------------------------------------
+class GyreHipSwinB(_NativeUpscaler):
+    """Drop-in for the reference's ``SwinB(pretrained=False)``, the backbone module ``InSPyReNet(backbone, ...)`` takes:
+    ``forward(x) -> tuple`` of five contiguous NCHW tensors, the normed patch embedding [B, C, ceil(H / 4), ceil(W / 4)] and the four
+    stage outputs at C, 2 C, 4 C, 8 C channels, each stage half the size of the one before (rounded up) - 128, 128, 256, 512, 1024
+    channels for Swin-B.  x NCHW [B, 3, H, W], H, W >= 4.  The parameters carry the reference's state-dict names and every attention's
+    ``relative_position_index`` is a buffer as there, so the ``backbone.`` part of an InSPyReNet checkpoint loads strictly; the buffer
+    is never read - the kernel computes the index.  ``depths`` / ``embed_dim`` / ``num_heads`` build smaller networks of the same
+    form; anything else is refused by ``config.swinb_config``.  The native call fills one flat buffer of which the five maps are views,
+    in the module's dtype: the caller casts them to the head's.  The handle, workspace and call machinery is the upscalers'."""
+
+    _kind = "swinb"
+    _param_shapes = staticmethod(swinb_param_shapes)
+    _in_key, _scale_key = "in_chans", None
+    _is_buffer = staticmethod(swinb_is_buffer)
+
+    def __init__(self, **kw):
+        _NativeModule.__init__(self)                 # (the reference's constructor takes keywords, not a configuration mapping)
+        self._adopt(swinb_config(**kw))
+
+    def _c_cfg(self):
+        c, cfg = self.config, _lib.SwinBCfg()
+        cfg.embed_dim, cfg.window_size = c.embed_dim, c.window_size
+        for i, (d, h) in enumerate(zip(c.depths, c.num_heads)):
+            cfg.depths[i], cfg.num_heads[i] = d, h
+        cfg.ape, cfg.patch_norm, cfg.qkv_bias = int(c.ape), int(c.patch_norm), int(c.qkv_bias)
+        return cfg
+
+    def map_shapes(self, shape):
+        """The five output shapes for an input of ``shape``."""
+        B, _, H, W = shape
+        E, h, w = self.config.embed_dim, -(-H // 4), -(-W // 4)
+        shapes = [(B, E, h, w)]
+        for i in range(4):
+            shapes.append((B, E << i, h, w))
+            h, w = -(-h // 2), -(-w // 2)
+        return shapes
+
+    def out_shape(self, shape):
+        return (sum(b * c * h * w for b, c, h, w in self.map_shapes(shape)),)
+
+    def _padding(self, H, W):
+        if H < 4 or W < 4:
+            raise ValueError(f"the Swin-B backbone takes images of at least 4 x 4 pixels, got {H} x {W}")
+        return 0, 0
+
+    def forward(self, x: torch.Tensor):
+        flat = super().forward(x)
+        maps, at = [], 0
+        for s in self.map_shapes(x.shape):
+            n = s[0] * s[1] * s[2] * s[3]
+            maps.append(flat[at:at + n].view(s))
+            at += n
+        return tuple(maps)
+
+
+def load_inspyrenet_backbone(path: str, torch_dtype=None, allow_patterns=None, ignore_patterns=None, **kw) -> GyreHipSwinB:
+    """The backbone with the ``backbone.`` weights of the InSPyReNet checkpoint at ``path``: a ``*.safetensors`` / ``*.pt`` / ``*.pth``
+    state dict, or a folder that holds exactly one (after the allow / ignore filters) - the layout of the reference's
+    ``background-removal`` model folders.  The head's keys are left to the caller's host module; the backbone's load is strict."""
+    import os
+    model = GyreHipSwinB(**kw)
+    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
+    sd = _read_state_dict(file)
+    model.load_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")})
+    return (model if torch_dtype is None else model.to(torch_dtype)).eval()

@@ -486,6 +486,49 @@ class _WindowShapes:
 SWINIR_BUFFERS = ("attn.relative_position_index", "attn_mask")      # state-dict entries that are buffers: loaded, never read
 
 
+def swinb_is_buffer(key: str) -> bool:
+    return key.endswith("relative_position_index")
+
+
+def swinb_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``SwinTransformer`` (gyre/pipeline/hinters/inspyrenet/backbones/SwinTransformer.py)
+    at window 12, in state_dict() order; every attention's ``relative_position_index`` is a (persistent) buffer there and is one
+    here; cfg: a mapping as gyre_amd.config.swinb_config returns."""
+    s: Shapes = OrderedDict()
+    E = cfg["embed_dim"]
+
+    def lin(p, o, i, bias=True):
+        s[p + ".weight"] = (o, i)
+        if bias:
+            s[p + ".bias"] = (o,)
+
+    def norm(p, c):
+        s[p + ".weight"] = (c,)
+        s[p + ".bias"] = (c,)
+
+    s["patch_embed.proj.weight"] = (E, 3, 4, 4)
+    s["patch_embed.proj.bias"] = (E,)
+    norm("patch_embed.norm", E)
+    for i, depth in enumerate(cfg["depths"]):
+        C = E << i
+        for j in range(depth):
+            p = f"layers.{i}.blocks.{j}"
+            norm(p + ".norm1", C)
+            s[p + ".attn.relative_position_bias_table"] = (529, cfg["num_heads"][i])
+            s[p + ".attn.relative_position_index"] = (144, 144)
+            lin(p + ".attn.qkv", 3 * C, C)
+            lin(p + ".attn.proj", C, C)
+            norm(p + ".norm2", C)
+            lin(p + ".mlp.fc1", 4 * C, C)
+            lin(p + ".mlp.fc2", C, 4 * C)
+        if i < 3:
+            lin(f"layers.{i}.downsample.reduction", 2 * C, 4 * C, bias=False)
+            norm(f"layers.{i}.downsample.norm", 4 * C)
+    for i in range(4):
+        norm(f"norm{i}", E << i)
+    return s
+
+
 def swinir_param_shapes(cfg) -> Shapes:
     """State-dict keys and shapes of the reference's ``SwinIR`` (gyre/pipeline/upscalers/models/network_swinir.py) with
     upsampler "nearest+conv", in state_dict() order and with its two kinds of buffers (SWINIR_BUFFERS): every attention's

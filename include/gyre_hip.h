@@ -266,7 +266,19 @@ typedef struct {
     int32_t kind, O, I, taps, o_pad, i_pad;
 } gyre_mlsd_fold_args;
 
+/* Swin-B backbone of InSPyReNet (the reference's gyre/pipeline/hinters/inspyrenet/backbones/SwinTransformer.py, SwinTransformer).
+ * Built: window_size 12, embed_dim = 32 num_heads[0] (a multiple of 32, at most 256), heads doubling per stage, depths 1 .. 64,
+ * in_chans 3, patch 4, mlp_ratio 4, ape 0, patch_norm 1, qkv_bias 1, all four stages as outputs; anything else: GYRE_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t embed_dim;
+    int32_t depths[4];
+    int32_t num_heads[4];
+    int32_t window_size;
+    int32_t ape, patch_norm, qkv_bias;
+} gyre_swinb_cfg;
+
 typedef struct gyre_unet gyre_unet;
+typedef struct gyre_swinb gyre_swinb;
 typedef struct gyre_hed gyre_hed;
 typedef struct gyre_mlsd gyre_mlsd;
 typedef struct gyre_swinir gyre_swinir;
@@ -661,6 +673,26 @@ size_t gyre_mlsd_workspace_bytes(gyre_mlsd* h, int B, int H, int W);
  * A sample's result does not depend on the batch it runs in. */
 int gyre_mlsd_forward(gyre_mlsd* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                       void* workspace, size_t workspace_bytes, void* out_nchw, int out_dtype);
+
+/* ---- Swin-B backbone (InSPyReNet) -------------------------------------------
+ * The reference's background-removal engine runs InSPyReNet on a SwinTransformer backbone it takes as a module; this handle is that
+ * backbone.  Weight keys, in the reference's state-dict order: patch_embed.{proj, norm}.*, layers.L.blocks.J.{norm1.*,
+ * attn.relative_position_bias_table, attn.qkv.*, attn.proj.*, norm2.*, mlp.fc1.*, mlp.fc2.*}, layers.L.downsample.{reduction.weight,
+ * norm.*} for L < 3, norm0 .. norm3.*; attn.relative_position_index is a buffer of the reference's state dict that the caller keeps -
+ * it is not a key here, the kernel computes the index.  finalize expands every block's table into the order k_win12_attn reads.
+ * Same workspace and dry-run sizing rules as the other handles. */
+int gyre_swinb_create(const gyre_swinb_cfg* cfg, int device, gyre_swinb** out);
+void gyre_swinb_destroy(gyre_swinb* h);
+int gyre_swinb_num_params(const gyre_swinb* h);
+const char* gyre_swinb_param_key(const gyre_swinb* h, int i);
+int gyre_swinb_set_weight(gyre_swinb* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_swinb_finalize(gyre_swinb* h, void* stream);
+size_t gyre_swinb_workspace_bytes(gyre_swinb* h, int B, int H, int W);
+/* out = the five maps of SwinTransformer.forward(image[B, 3, H, W]), NCHW of out_dtype, back to back: the normed patch embedding
+ * [B][C][h0][w0] with h0 = ceil(H / 4), then norm_i of stage i as [B][C 2^i][h_i][w_i], h_(i+1) = ceil(h_i / 2).  H, W >= 4
+ * (GYRE_ERR_INVALID otherwise, before any launch).  A sample's result does not depend on the batch it runs in. */
+int gyre_swinb_forward(gyre_swinb* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                       void* workspace, size_t workspace_bytes, void* out_maps, int out_dtype);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -1173,6 +1205,22 @@ int gyre_op_dconv3_d5(void* stream, const void* x, int B, int H, int W, const vo
 int gyre_op_mlsd_act(void* stream, void* x, size_t rows, int C, int ld, int relu6);
 int gyre_op_mlsd_relu_add(void* stream, void* y, const void* x, size_t n);
 int gyre_op_mlsd_exit(void* stream, const void* x, int B, int H, int W, void* out, int out_dtype);
+/* The kernels of the Swin-B backbone (kernels_swinb.hip), one launch each.
+ * win12_bias: relative_position_bias_table [529][heads] fp32 -> out [heads][144 x 144] fp32 in the register order of k_win12_attn.
+ * win12_attn: shifted-window attention over 12 x 12 windows at head dim 32 on the map [B][H][W] zero-padded (after norm1) to multiples
+ * of 12.  qkv [B H W][ld_qkv] storage, q / k / v of head h at columns 32 h / 32 (heads + h) / 32 (2 heads + h); qkv_bias [96 heads]
+ * fp32: what a padded token's q / k / v are, rounded to storage; o [B H W][ld_o], head h at [32 h, 32 h + 32); bias: win12_bias's
+ * output; shift 0 or 6 (always honoured).  Logits, softmax and the P V sums are fp32, scale 32^-1/2 on the fp32 dot product.
+ * swinb_embed: x NCHW [B][3][H][W] of dtype -> y [B][ceil(H / 4)][ceil(W / 4)][C] = LayerNorm(conv4x4 stride 4 (x zero-padded) + bias);
+ * w: the PyTorch weight [C][3][4][4] as fp32, rounded to storage as it is read; C a multiple of 32, at most 256.
+ * swinb_merge_ln: x [B][H][W][C] -> y [B][ceil(H / 2)][ceil(W / 2)][4 C] = LayerNorm over the 2 x 2 gather (even, even), (odd, even),
+ * (even, odd), (odd, odd) of the zero-padded map; 4 C at most 2048. */
+int gyre_op_win12_bias(void* stream, const float* table, int heads, float* out);
+int gyre_op_win12_attn(void* stream, const void* qkv, int ld_qkv, const float* qkv_bias, void* o, int ld_o, const float* bias, int B, int H,
+                       int W, int heads, int shift);
+int gyre_op_swinb_embed(void* stream, const void* x, int dtype, int B, int H, int W, int C, const float* w, const float* bias,
+                        const float* gamma, const float* beta, void* y);
+int gyre_op_swinb_merge_ln(void* stream, const void* x, int B, int H, int W, int C, const float* gamma, const float* beta, void* y);
 /* The kernels of the token-sequence T2I networks (StyleAdapter, CoAdapterFuser; kernels_seq.hip), one launch each.
  * seq_attn: multi-head self-attention over the packed in_proj output.  qkv [N L][ld_qkv] storage, sample-major rows (row n L + l), q / k
  * / v of head h at columns h D / heads D + h D / 2 heads D + h D; o [N L][ld_o], head h written at [h D, h D + D), every other element
