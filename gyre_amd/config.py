@@ -342,6 +342,45 @@ def swinb_config(**kw) -> SwinBConfig:
     return cfg
 
 
+class UniFormerConfig(_AttrDict):
+    """Configuration of the UniFormer backbone of the segmentation annotator - the keyword arguments of the reference's ``UniFormer``
+    constructor (gyre/pipeline/hinters/models/uniformer.py): a mapping that also reads as attributes."""
+
+
+# UniFormer.__init__'s defaults (uniformer_small); uniformer_base is layers [5, 8, 20, 7] at the same widths
+_UNIFORMER_CTOR = dict(layers=[3, 4, 8, 3], img_size=224, in_chans=3, num_classes=80, embed_dim=[64, 128, 320, 512], head_dim=64,
+                       mlp_ratio=4.0, qkv_bias=True, qk_scale=None, representation_size=None, drop_rate=0.0, attn_drop_rate=0.0,
+                       drop_path_rate=0.0, norm_layer=None, pretrained_path=None, use_checkpoint=False, checkpoint_num=[0, 0, 0, 0],
+                       windows=False, hybrid=False, window_size=14)
+
+
+def uniformer_config(**kw) -> UniFormerConfig:
+    """UniFormer()'s configuration under ``kw``, refused (NotImplementedError) outside what the native path builds: global attention
+    in stage 3 (windows=False, hybrid=False), head_dim 64, mlp_ratio 4, qkv_bias=True, qk_scale=None, in_chans 3, four stages with
+    embed_dim[0:2] == (64, 128) - the widths the local-relation kernel is built for - and later widths multiples of 64 up to 1024,
+    1 to 64 blocks per stage."""
+    unknown = sorted(set(kw) - set(_UNIFORMER_CTOR))
+    if unknown:
+        raise NotImplementedError(f"UniFormer: {unknown} are not arguments of its constructor (a configuration of another model family?)")
+    cfg = UniFormerConfig(**{**_UNIFORMER_CTOR, **kw})
+    cfg["layers"], cfg["embed_dim"] = [int(d) for d in cfg["layers"]], [int(d) for d in cfg["embed_dim"]]
+
+    def refuse(what):
+        raise NotImplementedError(f"UniFormer: {what} is outside the native path")
+    if cfg["windows"] or cfg["hybrid"]:
+        refuse("window / hybrid attention in stage 3 (global attention, windows=False and hybrid=False, is built)")
+    if cfg["head_dim"] != 64 or float(cfg["mlp_ratio"]) != 4.0 or not cfg["qkv_bias"] or cfg["qk_scale"] is not None:
+        refuse(f"head_dim {cfg['head_dim']} / mlp_ratio {cfg['mlp_ratio']} / qkv_bias {cfg['qkv_bias']} / qk_scale {cfg['qk_scale']} (64 / 4 / True / None are built)")
+    if cfg["in_chans"] != 3 or cfg["norm_layer"] is not None or cfg["representation_size"]:
+        refuse("in_chans other than 3, a norm_layer or a representation_size")
+    E = cfg["embed_dim"]
+    if len(E) != 4 or len(cfg["layers"]) != 4 or tuple(E[:2]) != (64, 128) or any(e < 64 or e % 64 or e > 1024 for e in E):
+        refuse(f"embed_dim {E} (four stages, (64, 128) first, then multiples of 64 up to 1024)")
+    if any(not 1 <= d <= 64 for d in cfg["layers"]):
+        refuse(f"layers {cfg['layers']} (1 to 64 blocks per stage)")
+    return cfg
+
+
 # the MobileNetV2 trunk of MLSD, cut after features[13]: (t, c, n, s) = expansion, width, repeats, stride of the first repeat
 MLSD_SETTING = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1))
 

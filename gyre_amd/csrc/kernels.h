@@ -356,6 +356,27 @@ int launch_swinb_embed(hipStream_t st, const void* x, int dtype, int B, int H, i
 int launch_swinb_merge_ln(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, const float* gamma, const float* beta, float eps,
                           bf16_t* y);
 
+// ---- UniFormer backbone kernels (kernels_uniformer.hip) --------------------------------
+// y = x + conv2(dw5x5(conv1(x))) over NHWC [B][H][W] at C = 64 / 128 channels with pixel strides ldx / ldy, one launch (arithmetic, the
+// three roundings and the tile: header of kernels_uniformer.hip).  w1 / w2 [C][C] storage, b1 / b2 [C], wd [25][C], bd [C] fp32.  A
+// position outside the map contributes ZERO to the 5x5 sum.  y overlapping x: GYRE_ERR_INVALID; outside the domain:
+// GYRE_ERR_UNSUPPORTED; nothing written either way.
+int uf_local_check(const bf16_t* x, int ldx, const bf16_t* y, int ldy, int B, int H, int W, int C, const bf16_t* w1, const float* b1,
+                   const float* wd, const float* bd, const bf16_t* w2, const float* b2);
+int launch_uf_local(hipStream_t st, const bf16_t* x, int ldx, bf16_t* y, int ldy, int B, int H, int W, int C, const bf16_t* w1, const float* b1,
+                    const float* wd, const float* bd, const bf16_t* w2, const float* b2);
+void uf_local_tile(int* th, int* tw);
+// y = x + dw3x3(x) + bias, zero padding 1, NHWC dense, C % 8 == 0, w [9][C] / bias [C] fp32; fp32, one rounding; not in place
+int launch_uf_cpe(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, const float* w, const float* bias, bf16_t* y);
+// [B][H][W][C] -> [B][H / 2][W / 2][4 C], column (2 dy + dx) C + c, floor division; bit copies
+int launch_uf_gather(hipStream_t st, const bf16_t* x, int B, int H, int W, int C, bf16_t* y);
+// NCHW [B][3][H][W] of dtype -> [B][H / 4][W / 4][64] storage, column (4 ky + kx) 4 + c, channel 3 of every group zero
+int launch_uf_gather_img(hipStream_t st, const void* x, int dtype, int B, int H, int W, bf16_t* y);
+// BatchNorm (eval) in front of a 1x1 convolution w [O][I] fp32 (b [O] or null) folded into it: wout [O][I] storage, bout [O] fp32
+int launch_uf_fold(hipStream_t st, const float* w, const float* b, const float* gamma, const float* beta, const float* mean, const float* var,
+                   float eps, int O, int I, bf16_t* wout, float* bout);
+int launch_uf_taps(hipStream_t st, const float* w, int C, int T, float* out);       // [C][T] fp32 -> [T][C] fp32
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

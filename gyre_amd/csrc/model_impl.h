@@ -115,7 +115,10 @@ enum ParamKind { PK_CONV3 = 0, PK_MAT = 1, PK_VEC = 2, PK_MAT_GEGLU = 3, PK_VEC_
                  // per output parity, [4][O]
                  PK_CONV7 = 8, PK_TCONV_SUBPIX = 9, PK_VEC_REP4 = 10,
                  // token-sequence T2I networks (model_t2i_seq.hip): a parameter P [I][O] used as x @ P, stored transposed [o_pad][i_pad]
-                 PK_MAT_T = 11 };
+                 PK_MAT_T = 11,
+                 // UniFormer (model_uniformer.hip): a p x p / stride p patch-embedding convolution [O][I][p][p] as the matrix [O][p][p][i_pad]
+                 // that multiplies the space-to-depth gather's rows (launch_uf_gather: column (ky p + kx) i_pad + c)
+                 PK_CONV_PATCH = 12 };
 struct Param {
     std::string key;
     std::vector<int64_t> shape;  // PyTorch shape expected from the caller
@@ -295,6 +298,9 @@ struct Store {
                 break;
             }
             case PK_CONV7: TRY(launch_repack_conv(st, src, dtype, O, (int)p.shape[1], 7, 7, p.i_pad, (bf16_t*)p.dev)); break;
+            case PK_CONV_PATCH:
+                TRY(launch_repack_conv(st, src, dtype, O, (int)p.shape[1], (int)p.shape[2], (int)p.shape[3], p.i_pad, (bf16_t*)p.dev));
+                break;
             case PK_TCONV_SUBPIX: TRY(launch_tconv_compose(st, src, dtype, O, (int)p.shape[1], (bf16_t*)p.dev)); break;
             case PK_VEC_REP4:
                 for (int q = 0; q < 4; ++q) TRY(launch_cast_f32(st, src, dtype, (size_t)O, 0, (float*)p.dev + (size_t)q * O));

@@ -1,5 +1,5 @@
 """The hinters on the native path: model shells and pipelines of the line-art generator, of the HED edge detector and of the MLSD line
-detector, and the Swin-B backbone of the InSPyReNet background remover.
+detector, the Swin-B backbone of the InSPyReNet background remover and the UniFormer backbone of the segmentation annotator.
 
 The reference serves ``task: edge_detection`` engines (gyre/config/models/hinters.yaml) that turn a photo into the hint image a
 ControlNet or T2I adapter conditions on.  Three of them - ``hinters-lineart-anime``, ``-contour`` and ``-opensketch`` - are the
@@ -22,21 +22,29 @@ of its ``controlnet/mlsd`` hintsets:
                                    SwinTransformer.py                                     (``task: background-removal``): 12 x 12 shifted
                                                                                          windows, five feature maps; its PAA / SICA head
                                                                                          stays the host module it is
+  ``UniFormer``                    gyre/pipeline/hinters/models/uniformer.py              the backbone of ``hinters-uniformer``, the default
+                                                                                         ``task: segmentation`` engine behind the
+                                                                                         ``controlnet/seg`` hintsets: two convolutional
+                                                                                         local-relation stages, two global-attention
+                                                                                         stages, four feature maps.  The mmseg UPerNet head,
+                                                                                         ``MmsegPipeline`` and ``MmLoader`` stay host code
 
 The modules' parameters carry the reference's state-dict names, so its checkpoints load strictly; all compute happens in the HIP
-library (gyre_lineart_forward, gyre_hed_forward, gyre_mlsd_forward, gyre_swinb_forward) - there is no PyTorch fallback.  The other
-hinters (DexiNed, MiDaS / ZoeDepth, the segmenters, ...) and the InSPyReNet head are not built and stay host models.
+library (gyre_lineart_forward, gyre_hed_forward, gyre_mlsd_forward, gyre_swinb_forward, gyre_uniformer_forward) - there is no PyTorch
+fallback.  The other hinters (DexiNed, MiDaS / ZoeDepth, the mmpose models, ...), the InSPyReNet head and the segmenter's UPerNet head
+are not built and stay host models.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
-from .config import hed_config, lineart_config, mlsd_config, mlsd_size_ok, swinb_config
+from .config import hed_config, lineart_config, mlsd_config, mlsd_size_ok, swinb_config, uniformer_config
 from .hints import normalise_tensor
 from .modules import _NativeModule
 from .upscaler import MODELS_PATTERN, _NativeUpscaler, _only_match, _read_state_dict
-from .weights import hed_param_shapes, lineart_param_shapes, mlsd_is_buffer, mlsd_param_shapes, swinb_is_buffer, swinb_param_shapes
+from .weights import (hed_param_shapes, lineart_param_shapes, mlsd_is_buffer, mlsd_param_shapes, swinb_is_buffer, swinb_param_shapes,
+                      uniformer_is_buffer, uniformer_param_shapes)
 
 
 class GyreHipDrawingGenerator(_NativeUpscaler):
@@ -380,5 +388,76 @@ def load_inspyrenet_backbone(path: str, torch_dtype=None, allow_patterns=None, i
     model = GyreHipSwinB(**kw)
     file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
     sd = _read_state_dict(file)
+    model.load_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")})
+    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+
+
+# ---- UniFormer backbone of the segmentation annotator ---------------------------------------------------------------------------------
+class GyreHipUniFormer(_NativeUpscaler):
+    """Drop-in for the reference's ``UniFormer(...)`` (windows=False, hybrid=False), the backbone of the mmseg segmentor behind
+    ``hinters-uniformer``: ``forward(x) -> tuple`` of four contiguous NCHW tensors, ``norm1 .. norm4`` of the four stages at
+    ``embed_dim`` channels (64, 128, 320, 512) and 1/4, 1/8, 1/16, 1/32 of the image (floor division at every step).  x NCHW
+    [B, 3, H, W], H, W >= 32.  The parameters carry the reference's state-dict names in its order, the BatchNorm statistics of the
+    convolutional blocks are buffers as there (``num_batches_tracked`` included), so the ``backbone.`` part of a segmentor checkpoint
+    loads strictly; the native handle folds each BatchNorm into the 1x1 convolution behind it.  ``layers`` / ``embed_dim[2:]`` build
+    uniformer_small, uniformer_base and smaller networks of the same form; anything else is refused by ``config.uniformer_config``.
+    The native call fills one flat buffer of which the four maps are views, in the module's dtype.  The UPerNet head, ``MmsegPipeline``
+    and ``MmLoader`` stay host code.  The handle, workspace and call machinery is the upscalers'."""
+
+    _kind = "uniformer"
+    _param_shapes = staticmethod(uniformer_param_shapes)
+    _in_key, _scale_key = "in_chans", None
+    _is_buffer = staticmethod(uniformer_is_buffer)
+    _buffer_dtype = staticmethod(lambda leaf: torch.long if leaf == "num_batches_tracked" else torch.float32)
+
+    def __init__(self, **kw):
+        _NativeModule.__init__(self)                 # (the reference's constructor takes keywords, not a configuration mapping)
+        self._adopt(uniformer_config(**kw))
+
+    def _c_cfg(self):
+        c, cfg = self.config, _lib.UniFormerCfg()
+        for i, (d, e) in enumerate(zip(c.layers, c.embed_dim)):
+            cfg.layers[i], cfg.embed_dim[i] = d, e
+        cfg.head_dim, cfg.mlp_ratio, cfg.qkv_bias = c.head_dim, int(c.mlp_ratio), int(c.qkv_bias)
+        cfg.windows, cfg.hybrid = int(c.windows), int(c.hybrid)
+        return cfg
+
+    def map_shapes(self, shape):
+        """The four output shapes for an input of ``shape``."""
+        B, _, H, W = shape
+        h, w, shapes = H // 4, W // 4, []
+        for e in self.config.embed_dim:
+            shapes.append((B, e, h, w))
+            h, w = h // 2, w // 2
+        return shapes
+
+    def out_shape(self, shape):
+        return (sum(b * c * h * w for b, c, h, w in self.map_shapes(shape)),)
+
+    def _padding(self, H, W):
+        if H < 32 or W < 32:
+            raise ValueError(f"the UniFormer backbone takes images of at least 32 x 32 pixels, got {H} x {W}")
+        return 0, 0
+
+    def forward(self, x: torch.Tensor):
+        flat = super().forward(x)
+        maps, at = [], 0
+        for s in self.map_shapes(x.shape):
+            n = s[0] * s[1] * s[2] * s[3]
+            maps.append(flat[at:at + n].view(s))
+            at += n
+        return tuple(maps)
+
+
+def load_uniformer_backbone(path: str, torch_dtype=None, allow_patterns=None, ignore_patterns=None, **kw) -> GyreHipUniFormer:
+    """The backbone with the ``backbone.`` weights of the mmseg segmentor checkpoint at ``path``: a ``*.safetensors`` / ``*.pt`` /
+    ``*.pth`` file (an mmcv checkpoint keeps its weights under ``state_dict``), or a folder that holds exactly one (after the allow /
+    ignore filters) - the layout of the reference's ``hinters-uniformer`` model folder.  The decode and auxiliary heads' keys are left to
+    the caller's host module; the backbone's load is strict."""
+    import os
+    model = GyreHipUniFormer(**kw)
+    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
+    sd = _read_state_dict(file)
+    sd = sd.get("state_dict", sd)
     model.load_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")})
     return (model if torch_dtype is None else model.to(torch_dtype)).eval()

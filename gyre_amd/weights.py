@@ -529,6 +529,54 @@ def swinb_param_shapes(cfg) -> Shapes:
     return s
 
 
+def uniformer_is_buffer(key: str) -> bool:
+    return key.endswith(MLSD_BUFFERS)                    # a BatchNorm's running statistics and num_batches_tracked
+
+
+def uniformer_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``UniFormer`` (gyre/pipeline/hinters/models/uniformer.py) with global attention
+    in stages 3 and 4, in state_dict() order: the four patch embeddings (norm before proj, as the module registers them), then per stage
+    its blocks and its norm.  The BatchNorms of the convolutional blocks carry running_mean, running_var and the scalar
+    num_batches_tracked as buffers (the last accepted by a strict load, never uploaded); cfg: a mapping as
+    gyre_amd.config.uniformer_config returns."""
+    s: Shapes = OrderedDict()
+    E = cfg["embed_dim"]
+
+    def lin(p, o, i, k=None):
+        s[p + ".weight"] = (o, i) if k is None else (o, i, k, k)
+        s[p + ".bias"] = (o,)
+
+    def norm(p, c, batch=False):
+        s[p + ".weight"] = (c,)
+        s[p + ".bias"] = (c,)
+        if batch:
+            s[p + ".running_mean"] = (c,)
+            s[p + ".running_var"] = (c,)
+            s[p + ".num_batches_tracked"] = ()
+
+    for i in range(4):
+        norm(f"patch_embed{i + 1}.norm", E[i])
+        lin(f"patch_embed{i + 1}.proj", E[i], E[i - 1] if i else 3, 2 if i else 4)
+    for i, depth in enumerate(cfg["layers"]):
+        C = E[i]
+        for j in range(depth):
+            p = f"blocks{i + 1}.{j}"
+            lin(p + ".pos_embed", C, 1, 3)
+            norm(p + ".norm1", C, batch=i < 2)
+            if i < 2:
+                lin(p + ".conv1", C, C, 1)
+                lin(p + ".conv2", C, C, 1)
+                lin(p + ".attn", C, 1, 5)
+            else:
+                lin(p + ".attn.qkv", 3 * C, C)
+                lin(p + ".attn.proj", C, C)
+            norm(p + ".norm2", C, batch=i < 2)
+            lin(p + ".mlp.fc1", 4 * C, C, 1 if i < 2 else None)
+            lin(p + ".mlp.fc2", C, 4 * C, 1 if i < 2 else None)
+        norm(f"norm{i + 1}", C)
+    return s
+
+
 def swinir_param_shapes(cfg) -> Shapes:
     """State-dict keys and shapes of the reference's ``SwinIR`` (gyre/pipeline/upscalers/models/network_swinir.py) with
     upsampler "nearest+conv", in state_dict() order and with its two kinds of buffers (SWINIR_BUFFERS): every attention's

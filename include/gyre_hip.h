@@ -277,8 +277,18 @@ typedef struct {
     int32_t ape, patch_norm, qkv_bias;
 } gyre_swinb_cfg;
 
+/* UniFormer backbone of the segmentation annotator (the reference's gyre/pipeline/hinters/models/uniformer.py, UniFormer).
+ * Built: windows 0, hybrid 0, head_dim 64, mlp_ratio 4, qkv_bias 1, embed_dim[0 .. 1] = (64, 128), embed_dim[2 .. 3] multiples of 64
+ * up to 1024, layers 1 .. 64 per stage (uniformer_small (3, 4, 8, 3), uniformer_base (5, 8, 20, 7)); anything else: GYRE_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t layers[4];
+    int32_t embed_dim[4];
+    int32_t head_dim, mlp_ratio, qkv_bias, windows, hybrid;
+} gyre_uniformer_cfg;
+
 typedef struct gyre_unet gyre_unet;
 typedef struct gyre_swinb gyre_swinb;
+typedef struct gyre_uniformer gyre_uniformer;
 typedef struct gyre_hed gyre_hed;
 typedef struct gyre_mlsd gyre_mlsd;
 typedef struct gyre_swinir gyre_swinir;
@@ -693,6 +703,26 @@ size_t gyre_swinb_workspace_bytes(gyre_swinb* h, int B, int H, int W);
  * (GYRE_ERR_INVALID otherwise, before any launch).  A sample's result does not depend on the batch it runs in. */
 int gyre_swinb_forward(gyre_swinb* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                        void* workspace, size_t workspace_bytes, void* out_maps, int out_dtype);
+
+/* ---- UniFormer backbone (segmentation annotator) -----------------------------
+ * The reference's default segmentation engine runs an mmseg UPerNet on the UniFormer backbone vendored in its tree; this handle is that
+ * backbone.  Weight keys, in the reference's state-dict order: patch_embedS.{norm, proj}.*, blocks1 / blocks2.J.{pos_embed.*, norm1.*
+ * (BatchNorm: weight, bias, running_mean, running_var), conv1.*, conv2.*, attn.*, norm2.*, mlp.fc1.*, mlp.fc2.*}, blocks3 / blocks4.J.
+ * {pos_embed.*, norm1.*, attn.qkv.*, attn.proj.*, norm2.*, mlp.fc1.*, mlp.fc2.*}, norm1 .. norm4.*; a BatchNorm's num_batches_tracked
+ * is a buffer the caller keeps, not a key here.  finalize folds every BatchNorm into the 1x1 convolution behind it (fp32, one rounding)
+ * and transposes the depthwise weights.  Same workspace and dry-run sizing rules as the other handles. */
+int gyre_uniformer_create(const gyre_uniformer_cfg* cfg, int device, gyre_uniformer** out);
+void gyre_uniformer_destroy(gyre_uniformer* h);
+int gyre_uniformer_num_params(const gyre_uniformer* h);
+const char* gyre_uniformer_param_key(const gyre_uniformer* h, int i);
+int gyre_uniformer_set_weight(gyre_uniformer* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_uniformer_finalize(gyre_uniformer* h, void* stream);
+size_t gyre_uniformer_workspace_bytes(gyre_uniformer* h, int B, int H, int W);
+/* out = the four maps of UniFormer.forward(image[B, 3, H, W]), NCHW of out_dtype, back to back: norm_i of stage i as
+ * [B][embed_dim[i]][h_i][w_i], h_1 = floor(H / 4), h_(i+1) = floor(h_i / 2).  H, W >= 32 (GYRE_ERR_INVALID otherwise, before any
+ * launch).  A sample's result does not depend on the batch it runs in. */
+int gyre_uniformer_forward(gyre_uniformer* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
+                           void* workspace, size_t workspace_bytes, void* out_maps, int out_dtype);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -1221,6 +1251,30 @@ int gyre_op_win12_attn(void* stream, const void* qkv, int ld_qkv, const float* q
 int gyre_op_swinb_embed(void* stream, const void* x, int dtype, int B, int H, int W, int C, const float* w, const float* bias,
                         const float* gamma, const float* beta, void* y);
 int gyre_op_swinb_merge_ln(void* stream, const void* x, int B, int H, int W, int C, const float* gamma, const float* beta, void* y);
+/* The kernels of the UniFormer backbone (kernels_uniformer.hip), one launch each; a refused call writes nothing.
+ * uf_local: y = x + conv2(dw5x5(conv1(x))) over an NHWC storage map [B][H][W] of C = 64 or 128 channels, pixel strides ldx / ldy >= C
+ * (ldx % 8, ldy % 4; only the C channels of a pixel are written).  w1, w2 [C][C] storage, b1, b2 [C] fp32 (w1 / b1 with the block's
+ * BatchNorm already folded in: uf_fold); wd [25][C], bd [C] fp32 (uf_taps of the PyTorch [C][1][5][5]).  Roundings: conv1(x) + b1 once
+ * to storage - and ZERO at a position outside the map, the depthwise convolution's own padding; the 25 fp32 taps + bd once; conv2 + b2
+ * + x once.  Any H, W >= 1.  y overlapping x: GYRE_ERR_INVALID (the neighbouring tiles read x); another C, misaligned rows:
+ * GYRE_ERR_UNSUPPORTED.  uf_local_tile: the output tile of a workgroup, pixels (rows, columns).
+ * uf_cpe: y = x + dw3x3(x) + bias, zero padding 1, [B][H][W][C] dense, C % 8 == 0; w [9][C], bias [C] fp32; fp32, one rounding; y must
+ * not overlap x (GYRE_ERR_INVALID).
+ * uf_gather: x [B][H][W][C] -> y [B][H / 2][W / 2][4 C], column (2 dy + dx) C + c = x[2 i + dy][2 j + dx][c]; floor division, a
+ * trailing odd row / column is dropped; bit copies; C % 8 == 0, H, W >= 2.
+ * uf_gather_img: x NCHW [B][3][H][W] of dtype -> y [B][H / 4][W / 4][64] storage, column (4 ky + kx) 4 + c, rounded once, c = 3 zero.
+ * uf_fold: a BatchNorm (eval) in front of a 1x1 convolution folded into it in fp32: wout [O][I] storage = rnd(w[o][i] s[i]),
+ * bout[o] = b[o] + sum_i w[o][i] (beta[i] - mean[i] s[i]), s = gamma / sqrt(var + eps); w [O][I] fp32, b [O] fp32 or null.
+ * uf_taps: w [C][T] fp32 -> out [T][C] fp32. */
+int gyre_op_uf_local(void* stream, const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, const void* w1, const float* b1,
+                     const float* wd, const float* bd, const void* w2, const float* b2);
+int gyre_op_uf_local_tile(int32_t* rows, int32_t* cols);
+int gyre_op_uf_cpe(void* stream, const void* x, int B, int H, int W, int C, const float* w, const float* bias, void* y);
+int gyre_op_uf_gather(void* stream, const void* x, int B, int H, int W, int C, void* y);
+int gyre_op_uf_gather_img(void* stream, const void* x, int dtype, int B, int H, int W, void* y);
+int gyre_op_uf_fold(void* stream, const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
+                    const float* var, float eps, int O, int I, void* wout, float* bout);
+int gyre_op_uf_taps(void* stream, const float* w, int C, int T, float* out);
 /* The kernels of the token-sequence T2I networks (StyleAdapter, CoAdapterFuser; kernels_seq.hip), one launch each.
  * seq_attn: multi-head self-attention over the packed in_proj output.  qkv [N L][ld_qkv] storage, sample-major rows (row n L + l), q / k
  * / v of head h at columns h D / heads D + h D / 2 heads D + h D; o [N L][ld_o], head h written at [h D, h D + D), every other element
