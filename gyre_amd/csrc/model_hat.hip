@@ -38,8 +38,7 @@ struct gyre_hat : WinTrunk {
 
     // a 1 x 1 convolution of the channel attention, kept in fp32 [O][I] for k_chan_gate
     void gate_mat(const std::string& key, int O, int I, float** w, float** b) {
-        *w = (float*)store.dmalloc((size_t)O * I * 4, true);
-        store.add(key + ".weight", {O, I, 1, 1}, PK_TABLE_F32, *w);
+        *w = f32(key + ".weight", {O, I, 1, 1});
         store.vec(key + ".bias", O, b);
     }
     int build() {
@@ -146,20 +145,10 @@ struct gyre_hat : WinTrunk {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(hat)
+
 extern "C" {
 
-int gyre_hat_create(const gyre_hat_cfg* cfg, int device, gyre_hat** out) { return handle_create(cfg, device, out); }
-void gyre_hat_destroy(gyre_hat* h) { delete h; }
-int gyre_hat_num_params(const gyre_hat* h) { return handle_num_params(h); }
-const char* gyre_hat_param_key(const gyre_hat* h, int i) { return handle_param_key(h, i); }
-int gyre_hat_set_weight(gyre_hat* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_hat_finalize(gyre_hat* h, void* st) { return handle_finalize(h); }
-size_t gyre_hat_workspace_bytes(gyre_hat* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_hat_forward(gyre_hat* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "hat", st, img, idt, B, H, W, ws, wsb, out, odt);
-}
 
 int gyre_op_hat_attn(void* st, const void* qkv, int ld_qkv, void* o, int ld_o, const float* table, int mode, int B, int H, int W, int heads,
                      int shift) {

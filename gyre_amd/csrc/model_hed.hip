@@ -16,6 +16,7 @@
 //
 // The planner sees every launch as if its sample ran alone (BatchInvariantScope) and the tail's sums have an order that depends on the
 // channel count alone: a sample's result does not depend on the batch it runs in.
+// The weight registration, the planner calls with their shape checks and the C ABI shell are ImageGraph's (model_upscaler.h).
 #include "model_upscaler.h"
 
 namespace {
@@ -40,21 +41,12 @@ inline void crop_offsets(int n, const int* s, int* o) {
 }
 }  // namespace
 
-struct gyre_hed {
+struct gyre_hed : ImageGraph {
     gyre_hed_cfg cfg;
-    Store store;
-    Exec ex;
-    bool finalized = false;
-    UpConv conv[13];
+    UpConv convs[13];
     float *sw[HED_STAGES] = {}, *sb[HED_STAGES] = {}, *fw = nullptr, *fb = nullptr;      // score_dsn1..5, score_final: fp32 vectors
+    gyre_hed() : ImageGraph("hed") {}
 
-    void conv3reg(const std::string& key, int cout, int cin, int cin_pad, UpConv& c) {
-        c.cin = cin_pad; c.cout = cout; c.rows = cout;
-        c.w = (bf16_t*)store.dmalloc((size_t)cout * 9 * cin_pad * 2, true);
-        store.add(key + ".weight", {cout, cin, 3, 3}, PK_CONV3, c.w, cout, cin_pad);
-        c.b = (float*)store.dmalloc((size_t)cout * 4, true);
-        store.add(key + ".bias", {cout}, PK_VEC, c.b);
-    }
     // a 1x1 convolution to one channel, kept as fp32 vectors (the kernels read them as such)
     void scorereg(const std::string& key, int cin, float** w, float** b) {
         *w = (float*)store.dmalloc((size_t)pad8(cin) * 4, true);
@@ -64,30 +56,15 @@ struct gyre_hed {
     }
     int build() {
         if (cfg.reserved != 0) GYRE_FAIL(GYRE_ERR_INVALID, "hed: the reserved configuration field must be 0");
-        ex.store = &store;
         int n = 0, cin = 3;
         for (int k = 0; k < HED_STAGES; ++k)
             for (int j = 0; j < HED_CONVS[k]; ++j) {
-                conv3reg("conv" + std::to_string(k + 1) + "_" + std::to_string(j + 1), HED_WIDTH[k], cin, cin == 3 ? 8 : cin, conv[n++]);
+                conv("conv" + std::to_string(k + 1) + "_" + std::to_string(j + 1), HED_WIDTH[k], cin, 3, HED_WIDTH[k], cin == 3 ? 8 : cin, PK_CONV3, convs[n++]);
                 cin = HED_WIDTH[k];
             }
         for (int k = 0; k < HED_STAGES; ++k) scorereg("score_dsn" + std::to_string(k + 1), HED_WIDTH[k], &sw[k], &sb[k]);
         scorereg("score_final", 5, &fw, &fb);
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
-    }
-
-    bf16_t* at(const Tn& t) const { return ex.arena.dry ? (bf16_t*)(uintptr_t)4096 : t.p; }
-    // out = conv3x3(x) + bias, zero padding 1, on the planner
-    int conv3(const Tn& x, const UpConv& c, Tn& out) {
-        if (x.C != c.cin || out.C != c.rows || out.H != x.H || out.W != x.W || out.B != x.B) GYRE_FAIL(GYRE_ERR_INVALID, "hed: internal shape mismatch");
-        GemmParams p;
-        p.A = at(x); p.lda = x.C; p.mode = GEMM_CONV3;
-        p.Hi = x.H; p.Wi = x.W; p.Cin = x.C; p.Ho = x.H; p.Wo = x.W; p.stride = 1; p.pad = 1; p.ups = 0;
-        p.W = c.w; p.K = 9 * x.C; p.N = c.rows; p.M = x.B * x.H * x.W;
-        p.bias = c.b; p.rows_per_sample = x.H * x.W;
-        p.out = at(out); p.ldc = out.C; p.out_mode = OUT_BF16;
-        return ex.run_gemm(p);
+        return check_allocs();
     }
 
     int run(bool dry, hipStream_t st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
@@ -97,7 +74,7 @@ struct gyre_hed {
             (size_t)B * (H + 2 * HED_BORDER) * (W + 2 * HED_BORDER) > 0x3fffffff)
             GYRE_FAIL(GYRE_ERR_INVALID, "hed: image too large (B (H + 68) (W + 68) must stay below 2^30)");
         BatchInvariantScope invariant;
-        ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
+        begin(dry, st, B, ws, wsb);
         int hs[HED_STAGES], wsz[HED_STAGES];
         stage_sizes(H, hs); stage_sizes(W, wsz);
         Tn cur, nxt, so[HED_STAGES];
@@ -107,7 +84,7 @@ struct gyre_hed {
         for (int k = 0; k < HED_STAGES; ++k) {
             for (int j = 0; j < HED_CONVS[k]; ++j) {
                 TRY(ex.alloc(nxt, B, hs[k], wsz[k], HED_WIDTH[k]));
-                TRY(conv3(cur, conv[n++], nxt));
+                TRY(conv3(cur, cur.C, convs[n++], 1, 1, 0, nullptr, nxt));        // (nxt is allocated at the convolution's width)
                 ex.free(cur);
                 cur = nxt; nxt = Tn();
                 if (j + 1 < HED_CONVS[k] && !dry) TRY(launch_relu(st, cur.p, (size_t)cur.rows() * cur.C));
@@ -132,20 +109,10 @@ struct gyre_hed {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(hed)
+
 extern "C" {
 
-int gyre_hed_create(const gyre_hed_cfg* cfg, int device, gyre_hed** out) { return handle_create(cfg, device, out); }
-void gyre_hed_destroy(gyre_hed* h) { delete h; }
-int gyre_hed_num_params(const gyre_hed* h) { return handle_num_params(h); }
-const char* gyre_hed_param_key(const gyre_hed* h, int i) { return handle_param_key(h, i); }
-int gyre_hed_set_weight(gyre_hed* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_hed_finalize(gyre_hed* h, void* st) { return handle_finalize(h); }
-size_t gyre_hed_workspace_bytes(gyre_hed* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_hed_forward(gyre_hed* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "hed", st, img, idt, B, H, W, ws, wsb, out, odt);
-}
 // the geometry the graph uses for an image side n: sizes[5] of the stages, offsets[5] of the crops
 int gyre_hed_geometry(int n, int32_t* sizes, int32_t* offsets) {
     if (n < 1 || n > 0x3fffffff - 2 * HED_BORDER || !sizes || !offsets) GYRE_FAIL(GYRE_ERR_INVALID, "hed_geometry: a side of at least 1 and two arrays of 5");

@@ -1,5 +1,5 @@
 // Model runtime internals shared by model.hip (forward graphs + C ABI), model_vjp.hip (input-gradient graphs), model_ctrl.hip,
-// model_t2i.hip and, through model_upscaler.h, the upscaler graphs (model_rrdb.hip, model_swinir.hip, model_hat.hip) and the hinter graphs (model_lineart.hip, model_hed.hip): workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
+// model_t2i.hip and, through model_upscaler.h, the upscaler graphs (model_rrdb.hip, model_swinir.hip, model_hat.hip) and the hinter graphs (model_lineart.hip, model_hed.hip, model_mlsd.hip, model_swinb.hip, model_uniformer.hip): workspace arena, weight store, per-layer weight records, the op executor, the UNet trunk and the UNet / VAE graph objects.
 #pragma once
 #include "../../include/gyre_hip.h"
 #include "kernels.h"
@@ -1959,12 +1959,17 @@ template <typename H> static int handle_finalize(H* h) {
     h->finalized = true;
     return 0;
 }
+// the image models (ImageGraph, model_upscaler.h): the handle's own finalize, which also fills the weights it derives on `st`
+template <typename H> static int handle_finalize(H* h, void* st) {
+    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
+    return h->finalize((hipStream_t)st);
+}
 template <typename H> static int handle_set_weight(H* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
     if (!h || !key || !p || !shape) GYRE_FAIL(GYRE_ERR_INVALID, "null argument");
     h->finalized = false;
     return h->store.set_weight(key, p, dtype, shape, ndim, (hipStream_t)st);
 }
-// the two below: handles of the image-in / image-out shape (gyre_{rrdb,swinir,hat,lineart,hed}), whose run(dry, stream, image, dtype, B, H, W,
+// the two below: handles of the image-in / image-out shape (every ImageGraph of model_upscaler.h), whose run(dry, stream, image, dtype, B, H, W,
 // workspace, bytes, out, dtype) sizes the workspace when dry
 template <typename H> static size_t handle_workspace_bytes(H* h, int B, int H_, int W) {
     if (!h) return 0;

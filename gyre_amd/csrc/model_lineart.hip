@@ -20,31 +20,18 @@
 // A convolution's bias is kept (the normalisation behind it cancels it in exact arithmetic only).  The planner sees every launch as
 // if its sample ran alone (BatchInvariantScope), and the statistics are per-sample partials: a sample's result does not depend on the
 // batch it runs in.
+// The weight registration, the planner calls with their shape checks and the C ABI shell are ImageGraph's (model_upscaler.h).
 #include "model_upscaler.h"
 
-struct gyre_lineart {
+struct gyre_lineart : ImageGraph {
     gyre_lineart_cfg cfg;
-    Store store;
-    Exec ex;
-    bool finalized = false;
     UpConv c0, d1, d2, c4;             // model0.1 (7x7), model1.0, model1.3, model4.1 (7x7)
     std::vector<UpConv> rb;            // model2.{i}.conv_block.1 / .5
     UpLin t1, t2;                      // model3.0, model3.3 in sub-pixel form
+    gyre_lineart() : ImageGraph("lineart") {}
 
-    void conv3reg(const std::string& key, int cout, int cin, UpConv& c) {
-        c.cin = cin; c.cout = cout; c.rows = cout;
-        c.w = (bf16_t*)store.dmalloc((size_t)cout * 9 * cin * 2, true);
-        store.add(key + ".weight", {cout, cin, 3, 3}, PK_CONV3, c.w, cout, cin);
-        c.b = (float*)store.dmalloc((size_t)cout * 4, true);
-        store.add(key + ".bias", {cout}, PK_VEC, c.b);
-    }
-    void conv7reg(const std::string& key, int cout, int cin, int cin_pad, UpConv& c) {
-        c.cin = cin_pad; c.cout = cout; c.rows = cout;
-        c.w = (bf16_t*)store.dmalloc((size_t)cout * 49 * cin_pad * 2, true);
-        store.add(key + ".weight", {cout, cin, 7, 7}, PK_CONV7, c.w, cout, cin_pad);
-        c.b = (float*)store.dmalloc((size_t)cout * 4, true);
-        store.add(key + ".bias", {cout}, PK_VEC, c.b);
-    }
+    void conv3reg(const std::string& key, int cout, int cin, UpConv& c) { conv(key, cout, cin, 3, cout, cin, PK_CONV3, c); }
+    void conv7reg(const std::string& key, int cout, int cin, int cin_pad, UpConv& c) { conv(key, cout, cin, 7, cout, cin_pad, PK_CONV7, c); }
     void tconvreg(const std::string& key, int cin, int cout, UpLin& l) {
         l.K = 4 * cin; l.N = 4 * cout;
         l.w = (bf16_t*)store.dmalloc((size_t)l.N * l.K * 2, true);
@@ -58,7 +45,6 @@ struct gyre_lineart {
         if (c.output_nc != 1) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "lineart: output_nc 1 is the only one built");
         if (c.n_residual_blocks < 1 || c.n_residual_blocks > 16) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "lineart: 1 to 16 residual blocks are built");
         if (c.sigmoid != 0 && c.sigmoid != 1) GYRE_FAIL(GYRE_ERR_INVALID, "lineart: sigmoid must be 0 or 1");
-        ex.store = &store;
         conv7reg("model0.1", 64, 3, 8, c0);
         conv3reg("model1.0", 128, 64, d1);
         conv3reg("model1.3", 256, 128, d2);
@@ -71,22 +57,13 @@ struct gyre_lineart {
         tconvreg("model3.0", 256, 128, t1);
         tconvreg("model3.3", 128, 64, t2);
         conv7reg("model4.1", 1, 64, 64, c4);
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
+        return check_allocs();
     }
 
-    bf16_t* at(const Tn& t) const { return ex.arena.dry ? (bf16_t*)(uintptr_t)4096 : t.p; }
     // out = conv3x3(x) + bias on the planner: zero padding `pad` (1: the stride-2 convolutions; 0: over a reflect-padded image)
     int conv3(const Tn& x, const UpConv& c, int stride, int pad, Tn& out) {
-        const int Ho = (x.H + 2 * pad - 3) / stride + 1, Wo = (x.W + 2 * pad - 3) / stride + 1;
-        if (x.C != c.cin || out.C != c.rows || out.H != Ho || out.W != Wo || out.B != x.B) GYRE_FAIL(GYRE_ERR_INVALID, "lineart: internal shape mismatch");
-        GemmParams p;
-        p.A = at(x); p.lda = x.C; p.mode = GEMM_CONV3;
-        p.Hi = x.H; p.Wi = x.W; p.Cin = x.C; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad = pad; p.ups = 0;
-        p.W = c.w; p.K = 9 * x.C; p.N = c.rows; p.M = x.B * Ho * Wo;
-        p.bias = c.b; p.rows_per_sample = Ho * Wo;
-        p.out = at(out); p.ldc = out.C; p.out_mode = OUT_BF16;
-        return ex.run_gemm(p);
+        if (out.C != c.rows) return mismatch();
+        return ImageGraph::conv3(x, x.C, c, stride, pad, 0, nullptr, out);
     }
     // stats of the logical image [B][rows][C] held by t (dense rows of C channels), then the apply pass `a` over it
     int norm(const Tn& t, size_t rows, int C, InormApply a) {
@@ -106,7 +83,7 @@ struct gyre_lineart {
         if (B < 1 || B > 65535 || H < 5 || W < 5) GYRE_FAIL(GYRE_ERR_INVALID, "lineart: the image must be at least 5 x 5 (below that the reflection paddings have nothing to mirror)");
         if ((size_t)B * H * W > 0x3fffffff) GYRE_FAIL(GYRE_ERR_INVALID, "lineart: image too large");
         BatchInvariantScope invariant;
-        ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
+        begin(dry, st, B, ws, wsb);
         const int H1 = (H + 1) / 2, W1 = (W + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
         Tn x0, raw, act;
         // model0
@@ -150,13 +127,13 @@ struct gyre_lineart {
         // model3
         Tn up1, pat2, up2, fin;
         TRY(ex.alloc(up1, B, H2, W2, 512));
-        TRY(ex.linear(at(xp), 1024, nullptr, 0, 0, xp.rows(), t1.K, t1.w, t1.N, t1.b, nullptr, 0, 0, at(up1), 512));
+        TRY(linear(xp, t1, nullptr, up1));
         ex.free(xp);
         TRY(ex.alloc(pat2, B, 2 * H2, 2 * W2, 512));
         { InormApply a; a.H = 2 * H2; a.W = 2 * W2; a.shuffled = 1; a.relu = 1; a.patch = 1; a.out = pat2.p; TRY(norm(up1, (size_t)4 * H2 * W2, 128, a)); }
         ex.free(up1);
         TRY(ex.alloc(up2, B, 2 * H2, 2 * W2, 256));
-        TRY(ex.linear(at(pat2), 512, nullptr, 0, 0, pat2.rows(), t2.K, t2.w, t2.N, t2.b, nullptr, 0, 0, at(up2), 256));
+        TRY(linear(pat2, t2, nullptr, up2));
         ex.free(pat2);
         // model4
         const int Ho = 4 * H2, Wo = 4 * W2;
@@ -172,20 +149,10 @@ struct gyre_lineart {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(lineart)
+
 extern "C" {
 
-int gyre_lineart_create(const gyre_lineart_cfg* cfg, int device, gyre_lineart** out) { return handle_create(cfg, device, out); }
-void gyre_lineart_destroy(gyre_lineart* h) { delete h; }
-int gyre_lineart_num_params(const gyre_lineart* h) { return handle_num_params(h); }
-const char* gyre_lineart_param_key(const gyre_lineart* h, int i) { return handle_param_key(h, i); }
-int gyre_lineart_set_weight(gyre_lineart* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_lineart_finalize(gyre_lineart* h, void* st) { return handle_finalize(h); }
-size_t gyre_lineart_workspace_bytes(gyre_lineart* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_lineart_forward(gyre_lineart* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "lineart", st, img, idt, B, H, W, ws, wsb, out, odt);
-}
 
 // ---- test hooks of kernels_inorm.hip ----
 size_t gyre_op_inorm_workspace(int B, size_t HW, int C) { return inorm_partial_floats(B, HW, C) * sizeof(float); }

@@ -22,6 +22,7 @@
 //
 // Accepted sizes: those where the reference's concatenations line up, n >= 16 and (n / 2) % 8 == 0 per side.
 // The planner sees every launch as if its sample ran alone (BatchInvariantScope); the other kernels work per pixel.
+// The weight registration, the planner calls with their shape checks and the C ABI shell are ImageGraph's (model_upscaler.h).
 #include "model_upscaler.h"
 
 namespace {
@@ -38,37 +39,29 @@ inline bool side_ok(int n) { return n >= 16 && (n / 2) % 8 == 0; }
 struct BnConv {
     MlsdFold f;
     bf16_t* w = nullptr; float* bias = nullptr;
+    UpConv conv() const { UpConv c; c.w = w; c.b = bias; c.cin = f.i_pad; c.cout = f.O; c.rows = f.o_pad; return c; }
 };
 }  // namespace
 
-struct gyre_mlsd {
+struct gyre_mlsd : ImageGraph {
     gyre_mlsd_cfg cfg;
-    Store store;
-    Exec ex;
-    bool finalized = false;
     BnConv first, expand[MLSD_BLOCKS], dw[MLSD_BLOCKS], proj[MLSD_BLOCKS];
     BnConv a1[4], a2[4], b1[4], b2[4], c1, c2;              // blocks 15/17/19/21 (conv1, conv2), 16/18/20/22, 23
     UpLin c3;                                               // block23.conv3: biased 1x1 without a BatchNorm
     std::vector<BnConv*> folds;
+    gyre_mlsd() : ImageGraph("mlsd") {}
 
-    float* stage(const std::string& key, std::vector<int64_t> shape) {
-        size_t n = 1;
-        for (auto d : shape) n *= (size_t)d;
-        float* p = (float*)store.dmalloc(n * 4, true);
-        store.add(key, std::move(shape), PK_TABLE_F32, p);
-        return p;
-    }
     // conv: key of the convolution, bn: key of its BatchNorm; state-dict order: conv.weight (conv.bias) bn.weight bn.bias bn.running_mean bn.running_var
     void reg(const std::string& conv, const std::string& bn, int kind, int O, int I, int taps, int o_pad, int i_pad, bool has_bias, BnConv& c) {
         const int k = taps == 9 ? 3 : 1;
         MlsdFold& f = c.f;
         f.kind = kind; f.O = O; f.I = I; f.taps = taps; f.o_pad = o_pad; f.i_pad = i_pad;
-        f.w = stage(conv + ".weight", {O, kind == MLSD_FOLD_DEPTHWISE ? 1 : I, k, k});
-        if (has_bias) f.conv_bias = stage(conv + ".bias", {O});
-        f.gamma = stage(bn + ".weight", {O});
-        f.beta = stage(bn + ".bias", {O});
-        f.mean = stage(bn + ".running_mean", {O});
-        f.var = stage(bn + ".running_var", {O});
+        f.w = f32(conv + ".weight", {O, kind == MLSD_FOLD_DEPTHWISE ? 1 : I, k, k});
+        if (has_bias) f.conv_bias = f32(conv + ".bias", {O});
+        f.gamma = f32(bn + ".weight", {O});
+        f.beta = f32(bn + ".bias", {O});
+        f.mean = f32(bn + ".running_mean", {O});
+        f.var = f32(bn + ".running_var", {O});
         const size_t n = kind == MLSD_FOLD_DENSE ? (size_t)o_pad * taps * i_pad : kind == MLSD_FOLD_DEPTHWISE ? (size_t)9 * o_pad : (size_t)9 * I * o_pad;
         c.w = (bf16_t*)store.dmalloc(n * 2, true);
         c.bias = (float*)store.dmalloc((size_t)o_pad * 4, true);
@@ -80,7 +73,6 @@ struct gyre_mlsd {
     }
     int build() {
         if (cfg.reserved != 0) GYRE_FAIL(GYRE_ERR_INVALID, "mlsd: the reserved configuration field must be 0");
-        ex.store = &store;
         folds.reserve(64);
         reg("backbone.features.0.0", "backbone.features.0.1", MLSD_FOLD_ENTRY, 32, 4, 9, 32, 4, false, first);
         for (int i = 0; i < MLSD_BLOCKS; ++i) {
@@ -102,13 +94,8 @@ struct gyre_mlsd {
         }
         dense("block23.conv1.0", "block23.conv1.1", 64, 64, 9, true, c1);
         dense("block23.conv2.0", "block23.conv2.1", 64, 64, 9, true, c2);
-        c3.K = 64; c3.N = 16;
-        c3.w = (bf16_t*)store.dmalloc((size_t)16 * 64 * 2, true);
-        store.add("block23.conv3.weight", {16, 64, 1, 1}, PK_MAT, c3.w, 16, 64);
-        c3.b = (float*)store.dmalloc(16 * 4, true);
-        store.add("block23.conv3.bias", {16}, PK_VEC, c3.b);
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
+        lin("block23.conv3", 16, 64, 16, 64, true, true, c3);
+        return check_allocs();
     }
     int finalize(hipStream_t st) {
         TRY(store.finalize());
@@ -117,38 +104,27 @@ struct gyre_mlsd {
         return 0;
     }
 
-    bf16_t* at(const Tn& t) const { return ex.arena.dry ? (bf16_t*)(uintptr_t)4096 : t.p; }
-    // out[.., 0 .. N) (pixel stride ldc) = x @ w^T + b (+ res), a 1x1 convolution on the planner
-    int lin(const Tn& x, const bf16_t* w, const float* b, int K, int N, const Tn* res, bf16_t* out, int ldc) {
-        if (x.C != K || (res && res->C != N)) GYRE_FAIL(GYRE_ERR_INVALID, "mlsd: internal shape mismatch");
-        return ex.linear(at(x), x.C, nullptr, 0, 0, x.rows(), K, w, N, b, res ? at(*res) : nullptr, res ? res->C : 0, 0, out, ldc);
-    }
-    int lin(const Tn& x, const BnConv& c, const Tn* res, Tn& out) { return lin(x, c.w, c.bias, c.f.i_pad, c.f.o_pad, res, at(out), out.C); }
+    // a folded 1x1 convolution on the planner, written over the whole of `out`
+    int pointwise(const Tn& x, const BnConv& c, const Tn* res, Tn& out) { return linear_to(x, c.w, c.bias, c.f.i_pad, c.f.o_pad, res, at(out), out.C); }
     // out = conv3x3(x) + b, zero padding 1, on the planner
     int conv3(const Tn& x, const BnConv& c, Tn& out) {
-        if (x.C != c.f.i_pad || out.C != c.f.o_pad || out.H != x.H || out.W != x.W || out.B != x.B) GYRE_FAIL(GYRE_ERR_INVALID, "mlsd: internal shape mismatch");
-        GemmParams p;
-        p.A = at(x); p.lda = x.C; p.mode = GEMM_CONV3;
-        p.Hi = x.H; p.Wi = x.W; p.Cin = x.C; p.Ho = x.H; p.Wo = x.W; p.stride = 1; p.pad = 1; p.ups = 0;
-        p.W = c.w; p.K = 9 * x.C; p.N = c.f.o_pad; p.M = x.B * x.H * x.W;
-        p.bias = c.bias; p.rows_per_sample = x.H * x.W;
-        p.out = at(out); p.ldc = out.C; p.out_mode = OUT_BF16;
-        return ex.run_gemm(p);
+        if (out.C != c.f.o_pad) return mismatch();
+        return ImageGraph::conv3(x, x.C, c.conv(), 1, 1, 0, nullptr, out);
     }
     int relu(Tn& t) { return ex.dry() ? 0 : launch_mlsd_act(ex.st, t.p, (size_t)t.rows(), t.C, t.C, 0); }
 
     // BlockTypeA over the taps a (1x1 conv2) and b (1x1 conv1, upsampled x2 unless k == 0) -> cat [B][a.H][a.W][128]
     int block_a(int k, const Tn& a, const Tn& b, Tn& cat) {
         TRY(ex.alloc(cat, a.B, a.H, a.W, 128));
-        TRY(lin(a, a2[k].w, a2[k].bias, a2[k].f.i_pad, 64, nullptr, at(cat), 128));
+        TRY(linear_to(a, a2[k].w, a2[k].bias, a2[k].f.i_pad, 64, nullptr, at(cat), 128));
         if (k == 0) {
-            TRY(lin(b, a1[k].w, a1[k].bias, a1[k].f.i_pad, 64, nullptr, at(cat) + 64, 128));
+            TRY(linear_to(b, a1[k].w, a1[k].bias, a1[k].f.i_pad, 64, nullptr, at(cat) + 64, 128));
             return relu(cat);
         }
         if (a.H != 2 * b.H || a.W != 2 * b.W) GYRE_FAIL(GYRE_ERR_INVALID, "mlsd: internal shape mismatch");
         Tn bb;
         TRY(ex.alloc(bb, b.B, b.H, b.W, 64));
-        TRY(lin(b, a1[k], nullptr, bb));
+        TRY(pointwise(b, a1[k], nullptr, bb));
         if (!ex.dry()) {
             TRY(launch_mlsd_act(ex.st, cat.p, (size_t)cat.rows(), 64, 128, 0));
             TRY(launch_mlsd_up2(ex.st, bb.p, b.B, b.H, b.W, 64, 64, 1, cat.p + 64, 128));
@@ -176,7 +152,7 @@ struct gyre_mlsd {
         // the planner indexes rows with 32-bit integers
         if ((size_t)B * (H / 2) * (W / 2) > 0x3fffffff) GYRE_FAIL(GYRE_ERR_INVALID, "mlsd: image too large (B (H / 2) (W / 2) must stay below 2^30)");
         BatchInvariantScope invariant;
-        ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
+        begin(dry, st, B, ws, wsb);
         int h = H / 2, w = W / 2;
         Tn cur, c[5];
         TRY(ex.alloc(cur, B, h, w, 32));
@@ -188,7 +164,7 @@ struct gyre_mlsd {
             Tn e, d, o;
             if (s.t != 1) {
                 TRY(ex.alloc(e, B, h, w, hidp));
-                TRY(lin(cur, expand[i], nullptr, e));
+                TRY(pointwise(cur, expand[i], nullptr, e));
             }
             const Tn& src = s.t != 1 ? e : cur;
             if (src.C != hidp) GYRE_FAIL(GYRE_ERR_INVALID, "mlsd: internal shape mismatch");
@@ -196,7 +172,7 @@ struct gyre_mlsd {
             if (!dry) TRY(launch_mlsd_dw(st, src.p, B, h, w, hidp, dw[i].w, dw[i].bias, s.stride, s.t != 1, d.p));
             if (s.t != 1) ex.free(e);
             TRY(ex.alloc(o, B, ho, wo, proj[i].f.o_pad));
-            TRY(lin(d, proj[i], res ? &cur : nullptr, o));
+            TRY(pointwise(d, proj[i], res ? &cur : nullptr, o));
             ex.free(d);
             if (tap_of(i) < 0) ex.free(cur);                      // (cur is features[i]; a tap stays until its decoder block)
             cur = o; h = ho; w = wo;
@@ -222,7 +198,7 @@ struct gyre_mlsd {
         ex.free(t1);
         TRY(relu(t2));
         TRY(ex.alloc(t3, t2.B, t2.H, t2.W, 16));
-        TRY(lin(t2, c3.w, c3.b, 64, 16, nullptr, at(t3), 16));
+        TRY(linear(t2, c3, nullptr, t3));
         ex.free(t2);
         if (!dry) {
             if (!out) GYRE_FAIL(GYRE_ERR_INVALID, "mlsd: null output buffer");
@@ -233,23 +209,10 @@ struct gyre_mlsd {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(mlsd)
+
 extern "C" {
 
-int gyre_mlsd_create(const gyre_mlsd_cfg* cfg, int device, gyre_mlsd** out) { return handle_create(cfg, device, out); }
-void gyre_mlsd_destroy(gyre_mlsd* h) { delete h; }
-int gyre_mlsd_num_params(const gyre_mlsd* h) { return handle_num_params(h); }
-const char* gyre_mlsd_param_key(const gyre_mlsd* h, int i) { return handle_param_key(h, i); }
-int gyre_mlsd_set_weight(gyre_mlsd* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_mlsd_finalize(gyre_mlsd* h, void* st) {
-    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
-    return h->finalize((hipStream_t)st);
-}
-size_t gyre_mlsd_workspace_bytes(gyre_mlsd* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_mlsd_forward(gyre_mlsd* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "mlsd", st, img, idt, B, H, W, ws, wsb, out, odt);
-}
 
 // ---- test hooks of kernels_mlsd.hip ----
 int gyre_op_mlsd_fold(void* st, const gyre_mlsd_fold_args* g) {

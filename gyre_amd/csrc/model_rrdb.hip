@@ -16,7 +16,8 @@
 //   generic  launch_gemm (the planner's tile kernels) with bias only, then k_rdb_epilogue in place over the written slice
 //   fused    k_rdb_conv (kernels_rdb.hip): one launch, the epilogue applied to the fp32 accumulators, one rounding
 // auto takes the fused kernel for the shape groups of RDB_AUTO_MASK: where it measured faster (profiles/upscaler_time.json).
-// The weight record (UpConv) is the one of model_upscaler.h; the graph itself shares nothing with the window transformers.
+// The weight record (UpConv), its registration, the generic path's planner convolution (into a channel slice) and the C ABI shell are
+// ImageGraph's (model_upscaler.h); run() takes no BatchInvariantScope, unlike the other graphs on that base.
 #include "model_upscaler.h"
 
 namespace {
@@ -40,23 +41,15 @@ constexpr int RDB_AUTO_MASK = 0x1f;
 constexpr int RDB_PATH_TUNING = 0x100;     // gyre_rrdb_set_path(0x100 | mask): fused exactly for the groups of the mask
 }  // namespace
 
-struct gyre_rrdb {
+struct gyre_rrdb : ImageGraph {
     gyre_rrdb_cfg cfg;
-    Store store;
-    Exec ex;
-    bool finalized = false;
     int path = 0;                  // 0 auto, 1 generic, 2 fused, RDB_PATH_TUNING | group mask
     int r = 1, cin0 = 32;          // unshuffle factor and padded channels of the unshuffled image
     UpConv conv_first, conv_body, conv_up1, conv_up2, conv_hr, conv_last;
     std::vector<RDense> dense;     // 3 per RRDB
+    gyre_rrdb() : ImageGraph("rrdb") {}
 
-    void reg(const std::string& key, int cout, int cin, int cin_pad, UpConv& c) {
-        c.cin = cin_pad; c.cout = cout; c.rows = pad8(cout);
-        c.w = (bf16_t*)store.dmalloc((size_t)c.rows * 9 * cin_pad * 2, true);
-        store.add(key + ".weight", {cout, cin, 3, 3}, PK_CONV3, c.w, c.rows, cin_pad);
-        c.b = (float*)store.dmalloc((size_t)c.rows * 4, true);
-        store.add(key + ".bias", {cout}, PK_VEC, c.b);
-    }
+    void reg(const std::string& key, int cout, int cin, int cin_pad, UpConv& c) { ImageGraph::conv(key, cout, cin, 3, pad8(cout), cin_pad, PK_CONV3, c); }
     int build() {
         const gyre_rrdb_cfg& c = cfg;
         if (c.num_feat != 64 || c.num_grow_ch != 32)
@@ -66,7 +59,6 @@ struct gyre_rrdb {
         if (c.num_block < 1 || c.num_block > 64) GYRE_FAIL(GYRE_ERR_INVALID, "rrdb: num_block out of range");
         r = c.scale == 2 ? 2 : c.scale == 1 ? 4 : 1;
         cin0 = rdb_unshuffle_channels(c.num_in_ch, r);
-        ex.store = &store;
         reg("conv_first", 64, c.num_in_ch * r * r, cin0, conv_first);
         for (int i = 0; i < c.num_block; ++i)
             for (int j = 1; j <= 3; ++j) {
@@ -84,12 +76,9 @@ struct gyre_rrdb {
         reg("conv_up2", 64, 64, 64, conv_up2);
         reg("conv_hr", 64, 64, 64, conv_hr);
         reg("conv_last", c.num_out_ch, 64, 64, conv_last);
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
+        return check_allocs();
     }
 
-    // slice pointer; a dry run plans with aligned stand-ins of the same residue mod 256 (arena tensors are 256-byte aligned)
-    bf16_t* at(const Tn& t, int c0) const { return ex.arena.dry ? (bf16_t*)(uintptr_t)(4096 + 2 * c0) : t.p + c0; }
     bool fused(const UpConv& c, int Cin, int ups) const {
         if (path == 1 || path == 2) return path == 2;
         const int mask = path & RDB_PATH_TUNING ? path & 0x1f : RDB_AUTO_MASK;
@@ -110,14 +99,7 @@ struct gyre_rrdb {
             e.bias = c.b;
             return launch_rdb_conv(ex.st, x.p, x.C, Cin, x.B, x.H, x.W, ups, wd, NT, c.cout, out.p + c0, out.C, e);
         }
-        GemmParams p;
-        p.A = at(x, 0); p.lda = x.C; p.mode = GEMM_CONV3;
-        p.Hi = x.H; p.Wi = x.W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.stride = 1; p.pad = 1; p.ups = ups;
-        p.Hup = ups ? Ho : 0; p.Wup = ups ? Wo : 0;
-        p.W = c.w; p.K = 9 * Cin; p.N = c.rows; p.M = x.B * Ho * Wo;
-        p.bias = c.b; p.rows_per_sample = Ho * Wo;
-        p.out = at(out, c0); p.ldc = out.C; p.out_mode = OUT_BF16;
-        TRY(ex.run_gemm(p));
+        TRY(conv3(x, Cin, c, 1, 1, ups, nullptr, out, c0));
         if (ex.dry() || (e.alpha == 1.f && !e.act && !e.r1 && !e.r2)) return 0;
         e.bias = nullptr;                                   // (the GEMM added it)
         return launch_rdb_epilogue(ex.st, out.p + c0, out.C, c.cout, (size_t)x.B * Ho * Wo, e);
@@ -153,7 +135,7 @@ struct gyre_rrdb {
         const gyre_rrdb_cfg& c = cfg;
         if (B < 1 || H < r || W < r || H % r || W % r)
             GYRE_FAIL(GYRE_ERR_INVALID, "rrdb: H and W must be positive multiples of " + std::to_string(r) + " for scale " + std::to_string(c.scale));
-        ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
+        begin(dry, st, B, ws, wsb);
         const int h = H / r, w = W / r;
         Tn x0, feat, side, a, b;
         TRY(ex.alloc(x0, B, h, w, cin0));
@@ -206,26 +188,16 @@ struct gyre_rrdb {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(rrdb)
+
 extern "C" {
 
-int gyre_rrdb_create(const gyre_rrdb_cfg* cfg, int device, gyre_rrdb** out) { return handle_create(cfg, device, out); }
-void gyre_rrdb_destroy(gyre_rrdb* h) { delete h; }
-int gyre_rrdb_num_params(const gyre_rrdb* h) { return handle_num_params(h); }
-const char* gyre_rrdb_param_key(const gyre_rrdb* h, int i) { return handle_param_key(h, i); }
-int gyre_rrdb_set_weight(gyre_rrdb* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_rrdb_finalize(gyre_rrdb* h, void* st) { return handle_finalize(h); }
 int gyre_rrdb_set_path(gyre_rrdb* h, int path) {
     if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
     if ((path < 0 || path > 2) && (path & ~0x1f) != RDB_PATH_TUNING)
         GYRE_FAIL(GYRE_ERR_INVALID, "rrdb: path must be 0 (auto), 1 (generic), 2 (fused) or 0x100 | a mask of the five shape groups");
     h->path = path;
     return 0;
-}
-size_t gyre_rrdb_workspace_bytes(gyre_rrdb* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_rrdb_forward(gyre_rrdb* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "rrdb", st, img, idt, B, H, W, ws, wsb, out, odt);
 }
 
 int gyre_op_rdb_tile(int* th, int* tw) {

@@ -11,7 +11,7 @@
 //   stage out norm_i -> launch_nhwc_to_nchw into the caller's buffer: map i + 1
 //   merge     k_swinb_merge_ln (2 x 2 gather + LayerNorm over 4 C, written once) -> the bias-free 4 C -> 2 C reduction on the planner
 // The model_upscaler.h trunk does not fit (head dim 30 at a 32 pitch, padded widths, conv_first, one width for all layers), so this graph
-// stands beside it and shares only the planner scope and the handle shell.
+// stands beside it on the same base, ImageGraph: the weight registration, the planner linear, the dry-run pointer and the C ABI shell.
 //
 // finalize expands every block's relative-position table into the register order of k_win12_attn (launch_win12_bias), 81 KB per head.
 // The planner sees every launch as if its sample ran alone (BatchInvariantScope); the other kernels work per token or per window.
@@ -27,24 +27,14 @@ struct SwinbStage {
 };
 }  // namespace
 
-struct gyre_swinb {
+struct gyre_swinb : ImageGraph {
     gyre_swinb_cfg cfg;
-    Store store;
-    Exec ex;
-    bool finalized = false;
     float *pe_w = nullptr, *pe_b = nullptr, *pe_g = nullptr, *pe_n = nullptr;
     SwinbStage stage[4];
+    gyre_swinb() : ImageGraph("swinb") {}
 
-    void lin(const std::string& key, int O, int I, bool has_bias, UpLin& l) {
-        l.K = I; l.N = O;
-        l.w = (bf16_t*)store.dmalloc((size_t)O * I * 2, true);
-        store.add(key + ".weight", {O, I}, PK_MAT, l.w, O, I);
-        if (has_bias) store.vec(key + ".bias", O, &l.b);
-    }
-    void norm(const std::string& key, int C, float** g, float** b) {
-        store.vec(key + ".weight", C, g);
-        store.vec(key + ".bias", C, b);
-    }
+    // no padding anywhere: every width is a multiple of 32
+    void lin(const std::string& key, int O, int I, bool has_bias, UpLin& l) { ImageGraph::lin(key, O, I, O, I, has_bias, false, l); }
     int build() {
         const gyre_swinb_cfg& c = cfg;
         if (c.window_size != 12) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "swinb: window_size 12 is the only one built");
@@ -54,10 +44,8 @@ struct gyre_swinb {
             if (c.num_heads[i] != (c.embed_dim / 32) << i) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "swinb: head dim 32 with heads doubling per stage is built");
             if (c.depths[i] < 1 || c.depths[i] > 64) GYRE_FAIL(GYRE_ERR_INVALID, "swinb: depth out of range");
         }
-        ex.store = &store;
         const int E = c.embed_dim;
-        pe_w = (float*)store.dmalloc((size_t)E * 48 * 4, true);
-        store.add("patch_embed.proj.weight", {E, 3, 4, 4}, PK_TABLE_F32, pe_w);
+        pe_w = f32("patch_embed.proj.weight", {E, 3, 4, 4});
         store.vec("patch_embed.proj.bias", E, &pe_b);
         norm("patch_embed.norm", E, &pe_g, &pe_n);
         for (int i = 0; i < 4; ++i) {
@@ -68,8 +56,7 @@ struct gyre_swinb {
                 SwinbBlock b;
                 b.shift = (j & 1) ? 6 : 0;
                 norm(p + ".norm1", s.C, &b.g1, &b.b1);
-                b.table = (float*)store.dmalloc((size_t)529 * s.heads * 4, true);
-                store.add(p + ".attn.relative_position_bias_table", {529, s.heads}, PK_TABLE_F32, b.table);
+                b.table = f32(p + ".attn.relative_position_bias_table", {529, s.heads});
                 b.ebias = (float*)store.dmalloc((size_t)s.heads * 144 * 144 * 4, false);
                 lin(p + ".attn.qkv", 3 * s.C, s.C, true, b.qkv);
                 lin(p + ".attn.proj", s.C, s.C, true, b.proj);
@@ -85,8 +72,7 @@ struct gyre_swinb {
             }
         }
         for (int i = 0; i < 4; ++i) norm("norm" + std::to_string(i), stage[i].C, &stage[i].ng, &stage[i].nb);
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
+        return check_allocs();
     }
     int finalize(hipStream_t st) {
         TRY(store.finalize());
@@ -96,12 +82,6 @@ struct gyre_swinb {
         return 0;
     }
 
-    // a dry run plans with aligned stand-ins (arena tensors are 256-byte aligned)
-    bf16_t* at(const Tn& t) const { return ex.arena.dry ? (bf16_t*)(uintptr_t)4096 : t.p; }
-    int linear(const Tn& x, const UpLin& l, const Tn* res, Tn& out) {
-        if (x.C != l.K || out.C != l.N || (res && res->C != l.N)) GYRE_FAIL(GYRE_ERR_INVALID, "swinb: internal shape mismatch");
-        return ex.linear(at(x), x.C, nullptr, 0, 0, x.rows(), l.K, l.w, l.N, l.b, res ? at(*res) : nullptr, res ? res->C : 0, 0, at(out), out.C);
-    }
     int ln(const Tn& x, const float* g, const float* b, Tn& y) {
         if (ex.dry()) return 0;
         return launch_layernorm(ex.st, x.p, x.rows(), x.C, g, b, 1e-5f, y.p);
@@ -115,7 +95,7 @@ struct gyre_swinb {
         if ((size_t)B * h * w > 0x3fffffff / (4 * (size_t)cfg.embed_dim)) GYRE_FAIL(GYRE_ERR_INVALID, "swinb: image too large");
         if (!dry && !out) GYRE_FAIL(GYRE_ERR_INVALID, "swinb: null output buffer");
         BatchInvariantScope invariant;
-        ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
+        begin(dry, st, B, ws, wsb);
         const size_t osz = odt == 0 ? 4 : 2;
         char* op = (char*)out;
         Tn a;
@@ -166,23 +146,10 @@ struct gyre_swinb {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(swinb)
+
 extern "C" {
 
-int gyre_swinb_create(const gyre_swinb_cfg* cfg, int device, gyre_swinb** out) { return handle_create(cfg, device, out); }
-void gyre_swinb_destroy(gyre_swinb* h) { delete h; }
-int gyre_swinb_num_params(const gyre_swinb* h) { return handle_num_params(h); }
-const char* gyre_swinb_param_key(const gyre_swinb* h, int i) { return handle_param_key(h, i); }
-int gyre_swinb_set_weight(gyre_swinb* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_swinb_finalize(gyre_swinb* h, void* st) {
-    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
-    return h->finalize((hipStream_t)st);
-}
-size_t gyre_swinb_workspace_bytes(gyre_swinb* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_swinb_forward(gyre_swinb* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "swinb", st, img, idt, B, H, W, ws, wsb, out, odt);
-}
 
 // ---- test hooks of kernels_swinb.hip ----
 int gyre_op_win12_bias(void* st, const float* table, int heads, float* out) { return launch_win12_bias((hipStream_t)st, table, heads, out); }

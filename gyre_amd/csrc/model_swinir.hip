@@ -129,20 +129,10 @@ struct gyre_swinir : WinTrunk {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(swinir)
+
 extern "C" {
 
-int gyre_swinir_create(const gyre_swinir_cfg* cfg, int device, gyre_swinir** out) { return handle_create(cfg, device, out); }
-void gyre_swinir_destroy(gyre_swinir* h) { delete h; }
-int gyre_swinir_num_params(const gyre_swinir* h) { return handle_num_params(h); }
-const char* gyre_swinir_param_key(const gyre_swinir* h, int i) { return handle_param_key(h, i); }
-int gyre_swinir_set_weight(gyre_swinir* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_swinir_finalize(gyre_swinir* h, void* st) { return handle_finalize(h); }
-size_t gyre_swinir_workspace_bytes(gyre_swinir* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_swinir_forward(gyre_swinir* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "swinir", st, img, idt, B, H, W, ws, wsb, out, odt);
-}
 
 int gyre_op_win_bias(void* st, const float* table, int heads, float* out) { return launch_win_bias((hipStream_t)st, table, heads, out); }
 int gyre_op_win_attn(void* st, const void* qkv, int ld_qkv, void* o, int ld_o, const float* bias, int B, int H, int W, int heads, int shift) {

@@ -20,14 +20,14 @@
 // finalize folds each BatchNorm into the 1x1 convolution it feeds (launch_uf_fold: fp32 from fp32 staging copies of the raw parameters,
 // one rounding to storage; exact, since the norm feeds the convolution directly) and transposes the depthwise weights to [taps][C] fp32.
 // The planner sees every launch as if its sample ran alone (BatchInvariantScope); the other kernels work per pixel, tile or sample.
+// The weight registration, the planner calls with their shape checks and the C ABI shell are ImageGraph's (model_upscaler.h).
 #include "model_upscaler.h"
 
 namespace {
-struct UfBn { float *g, *b, *m, *v; };
 struct UfBlock {
     float *pe_raw, *pe_b, *pe_w;                           // pos_embed [C][1][3][3] staged, its bias, [9][C]
     // CBlock
-    UfBn bn1, bn2;
+    Bn bn1, bn2;
     float *c1_raw, *c1_b, *b1f, *dw_raw, *dw_b, *dw_w, *f1_raw, *f1_b;
     bf16_t* w1f;
     UpLin conv2;
@@ -45,37 +45,15 @@ struct UfStage {
 };
 }  // namespace
 
-struct gyre_uniformer {
+struct gyre_uniformer : ImageGraph {
     gyre_uniformer_cfg cfg;
-    Store store;
-    Exec ex;
-    bool finalized = false;
     UfStage stage[4];
+    gyre_uniformer() : ImageGraph("uniformer") {}
 
-    float* stage_f32(const std::string& key, std::vector<int64_t> shape) {
-        size_t n = 1;
-        for (auto d : shape) n *= (size_t)d;
-        float* p = (float*)store.dmalloc(n * 4, true);
-        store.add(key, std::move(shape), PK_TABLE_F32, p);
-        return p;
-    }
-    void lin(const std::string& key, int O, int I, bool conv1x1, UpLin& l) {
-        l.K = I; l.N = O;
-        l.w = (bf16_t*)store.dmalloc((size_t)O * I * 2, true);
-        store.add(key + ".weight", conv1x1 ? std::vector<int64_t>{O, I, 1, 1} : std::vector<int64_t>{O, I}, PK_MAT, l.w, O, I);
-        store.vec(key + ".bias", O, &l.b);
-    }
-    void norm(const std::string& key, int C, float** g, float** b) {
-        store.vec(key + ".weight", C, g);
-        store.vec(key + ".bias", C, b);
-    }
-    void bnorm(const std::string& key, int C, UfBn& n) {
-        norm(key, C, &n.g, &n.b);
-        store.vec(key + ".running_mean", C, &n.m);
-        store.vec(key + ".running_var", C, &n.v);
-    }
+    // no padding anywhere (every width is a multiple of 64), a bias everywhere
+    void lin(const std::string& key, int O, int I, bool conv1x1, UpLin& l) { ImageGraph::lin(key, O, I, O, I, true, conv1x1, l); }
     void pos_embed(const std::string& p, int C, UfBlock& b) {
-        b.pe_raw = stage_f32(p + ".pos_embed.weight", {C, 1, 3, 3});
+        b.pe_raw = f32(p + ".pos_embed.weight", {C, 1, 3, 3});
         store.vec(p + ".pos_embed.bias", C, &b.pe_b);
         b.pe_w = (float*)store.dmalloc((size_t)9 * C * 4, false);
     }
@@ -88,7 +66,6 @@ struct gyre_uniformer {
             if (c.embed_dim[i] < 64 || c.embed_dim[i] % 64 || c.embed_dim[i] > 1024) GYRE_FAIL(GYRE_ERR_UNSUPPORTED, "uniformer: widths must be multiples of 64, at most 1024");
             if (c.layers[i] < 1 || c.layers[i] > 64) GYRE_FAIL(GYRE_ERR_INVALID, "uniformer: 1 to 64 blocks per stage");
         }
-        ex.store = &store;
         for (int i = 0; i < 4; ++i) {
             UfStage& s = stage[i];
             s.C = c.embed_dim[i]; s.heads = s.C / 64; s.patch = i ? 2 : 4;
@@ -110,16 +87,16 @@ struct gyre_uniformer {
                 pos_embed(p, C, b);
                 if (i < 2) {
                     bnorm(p + ".norm1", C, b.bn1);
-                    b.c1_raw = stage_f32(p + ".conv1.weight", {C, C, 1, 1});
+                    b.c1_raw = f32(p + ".conv1.weight", {C, C, 1, 1});
                     store.vec(p + ".conv1.bias", C, &b.c1_b);
                     b.w1f = (bf16_t*)store.dmalloc((size_t)C * C * 2, false);
                     b.b1f = (float*)store.dmalloc((size_t)C * 4, false);
                     lin(p + ".conv2", C, C, true, b.conv2);
-                    b.dw_raw = stage_f32(p + ".attn.weight", {C, 1, 5, 5});
+                    b.dw_raw = f32(p + ".attn.weight", {C, 1, 5, 5});
                     store.vec(p + ".attn.bias", C, &b.dw_b);
                     b.dw_w = (float*)store.dmalloc((size_t)25 * C * 4, false);
                     bnorm(p + ".norm2", C, b.bn2);
-                    b.f1_raw = stage_f32(p + ".mlp.fc1.weight", {4 * C, C, 1, 1});
+                    b.f1_raw = f32(p + ".mlp.fc1.weight", {4 * C, C, 1, 1});
                     store.vec(p + ".mlp.fc1.bias", 4 * C, &b.f1_b);
                     b.fc1.K = C; b.fc1.N = 4 * C;
                     b.fc1.w = (bf16_t*)store.dmalloc((size_t)4 * C * C * 2, false);
@@ -137,8 +114,7 @@ struct gyre_uniformer {
             }
             norm("norm" + std::to_string(i + 1), C, &s.ng, &s.nb);
         }
-        for (void* a : store.allocs) if (!a) GYRE_FAIL(GYRE_ERR_HIP, "hipMalloc failed");
-        return 0;
+        return check_allocs();
     }
     int finalize(hipStream_t st) {
         TRY(store.finalize());
@@ -156,12 +132,6 @@ struct gyre_uniformer {
         return 0;
     }
 
-    // a dry run plans with aligned stand-ins (arena tensors are 256-byte aligned)
-    bf16_t* at(const Tn& t) const { return ex.arena.dry ? (bf16_t*)(uintptr_t)4096 : t.p; }
-    int linear(const Tn& x, const UpLin& l, const Tn* res, Tn& out) {
-        if (x.C != l.K || out.C != l.N || (res && res->C != l.N)) GYRE_FAIL(GYRE_ERR_INVALID, "uniformer: internal shape mismatch");
-        return ex.linear(at(x), x.C, nullptr, 0, 0, x.rows(), l.K, l.w, l.N, l.b, res ? at(*res) : nullptr, res ? res->C : 0, 0, at(out), out.C);
-    }
     int ln(const Tn& x, const float* g, const float* b, float eps, Tn& y) {
         if (ex.dry()) return 0;
         return launch_layernorm(ex.st, x.p, x.rows(), x.C, g, b, eps, y.p);
@@ -182,7 +152,7 @@ struct gyre_uniformer {
             if ((size_t)B * (h >> i) * (w >> i) > 0x3fffffff / (4 * (size_t)stage[i].C)) GYRE_FAIL(GYRE_ERR_INVALID, "uniformer: image too large");
         if (!dry && !out) GYRE_FAIL(GYRE_ERR_INVALID, "uniformer: null output buffer");
         BatchInvariantScope invariant;
-        ex.arena.reset((char*)ws, wsb, dry); ex.st = st; ex.batch = B; ex.cs_unit = 0;
+        begin(dry, st, B, ws, wsb);
         const size_t osz = odt == 0 ? 4 : 2;
         char* op = (char*)out;
         Tn a;                                                                 // the residual stream of the stage
@@ -223,7 +193,7 @@ struct gyre_uniformer {
                     TRY(mlp(b, v, v, hdn, a));
                 } else {
                     TRY(ln(u, b.g1, b.b1, 1e-6f, nrm));
-                    TRY(ex.linear(at(nrm), C, nullptr, 0, 0, B * N, C, b.qkv.w, 2 * C, b.qkv.b, nullptr, 0, 0, at(qk), 2 * C));
+                    TRY(linear_to(nrm, b.qkv.w, b.qkv.b, C, 2 * C, nullptr, at(qk), 2 * C));
                     TRY(ex.linear_t(nrm.p, C, B * N, C, b.qkv.w + (size_t)2 * C * C, C, b.qkv.b + 2 * C, N, ldvt, vt.p));
                     if (!dry) {
                         AttnParams ap;
@@ -247,23 +217,10 @@ struct gyre_uniformer {
     }
 };
 
+GYRE_IMAGE_MODEL_ABI(uniformer)
+
 extern "C" {
 
-int gyre_uniformer_create(const gyre_uniformer_cfg* cfg, int device, gyre_uniformer** out) { return handle_create(cfg, device, out); }
-void gyre_uniformer_destroy(gyre_uniformer* h) { delete h; }
-int gyre_uniformer_num_params(const gyre_uniformer* h) { return handle_num_params(h); }
-const char* gyre_uniformer_param_key(const gyre_uniformer* h, int i) { return handle_param_key(h, i); }
-int gyre_uniformer_set_weight(gyre_uniformer* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* st) {
-    return handle_set_weight(h, key, p, dtype, shape, ndim, st);
-}
-int gyre_uniformer_finalize(gyre_uniformer* h, void* st) {
-    if (!h) GYRE_FAIL(GYRE_ERR_INVALID, "null handle");
-    return h->finalize((hipStream_t)st);
-}
-size_t gyre_uniformer_workspace_bytes(gyre_uniformer* h, int B, int H, int W) { return handle_workspace_bytes(h, B, H, W); }
-int gyre_uniformer_forward(gyre_uniformer* h, void* st, const void* img, int idt, int B, int H, int W, void* ws, size_t wsb, void* out, int odt) {
-    return handle_forward(h, "uniformer", st, img, idt, B, H, W, ws, wsb, out, odt);
-}
 
 // ---- test hooks of kernels_uniformer.hip ----
 int gyre_op_uf_local(void* st, const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, const void* w1, const float* b1,

@@ -36,6 +36,8 @@ are not built and stay host models.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import _lib
@@ -45,6 +47,61 @@ from .modules import _NativeModule
 from .upscaler import MODELS_PATTERN, _NativeUpscaler, _only_match, _read_state_dict
 from .weights import (hed_param_shapes, lineart_param_shapes, mlsd_is_buffer, mlsd_param_shapes, swinb_is_buffer, swinb_param_shapes,
                       uniformer_is_buffer, uniformer_param_shapes)
+
+
+def _load_weights(model, path, torch_dtype, allow_patterns, ignore_patterns, prefix=None, unwrap=None):
+    """What every loader below does behind its constructor: ``path`` is a state-dict file or a folder that holds exactly one (after the
+    allow / ignore filters); ``unwrap``: the key a checkpoint may keep its weights under; ``prefix``: only the keys under ``prefix.``
+    are taken, without it.  The load is strict; the model comes back in ``torch_dtype`` (when given) and in eval mode."""
+    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
+    sd = _read_state_dict(file)
+    if unwrap is not None:
+        sd = sd.get(unwrap, sd)
+    if prefix is not None:
+        sd = {k[len(prefix) + 1:]: v for k, v in sd.items() if k.startswith(prefix + ".")}
+    model.load_state_dict(sd)
+    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+
+
+def _bn_buffer_dtype(leaf):
+    """dtype of a BatchNorm buffer: ``num_batches_tracked`` is the one integer"""
+    return torch.long if leaf == "num_batches_tracked" else torch.float32
+
+
+class _HintPipeline:
+    """What the pipelines below share: the module, ``to``, ``pipeline_modules`` and the way a sample reaches the module."""
+
+    def __init__(self, module):
+        self.module = module
+
+    def to(self, device):
+        self.module.to(device)
+
+    def pipeline_modules(self):
+        return [("module", self.module)]
+
+    def _sample(self, tensor: torch.Tensor, dtype=None):
+        """(the tensor with a batch axis and three channels, the same on the module's device in ``dtype`` - the module's own by default)"""
+        tensor = normalise_tensor(tensor, 3)     # a batch axis for [C, H, W]; 1 or 2 channels repeat channel 0, 4 or more are cut to 3
+        p = next(self.module.parameters())
+        return tensor, tensor.to(p.device, dtype or p.dtype)
+
+
+class _NativeBackbone(_NativeUpscaler):
+    """A backbone whose native call fills one flat buffer with several feature maps: the family names their shapes (``map_shapes``),
+    ``forward`` returns the maps as views of the buffer."""
+
+    def out_shape(self, shape):
+        return (sum(b * c * h * w for b, c, h, w in self.map_shapes(shape)),)
+
+    def forward(self, x: torch.Tensor):
+        flat = super().forward(x)
+        maps, at = [], 0
+        for s in self.map_shapes(x.shape):
+            n = s[0] * s[1] * s[2] * s[3]
+            maps.append(flat[at:at + n].view(s))
+            at += n
+        return tuple(maps)
 
 
 class GyreHipDrawingGenerator(_NativeUpscaler):
@@ -84,31 +141,16 @@ def load_drawing_generator(path: str, torch_dtype=None, allow_patterns=None, ign
     """The generator with the weights of ``path``: a ``*.safetensors`` / ``*.pt`` / ``*.pth`` state dict, or a folder that holds
     exactly one (after the allow / ignore filters) - the layout of the reference's ``hinters-lineart-*`` model folders.  The load
     is strict."""
-    import os
-    model = GyreHipDrawingGenerator(3, 1, n_residual_blocks, sigmoid)
-    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
-    model.load_state_dict(_read_state_dict(file))
-    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+    return _load_weights(GyreHipDrawingGenerator(3, 1, n_residual_blocks, sigmoid), path, torch_dtype, allow_patterns, ignore_patterns)
 
 
-class GyreInformativeDrawingPipeline:
+class GyreInformativeDrawingPipeline(_HintPipeline):
     """The reference's ``InformativeDrawingPipeline``: ``pipeline(tensor) -> tensor``, a float image [B, C, H, W] or [C, H, W] in
     [0, 1] -> its line drawing [B, 1, Ho, Wo], white lines on black, on the input's device and in its dtype."""
 
-    def __init__(self, module):
-        self.module = module
-
-    def to(self, device):
-        self.module.to(device)
-
-    def pipeline_modules(self):
-        return [("module", self.module)]
-
     @torch.no_grad()
     def __call__(self, tensor: torch.Tensor) -> torch.Tensor:
-        tensor = normalise_tensor(tensor, 3)     # a batch axis for [C, H, W]; 1 or 2 channels repeat channel 0, 4 or more are cut to 3
-        p = next(self.module.parameters())
-        sample = tensor.to(p.device, p.dtype)
+        tensor, sample = self._sample(tensor)
         result = self.module(sample).clamp(0, 1)
         result = 1 - result                     # white on a black background, what the ControlNets were trained on
         return result.to(tensor.device, tensor.dtype)
@@ -153,11 +195,7 @@ def load_hed(path: str, torch_dtype=None, allow_patterns=None, ignore_patterns=N
     """The detector with the weights of ``path``: a ``*.safetensors`` / ``*.pt`` / ``*.pth`` state dict, or a folder that holds
     exactly one (after the allow / ignore filters) - the layout of the reference's ``hinters-hed`` model folders.  The load is
     strict."""
-    import os
-    model = GyreHipHED()
-    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
-    model.load_state_dict(_read_state_dict(file))
-    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+    return _load_weights(GyreHipHED(), path, torch_dtype, allow_patterns, ignore_patterns)
 
 
 def normalise_range(tensor: torch.Tensor) -> torch.Tensor:
@@ -168,24 +206,13 @@ def normalise_range(tensor: torch.Tensor) -> torch.Tensor:
     return (tensor - dmin) / (dmax - dmin)
 
 
-class GyreHedPipeline:
+class GyreHedPipeline(_HintPipeline):
     """The reference's ``HedPipeline``: ``pipeline(tensor) -> tensor``, a float image [B, C, H, W] or [C, H, W] in [0, 1] -> its
     fused edge map [B, 1, H, W] stretched to [0, 1] per sample, on the input's device and in its dtype."""
 
-    def __init__(self, module):
-        self.module = module
-
-    def to(self, device):
-        self.module.to(device)
-
-    def pipeline_modules(self):
-        return [("module", self.module)]
-
     @torch.no_grad()
     def __call__(self, tensor: torch.Tensor) -> torch.Tensor:
-        tensor = normalise_tensor(tensor, 3)
-        p = next(self.module.parameters())
-        sample = tensor.to(p.device, p.dtype)
+        tensor, sample = self._sample(tensor)
         mean = torch.tensor(IMAGENET_MEAN).to(sample).view(1, 3, 1, 1)
         sample = (sample - mean)[:, [2, 1, 0]] * 255         # the RGB mean comes off first, then BGR at 0 .. 255
         result = normalise_range(self.module(sample)[-1])
@@ -204,7 +231,7 @@ class GyreHipMLSD(_NativeUpscaler):
     _param_shapes = staticmethod(mlsd_param_shapes)
     _in_key, _scale_key = "input_nc", None
     _is_buffer = staticmethod(mlsd_is_buffer)
-    _buffer_dtype = staticmethod(lambda leaf: torch.long if leaf == "num_batches_tracked" else torch.float32)
+    _buffer_dtype = staticmethod(_bn_buffer_dtype)
 
     def __init__(self, **kw):
         _NativeModule.__init__(self)                 # (the reference's constructor has no arguments)
@@ -226,11 +253,7 @@ class GyreHipMLSD(_NativeUpscaler):
 def load_mlsd(path: str, torch_dtype=None, allow_patterns=None, ignore_patterns=None) -> GyreHipMLSD:
     """The detector with the weights of ``path``: a ``*.safetensors`` / ``*.pt`` / ``*.pth`` state dict, or a folder that holds
     exactly one (after the allow / ignore filters).  The load is strict."""
-    import os
-    model = GyreHipMLSD()
-    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
-    model.load_state_dict(_read_state_dict(file))
-    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+    return _load_weights(GyreHipMLSD(), path, torch_dtype, allow_patterns, ignore_patterns)
 
 
 def mlsd_decode(tp: torch.Tensor, size, input_size: int, score_threshold: float = 0.1, distance_threshold: float = 0.1, top_k: int = 200):
@@ -277,7 +300,7 @@ def mlsd_rasterise(lines: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return img
 
 
-class GyreMlsdPipeline:
+class GyreMlsdPipeline(_HintPipeline):
     """``pipeline(tensor) -> tensor``: a float image [B, C, H, W] or [C, H, W] in [0, 1] -> its straight-line drawing [B, 1, H, W],
     white lines on black, on the input's device and in its dtype; ``pipeline.lines(tensor)`` -> the segments themselves, a list of
     [n_i, 5] fp32 tensors (x0, y0, x1, y1, score) in image pixels.
@@ -292,25 +315,18 @@ class GyreMlsdPipeline:
             raise ValueError(f"input_size must be at least 16 with (input_size // 2) % 8 == 0, got {input_size}")
         if top_k < 1:
             raise ValueError(f"top_k must be at least 1, got {top_k}")
-        self.module, self.input_size, self.top_k = module, int(input_size), int(top_k)
+        super().__init__(module)
+        self.input_size, self.top_k = int(input_size), int(top_k)
         self.score_threshold, self.distance_threshold = float(score_threshold), float(distance_threshold)
-
-    def to(self, device):
-        self.module.to(device)
-
-    def pipeline_modules(self):
-        return [("module", self.module)]
 
     @torch.no_grad()
     def _lines(self, tensor: torch.Tensor):
-        tensor = normalise_tensor(tensor, 3)
-        p = next(self.module.parameters())
+        tensor, rgb = self._sample(tensor, torch.float32)          # (the resampling runs in fp32, whatever the module's dtype)
         H, W = tensor.shape[2:]
-        rgb = tensor.to(p.device, torch.float32)
         if (H, W) != (self.input_size, self.input_size):
             rgb = torch.nn.functional.interpolate(rgb, size=(self.input_size, self.input_size), mode="bilinear", antialias=True,
                                                   align_corners=False)
-        sample = torch.cat([2 * rgb - 1, torch.full_like(rgb[:, :1], 1 / 127.5 - 1)], 1).to(p.dtype)
+        sample = torch.cat([2 * rgb - 1, torch.full_like(rgb[:, :1], 1 / 127.5 - 1)], 1).to(next(self.module.parameters()).dtype)
         tp = self.module(sample).float()
         return tensor, mlsd_decode(tp, (H, W), self.input_size, self.score_threshold, self.distance_threshold, self.top_k)
 
@@ -325,7 +341,7 @@ class GyreMlsdPipeline:
 
 
 # ---- Swin-B backbone of InSPyReNet ------------------------------------------------------------------------------------------------------
-class GyreHipSwinB(_NativeUpscaler):
+class GyreHipSwinB(_NativeBackbone):
     """Drop-in for the reference's ``SwinB(pretrained=False)``, the backbone module ``InSPyReNet(backbone, ...)`` takes:
     ``forward(x) -> tuple`` of five contiguous NCHW tensors, the normed patch embedding [B, C, ceil(H / 4), ceil(W / 4)] and the four
     stage outputs at C, 2 C, 4 C, 8 C channels, each stage half the size of the one before (rounded up) - 128, 128, 256, 512, 1024
@@ -362,38 +378,21 @@ class GyreHipSwinB(_NativeUpscaler):
             h, w = -(-h // 2), -(-w // 2)
         return shapes
 
-    def out_shape(self, shape):
-        return (sum(b * c * h * w for b, c, h, w in self.map_shapes(shape)),)
-
     def _padding(self, H, W):
         if H < 4 or W < 4:
             raise ValueError(f"the Swin-B backbone takes images of at least 4 x 4 pixels, got {H} x {W}")
         return 0, 0
-
-    def forward(self, x: torch.Tensor):
-        flat = super().forward(x)
-        maps, at = [], 0
-        for s in self.map_shapes(x.shape):
-            n = s[0] * s[1] * s[2] * s[3]
-            maps.append(flat[at:at + n].view(s))
-            at += n
-        return tuple(maps)
 
 
 def load_inspyrenet_backbone(path: str, torch_dtype=None, allow_patterns=None, ignore_patterns=None, **kw) -> GyreHipSwinB:
     """The backbone with the ``backbone.`` weights of the InSPyReNet checkpoint at ``path``: a ``*.safetensors`` / ``*.pt`` / ``*.pth``
     state dict, or a folder that holds exactly one (after the allow / ignore filters) - the layout of the reference's
     ``background-removal`` model folders.  The head's keys are left to the caller's host module; the backbone's load is strict."""
-    import os
-    model = GyreHipSwinB(**kw)
-    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
-    sd = _read_state_dict(file)
-    model.load_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")})
-    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+    return _load_weights(GyreHipSwinB(**kw), path, torch_dtype, allow_patterns, ignore_patterns, prefix="backbone")
 
 
 # ---- UniFormer backbone of the segmentation annotator ---------------------------------------------------------------------------------
-class GyreHipUniFormer(_NativeUpscaler):
+class GyreHipUniFormer(_NativeBackbone):
     """Drop-in for the reference's ``UniFormer(...)`` (windows=False, hybrid=False), the backbone of the mmseg segmentor behind
     ``hinters-uniformer``: ``forward(x) -> tuple`` of four contiguous NCHW tensors, ``norm1 .. norm4`` of the four stages at
     ``embed_dim`` channels (64, 128, 320, 512) and 1/4, 1/8, 1/16, 1/32 of the image (floor division at every step).  x NCHW
@@ -408,7 +407,7 @@ class GyreHipUniFormer(_NativeUpscaler):
     _param_shapes = staticmethod(uniformer_param_shapes)
     _in_key, _scale_key = "in_chans", None
     _is_buffer = staticmethod(uniformer_is_buffer)
-    _buffer_dtype = staticmethod(lambda leaf: torch.long if leaf == "num_batches_tracked" else torch.float32)
+    _buffer_dtype = staticmethod(_bn_buffer_dtype)
 
     def __init__(self, **kw):
         _NativeModule.__init__(self)                 # (the reference's constructor takes keywords, not a configuration mapping)
@@ -431,22 +430,10 @@ class GyreHipUniFormer(_NativeUpscaler):
             h, w = h // 2, w // 2
         return shapes
 
-    def out_shape(self, shape):
-        return (sum(b * c * h * w for b, c, h, w in self.map_shapes(shape)),)
-
     def _padding(self, H, W):
         if H < 32 or W < 32:
             raise ValueError(f"the UniFormer backbone takes images of at least 32 x 32 pixels, got {H} x {W}")
         return 0, 0
-
-    def forward(self, x: torch.Tensor):
-        flat = super().forward(x)
-        maps, at = [], 0
-        for s in self.map_shapes(x.shape):
-            n = s[0] * s[1] * s[2] * s[3]
-            maps.append(flat[at:at + n].view(s))
-            at += n
-        return tuple(maps)
 
 
 def load_uniformer_backbone(path: str, torch_dtype=None, allow_patterns=None, ignore_patterns=None, **kw) -> GyreHipUniFormer:
@@ -454,10 +441,4 @@ def load_uniformer_backbone(path: str, torch_dtype=None, allow_patterns=None, ig
     ``*.pth`` file (an mmcv checkpoint keeps its weights under ``state_dict``), or a folder that holds exactly one (after the allow /
     ignore filters) - the layout of the reference's ``hinters-uniformer`` model folder.  The decode and auxiliary heads' keys are left to
     the caller's host module; the backbone's load is strict."""
-    import os
-    model = GyreHipUniFormer(**kw)
-    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
-    sd = _read_state_dict(file)
-    sd = sd.get("state_dict", sd)
-    model.load_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")})
-    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+    return _load_weights(GyreHipUniFormer(**kw), path, torch_dtype, allow_patterns, ignore_patterns, prefix="backbone", unwrap="state_dict")

@@ -41,7 +41,7 @@ _UNSHUFFLE = {4: 1, 2: 2, 1: 4}          # model scale -> pixel-unshuffle factor
 
 
 class _NativeUpscaler(_NativeModule):
-    """What the three upscaler shells share: the configuration merge, the parameter tree with the family's buffers, the workspace
+    """What every image-in / image-out model shell shares (the three upscalers here, the hinters and backbones of hinters.py): the configuration merge, the parameter tree with the family's buffers, the workspace
     query and the native call (gyre_{kind}_workspace_bytes / gyre_{kind}_forward).  A family names its configuration
     (``_make_config``, ``_param_shapes``, the keys of its channel count and scale - ``_scale_key = None``: the output has the input's scale), its buffers (``_is_buffer``, ``_buffer_dtype``) and
     its size rule (``_padding``), and builds its C configuration (``_c_cfg``)."""
