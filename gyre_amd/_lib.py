@@ -135,6 +135,11 @@ class UniFormerCfg(C.Structure):
                 ("qkv_bias", C.c_int32), ("windows", C.c_int32), ("hybrid", C.c_int32)]
 
 
+class BaeCfg(C.Structure):
+    """gyre_bae_cfg (include/gyre_hip.h)."""
+    _fields_ = [("num_features", C.c_int32), ("skip", C.c_int32 * 4), ("architecture", C.c_int32)]
+
+
 class MlsdFoldArgs(C.Structure):
     """gyre_mlsd_fold_args (include/gyre_hip.h): one launch of the BatchNorm fold, for tests."""
     _fields_ = [(n, C.c_void_p) for n in ("w", "conv_bias", "gamma", "beta", "mean", "var", "out", "bias")] + \
@@ -400,15 +405,19 @@ _SIGS = {
     "gyre_op_uf_gather_img": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "gyre_op_uf_fold": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
     "gyre_op_uf_taps": (_i, [_vp, _vp, _i, _i, _vp]),
+    "gyre_op_bae_refine": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "gyre_op_bae_refine_tile": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gyre_op_bae_up_concat": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i]),
     "gyre_op_seq_attn_max_len": (_i, [_i]),
     "gyre_op_seq_attn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
     "gyre_op_quick_gelu": (_i, [_vp, _vp, _sz]),
     "gyre_op_fuser_pool": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i]),
     "gyre_op_fuser_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _vp, _i]),
 }
-# the handle surface of the three upscaler families, of the three hinters and of the two backbones: image in, image(s) out
+# the handle surface of the three upscaler families, of the three hinters, of the two backbones and of the normal-map decoder: image
+# (or feature maps) in, image(s) out
 for _kind, _cfg in (("rrdb", RRDBCfg), ("swinir", SwinIRCfg), ("hat", HATCfg), ("lineart", LineartCfg), ("hed", HedCfg),
-                    ("mlsd", MlsdCfg), ("swinb", SwinBCfg), ("uniformer", UniFormerCfg)):
+                    ("mlsd", MlsdCfg), ("swinb", SwinBCfg), ("uniformer", UniFormerCfg), ("bae", BaeCfg)):
     _SIGS.update({f"gyre_{_kind}_create": (_i, [C.POINTER(_cfg), _i, C.POINTER(_vp)]),
                   f"gyre_{_kind}_destroy": (None, [_vp]),
                   f"gyre_{_kind}_num_params": (_i, [_vp]),

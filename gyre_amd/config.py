@@ -381,6 +381,41 @@ def uniformer_config(**kw) -> UniFormerConfig:
     return cfg
 
 
+class BaeConfig(_AttrDict):
+    """Configuration of the BAE surface-normal decoder - the ``args.architecture`` of the reference's ``Decoder`` constructor
+    (gyre/pipeline/hinters/baenormal/submodules/decoder.py) and the widths its layers hard-code: a mapping that also reads as
+    attributes."""
+
+
+# the widths Decoder.__init__ writes out: x_block4 / conv2 at 2048 channels, x_block0 .. x_block3 of tf_efficientnet_b5_ap
+_BAE_CTOR = dict(architecture="BN", num_features=2048, skip_features=(24, 40, 64, 176), sampling_ratio=0.4, importance_ratio=0.7)
+
+
+def bae_config(**kw) -> BaeConfig:
+    """Decoder()'s configuration under ``kw``, refused (NotImplementedError) outside what the native path builds: architecture "BN"
+    ("GN" - weight standardisation + GroupNorm - is not built), num_features a multiple of 512 from 512 to 4096 (the up blocks produce
+    / 2, / 4, / 8, / 16 of it and the last must stay a multiple of 32), four skip widths.  ``sampling_ratio`` / ``importance_ratio``
+    only steer the training-mode point sampling, which is not built; they are kept for the caller."""
+    unknown = sorted(set(kw) - set(_BAE_CTOR))
+    if unknown:
+        raise NotImplementedError(f"Decoder: {unknown} are not part of its configuration (a configuration of another model family?)")
+    cfg = BaeConfig(**{**_BAE_CTOR, **kw})
+    if cfg["architecture"] != "BN":
+        raise NotImplementedError(f"Decoder: architecture {cfg['architecture']!r} is outside the native path ('BN' is built; 'GN' is not)")
+    cfg["num_features"], cfg["skip_features"] = int(cfg["num_features"]), tuple(int(c) for c in cfg["skip_features"])
+    if cfg["num_features"] < 512 or cfg["num_features"] % 512 or cfg["num_features"] > 4096:
+        raise NotImplementedError(f"Decoder: num_features {cfg['num_features']} is outside the native path (multiples of 512, 512 to 4096)")
+    if len(cfg["skip_features"]) != 4 or any(not 1 <= c <= 4096 for c in cfg["skip_features"]):
+        raise NotImplementedError(f"Decoder: skip_features {cfg['skip_features']} is outside the native path (four widths of 1 to 4096)")
+    return cfg
+
+
+def bae_size_ok(n: int) -> bool:
+    """the sides of x_block0 the decoder takes: those at which the reference's own concatenations line up (x_block1 = 2 x_block2 and
+    x_block0 = 2 x_block1 under the encoder's ceil halving)"""
+    return n >= 4 and n % 4 == 0
+
+
 # the MobileNetV2 trunk of MLSD, cut after features[13]: (t, c, n, s) = expansion, width, repeats, stride of the first repeat
 MLSD_SETTING = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1))
 

@@ -377,6 +377,24 @@ int launch_uf_fold(hipStream_t st, const float* w, const float* b, const float* 
                    float eps, int O, int I, bf16_t* wout, float* bout);
 int launch_uf_taps(hipStream_t st, const float* w, int C, int T, float* out);       // [C][T] fp32 -> [T][C] fp32
 
+// ---- BAE normal-map decoder kernels (kernels_bae.hip) -----------------------------------
+// One refinement stage in one launch (arithmetic, roundings and the tile: header of kernels_bae.hip): out NCHW [B][4][2 Hs][2 Ws] fp32 =
+// [norm_normalize] MLP(bilinear x2, align_corners=True, of [x | p]); x NHWC [B][Hs][Ws] of CF channels in storage (pixel stride ldx),
+// p NCHW [B][4][Hs][Ws] fp32.  w1 [128][CF + 32] storage (columns CF .. CF + 3 the prediction's, the rest zero), w2 / w3 [128][128]
+// storage, w4 [4][128] fp32, b1 .. b3 [128], b4 [4] fp32.  out overlapping x or p: GYRE_ERR_INVALID; outside the domain:
+// GYRE_ERR_UNSUPPORTED; nothing written either way.
+int launch_bae_refine(hipStream_t st, const bf16_t* x, int ldx, const float* pred, int B, int Hs, int Ws, int CF, const bf16_t* w1,
+                      const float* b1, const bf16_t* w2, const float* b2, const bf16_t* w3, const float* b3, const float* w4, const float* b4,
+                      int normalize, float* out);
+void bae_refine_tile(int* th, int* tw);
+// y [B][H][W][ldo] storage: [0, C) = bilinear resize (align_corners=True, any size) of x NHWC [B][Hs][Ws] (pixel stride ldx),
+// [C, C + Cs) = skip NCHW [B][Cs][H][W] of skip_dtype, [C + Cs, ldo) = 0; C == 0: the NCHW -> NHWC entry alone
+int launch_bae_up_concat(hipStream_t st, const bf16_t* x, int B, int Hs, int Ws, int C, int ldx, const void* skip, int skip_dtype, int Cs,
+                         int H, int W, bf16_t* y, int ldo);
+// out NCHW [B][4][HW] fp32 = norm_normalize of the first four channels of x NHWC [B][HW] (pixel stride ldx)
+int launch_bae_norm8(hipStream_t st, const bf16_t* x, int ldx, int B, size_t HW, float* out);
+int launch_bae_exit(hipStream_t st, const float* x, size_t n, void* out, int dtype);      // fp32 -> a boundary dtype
+
 // ---- ControlNet element-wise ops (kernels_ctrl.hip) ----------------------------
 int launch_silu(hipStream_t st, bf16_t* x, size_t n);                      // x * sigmoid(x) in place, n % 8 == 0
 // out NCHW [out_B][C][HW] of a runtime dtype <- scale * f, f NHWC storage [B][HW][Cpad] (first C channels), samples [out_b0, out_b0 + B):

@@ -1,5 +1,6 @@
 """The hinters on the native path: model shells and pipelines of the line-art generator, of the HED edge detector and of the MLSD line
-detector, the Swin-B backbone of the InSPyReNet background remover and the UniFormer backbone of the segmentation annotator.
+detector, the Swin-B backbone of the InSPyReNet background remover, the UniFormer backbone of the segmentation annotator and the decoder
+of the BAE surface-normal estimator.
 
 The reference serves ``task: edge_detection`` engines (gyre/config/models/hinters.yaml) that turn a photo into the hint image a
 ControlNet or T2I adapter conditions on.  Three of them - ``hinters-lineart-anime``, ``-contour`` and ``-opensketch`` - are the
@@ -28,25 +29,33 @@ of its ``controlnet/mlsd`` hintsets:
                                                                                          local-relation stages, two global-attention
                                                                                          stages, four feature maps.  The mmseg UPerNet head,
                                                                                          ``MmsegPipeline`` and ``MmLoader`` stay host code
+  ``Decoder`` / ``NNET``           gyre/pipeline/hinters/baenormal/                       the decoder of ``hinters-baenormal`` behind the
+                                                                                         ``controlnet/normalbae`` hintsets: four
+                                                                                         UpSampleBN blocks and three fused refinement
+                                                                                         stages, well over 95 % of the network's arithmetic.
+                                                                                         The EfficientNet-B5 encoder (``torch.hub``) stays
+                                                                                         the host module the caller supplies
+  ``BaenormalPipeline``            gyre/pipeline/hinters/baenormal_pipeline.py            ImageNet mean / std, module, unit length, 0 .. 1
 
 The modules' parameters carry the reference's state-dict names, so its checkpoints load strictly; all compute happens in the HIP
-library (gyre_lineart_forward, gyre_hed_forward, gyre_mlsd_forward, gyre_swinb_forward, gyre_uniformer_forward) - there is no PyTorch
-fallback.  The other hinters (DexiNed, MiDaS / ZoeDepth, the mmpose models, ...), the InSPyReNet head and the segmenter's UPerNet head
-are not built and stay host models.
+library (gyre_lineart_forward, gyre_hed_forward, gyre_mlsd_forward, gyre_swinb_forward, gyre_uniformer_forward, gyre_bae_forward) -
+there is no PyTorch fallback.  The other hinters (DexiNed, MiDaS / ZoeDepth, the mmpose models, ...), the InSPyReNet head, the
+segmenter's UPerNet head and the normal estimator's encoder are not built and stay host models.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import torch
 
 from . import _lib
-from .config import hed_config, lineart_config, mlsd_config, mlsd_size_ok, swinb_config, uniformer_config
+from .config import bae_config, bae_size_ok, hed_config, lineart_config, mlsd_config, mlsd_size_ok, swinb_config, uniformer_config
 from .hints import normalise_tensor
 from .modules import _NativeModule
 from .upscaler import MODELS_PATTERN, _NativeUpscaler, _only_match, _read_state_dict
-from .weights import (hed_param_shapes, lineart_param_shapes, mlsd_is_buffer, mlsd_param_shapes, swinb_is_buffer, swinb_param_shapes,
-                      uniformer_is_buffer, uniformer_param_shapes)
+from .weights import (bae_is_buffer, bae_param_shapes, hed_param_shapes, lineart_param_shapes, mlsd_is_buffer, mlsd_param_shapes,
+                      swinb_is_buffer, swinb_param_shapes, uniformer_is_buffer, uniformer_param_shapes)
 
 
 def _load_weights(model, path, torch_dtype, allow_patterns, ignore_patterns, prefix=None, unwrap=None):
@@ -442,3 +451,134 @@ def load_uniformer_backbone(path: str, torch_dtype=None, allow_patterns=None, ig
     ignore filters) - the layout of the reference's ``hinters-uniformer`` model folder.  The decode and auxiliary heads' keys are left to
     the caller's host module; the backbone's load is strict."""
     return _load_weights(GyreHipUniFormer(**kw), path, torch_dtype, allow_patterns, ignore_patterns, prefix="backbone", unwrap="state_dict")
+
+
+# ---- BAE surface-normal estimator -------------------------------------------------------------------------------------------------------
+IMAGENET_STD = [0.229, 0.224, 0.225]
+
+
+class GyreHipBaeDecoder(_NativeUpscaler):
+    """Drop-in for the reference's ``Decoder(args)`` with ``args.architecture == "BN"``: ``forward(features, gt_norm_mask=None,
+    mode='test')`` takes the encoder's feature list, reads its entries 4, 5, 6, 8 and 11 (x_block0 .. x_block4) as the reference does
+    and returns the reference's triple ``([out_res8, out_res4, out_res2, out_res1], [out_res8, None, None, None], [None] * 4)``: four
+    contiguous [B, 4, h, w] tensors - unit normal and kappa - at 1/4 of x_block0's size doubling up to twice it, views of one flat
+    buffer in the module's dtype.  The sides of x_block0 must be multiples of 4, the sizes at which the reference's own concatenations
+    line up (a ValueError otherwise); ``mode='train'`` (uncertainty-guided point sampling) and architecture "GN" are refused with
+    NotImplementedError.  The parameters carry the reference's state-dict names in its order and the BatchNorm statistics are buffers
+    as there (``num_batches_tracked`` included), so the ``decoder.`` part of an NNET checkpoint loads strictly; the native handle folds
+    every BatchNorm into its convolution.  The handle, workspace and call machinery is the upscalers'."""
+
+    _kind = "bae"
+    _param_shapes = staticmethod(bae_param_shapes)
+    _in_key, _scale_key = "num_features", None
+    _is_buffer = staticmethod(bae_is_buffer)
+    _buffer_dtype = staticmethod(_bn_buffer_dtype)
+    BLOCKS = (4, 5, 6, 8, 11)                        # the encoder's feature-list entries the decoder reads
+
+    def __init__(self, architecture: str = "BN", **kw):
+        _NativeModule.__init__(self)                 # (the reference's constructor takes an args namespace, not a configuration mapping)
+        self._adopt(bae_config(architecture=getattr(architecture, "architecture", architecture), **kw))
+
+    def _c_cfg(self):
+        c, cfg = self.config, _lib.BaeCfg()
+        cfg.num_features, cfg.architecture = c.num_features, 0
+        for i, s in enumerate(c.skip_features):
+            cfg.skip[i] = s
+        return cfg
+
+    def block_shapes(self, B, H, W):
+        """The five input shapes for an x_block0 of H x W (the encoder's ceil halving)."""
+        shapes = []
+        for c in (*self.config.skip_features, self.config.num_features):
+            shapes.append((B, c, H, W))
+            H, W = -(-H // 2), -(-W // 2)
+        return shapes
+
+    def _padding(self, H, W):
+        if not (bae_size_ok(H) and bae_size_ok(W)):
+            raise ValueError(f"the BAE decoder takes an x_block0 whose sides are multiples of 4 (an image whose sides are multiples of 8), "
+                             f"got {H} x {W}")
+        return 0, 0
+
+    @torch.no_grad()
+    def forward(self, features, gt_norm_mask=None, mode="test"):
+        if mode != "test":
+            raise NotImplementedError(f"Decoder: mode {mode!r} is outside the native path (mode='test' is built; the training-mode point "
+                                      f"sampling is not)")
+        blocks = [features[i] for i in self.BLOCKS]
+        B, _, H, W = blocks[0].shape
+        self._padding(H, W)
+        want = self.block_shapes(B, H, W)
+        if [tuple(b.shape) for b in blocks] != want:
+            raise ValueError(f"expected feature maps of shapes {want}, got {[tuple(b.shape) for b in blocks]}")
+        dev = blocks[0].device
+        h = self._sync(dev)
+        dt = blocks[0].dtype if blocks[0].dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
+        flat = torch.cat([b.to(dt).reshape(-1) for b in blocks])
+        _lib.require_gpu_tensor(flat, "features")
+        L = self._L()
+        h4, w4 = H // 4, W // 4
+        shapes = [(B, 4, h4 << s, w4 << s) for s in range(4)]
+        with torch.cuda.device(dev):
+            need = self._native("workspace_bytes")(C.c_void_p(h), B, H, W)
+            if need == 0:
+                _lib.check(-1, L)
+            ws = self._workspace(need, dev)
+            wp = (ws.data_ptr() + 255) & ~255
+            out = torch.empty(sum(b * c * y * x for b, c, y, x in shapes), dtype=self.dtype, device=dev)
+            _lib.check(self._native("forward")(C.c_void_p(h), C.c_void_p(_lib.stream_ptr(dev)), C.c_void_p(flat.data_ptr()),
+                                               _lib.dtype_code(flat), B, H, W, C.c_void_p(wp), need, C.c_void_p(out.data_ptr()),
+                                               _lib.dtype_code(out)), L)
+        maps, at = [], 0
+        for s in shapes:
+            n = s[0] * s[1] * s[2] * s[3]
+            maps.append(out[at:at + n].view(s))
+            at += n
+        return maps, [maps[0], None, None, None], [None] * 4
+
+
+class GyreHipNNET(torch.nn.Module):
+    """The reference's ``NNET``: the caller's host ``encoder`` module (``tf_efficientnet_b5_ap`` behind the reference's ``Encoder``,
+    about 3 % of the network's arithmetic; its program text comes through ``torch.hub`` and is not restated here) and the native
+    decoder, under the reference's submodule names ``encoder`` / ``decoder``: ``forward(img, **kwargs)`` ->
+    ``decoder(encoder(img), **kwargs)``."""
+
+    def __init__(self, encoder: torch.nn.Module, **kw):
+        super().__init__()
+        self.encoder = encoder
+        self.decoder = GyreHipBaeDecoder(**kw)
+
+    def forward(self, img, **kwargs):
+        return self.decoder(self.encoder(img), **kwargs)
+
+
+def load_baenormal(path: str, encoder: torch.nn.Module, torch_dtype=None, allow_patterns=None, ignore_patterns=None, **kw) -> GyreHipNNET:
+    """``NNET`` with the weights of ``path``: a ``*.safetensors`` / ``*.pt`` / ``*.pth`` checkpoint, or a folder that holds exactly one
+    (after the allow / ignore filters) - the layout of the reference's ``hinters-baenormal`` model folder.  As the reference's loader:
+    a checkpoint may keep its weights under ``model`` and its keys may carry a ``module.`` prefix.  The ``decoder.`` entries load
+    strictly into the native decoder, the ``encoder.`` entries (strictly) into the given encoder."""
+    file = path if os.path.isfile(path) else _only_match(path, "model", MODELS_PATTERN, allow_patterns, ignore_patterns)
+    sd = _read_state_dict(file)
+    sd = sd.get("model", sd)
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    model = GyreHipNNET(encoder, **kw)
+    for name, part in (("decoder", model.decoder), ("encoder", model.encoder)):
+        part.load_state_dict({k[len(name) + 1:]: v for k, v in sd.items() if k.startswith(name + ".")})
+    return (model if torch_dtype is None else model.to(torch_dtype)).eval()
+
+
+class GyreBaenormalPipeline(_HintPipeline):
+    """The reference's ``BaenormalPipeline``: ``pipeline(tensor) -> tensor``, a float image [B, C, H, W] or [C, H, W] in [0, 1] -> its
+    normal map [B, 3, H, W] in [0, 1], on the input's device and in its dtype: ImageNet mean / std, the module (``GyreHipNNET``), the
+    first three channels of the last map, unit length, ``* 0.5 + 0.5``, clip.  (The reference's debug print is dropped.)"""
+
+    @torch.no_grad()
+    def __call__(self, tensor: torch.Tensor) -> torch.Tensor:
+        tensor, sample = self._sample(tensor)
+        mean = torch.tensor(IMAGENET_MEAN).to(sample).view(1, 3, 1, 1)
+        std = torch.tensor(IMAGENET_STD).to(sample).view(1, 3, 1, 1)
+        norm_out_list, _, _ = self.module((sample - mean) / std)
+        norm_out = norm_out_list[-1][:, :3]
+        norm_out = norm_out / (norm_out ** 2.0).sum(dim=1, keepdim=True) ** 0.5
+        result = (norm_out * 0.5 + 0.5).clip(0, 1)
+        return result.to(tensor.device, tensor.dtype)

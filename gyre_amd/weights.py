@@ -455,6 +455,40 @@ def mlsd_param_shapes(cfg=None) -> Shapes:
     return s
 
 
+def bae_is_buffer(key: str) -> bool:
+    return key.endswith(MLSD_BUFFERS)                    # a BatchNorm's running statistics and num_batches_tracked
+
+
+def bae_param_shapes(cfg) -> Shapes:
+    """State-dict keys and shapes of the reference's ``Decoder`` (gyre/pipeline/hinters/baenormal/submodules/decoder.py) with
+    architecture 'BN', in state_dict() order: conv2, the four UpSampleBN blocks (``_net.0`` / ``_net.3`` convolutions, ``_net.1`` /
+    ``_net.4`` BatchNorms with running_mean, running_var and the scalar num_batches_tracked as buffers - the last accepted by a strict
+    load, never uploaded), out_conv_res8 and the three Conv1d stacks with their [O, I, 1] weights; cfg: a mapping as
+    gyre_amd.config.bae_config returns."""
+    s: Shapes = OrderedDict()
+    NF, skip = cfg["num_features"], cfg["skip_features"]
+
+    def conv(p, o, i, *k):
+        s[p + ".weight"] = (o, i, *k)
+        s[p + ".bias"] = (o,)
+
+    conv("conv2", NF, NF, 1, 1)
+    for k in range(4):
+        p, cout = f"up{k + 1}._net", NF >> (k + 1)
+        for j, cin in ((0, (NF >> k) + skip[3 - k]), (3, cout)):
+            conv(f"{p}.{j}", cout, cin, 3, 3)
+            for leaf, shape in (("weight", (cout,)), ("bias", (cout,)), ("running_mean", (cout,)), ("running_var", (cout,)),
+                                ("num_batches_tracked", ())):
+                s[f"{p}.{j + 1}.{leaf}"] = shape
+    conv("out_conv_res8", 4, NF // 4, 3, 3)
+    for k, name in enumerate(("out_conv_res4", "out_conv_res2", "out_conv_res1")):
+        conv(name + ".0", 128, (NF >> (k + 2)) + 4, 1)
+        conv(name + ".2", 128, 128, 1)
+        conv(name + ".4", 128, 128, 1)
+        conv(name + ".6", 4, 128, 1)
+    return s
+
+
 class _WindowShapes:
     """The entries the SwinIR and HAT state dicts are made of, appended to ``s`` in call order: cfg gives the width and the MLP ratio."""
 

@@ -286,7 +286,18 @@ typedef struct {
     int32_t head_dim, mlp_ratio, qkv_bias, windows, hybrid;
 } gyre_uniformer_cfg;
 
+/* Decoder of the BAE surface-normal estimator (the reference's gyre/pipeline/hinters/baenormal/submodules/decoder.py, Decoder).
+ * num_features: the width of x_block4 and conv2 (2048), a multiple of 512 from 512 to 4096; the up blocks produce / 2, / 4, / 8, / 16
+ * of it.  skip[k]: the channels of x_block_k, k = 0 .. 3 ((24, 40, 64, 176) for tf_efficientnet_b5_ap).  architecture: 0 = 'BN';
+ * 1 = 'GN' (weight standardisation + GroupNorm) is GYRE_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t num_features;
+    int32_t skip[4];
+    int32_t architecture;
+} gyre_bae_cfg;
+
 typedef struct gyre_unet gyre_unet;
+typedef struct gyre_bae gyre_bae;
 typedef struct gyre_swinb gyre_swinb;
 typedef struct gyre_uniformer gyre_uniformer;
 typedef struct gyre_hed gyre_hed;
@@ -723,6 +734,28 @@ size_t gyre_uniformer_workspace_bytes(gyre_uniformer* h, int B, int H, int W);
  * launch).  A sample's result does not depend on the batch it runs in. */
 int gyre_uniformer_forward(gyre_uniformer* h, void* stream, const void* image_nchw, int in_dtype, int B, int H, int W,
                            void* workspace, size_t workspace_bytes, void* out_maps, int out_dtype);
+
+/* ---- BAE surface-normal decoder (normal-map hinter) ---------------------------
+ * The reference's hinters-baenormal engine is NNET = an EfficientNet-B5 encoder fetched through torch.hub + the Decoder in its tree; this
+ * handle is that Decoder in mode='test' - well over 95 % of the network's arithmetic - and the encoder stays the caller's host module.
+ * Weight keys, in the reference's state-dict order: conv2.*, upK._net.{0, 3}.* (convolutions) and upK._net.{1, 4}.{weight, bias,
+ * running_mean, running_var} (BatchNorm) for K = 1 .. 4, out_conv_res8.*, out_conv_res{4, 2, 1}.{0, 2, 4, 6}.* (Conv1d: weights
+ * [O][I][1]); a BatchNorm's num_batches_tracked is a buffer the caller keeps, not a key here.  finalize folds every BatchNorm into its
+ * convolution (fp32, one rounding).  Same workspace and dry-run sizing rules as the other handles. */
+int gyre_bae_create(const gyre_bae_cfg* cfg, int device, gyre_bae** out);
+void gyre_bae_destroy(gyre_bae* h);
+int gyre_bae_num_params(const gyre_bae* h);
+const char* gyre_bae_param_key(const gyre_bae* h, int i);
+int gyre_bae_set_weight(gyre_bae* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int gyre_bae_finalize(gyre_bae* h, void* stream);
+size_t gyre_bae_workspace_bytes(gyre_bae* h, int B, int H, int W);
+/* features = x_block0 .. x_block4 of the encoder (its feature list's entries 4, 5, 6, 8, 11), NCHW of in_dtype, back to back:
+ * [B][skip[k]][h_k][w_k] for k < 4 and [B][num_features][h_4][w_4], (h_0, w_0) = (H, W), h_(k+1) = ceil(h_k / 2).  out = out_res8,
+ * out_res4, out_res2, out_res1 of Decoder.forward(mode='test'), NCHW [B][4][.][.] of out_dtype, back to back, at (H / 4, W / 4) doubling
+ * up to (2 H, 2 W).  H and W must be positive multiples of 4 - the only sizes at which the reference's concatenations line up
+ * (GYRE_ERR_INVALID otherwise, before any launch).  A sample's result does not depend on the batch it runs in. */
+int gyre_bae_forward(gyre_bae* h, void* stream, const void* features, int in_dtype, int B, int H, int W,
+                     void* workspace, size_t workspace_bytes, void* out_maps, int out_dtype);
 
 /* ---- ControlNet ------------------------------------------------------------ */
 /* Weight keys are the diffusers ControlNetModel state-dict keys: conv_in, time_embedding.*, down_blocks.*, mid_block.* as in the UNet,
@@ -1275,6 +1308,24 @@ int gyre_op_uf_gather_img(void* stream, const void* x, int dtype, int B, int H, 
 int gyre_op_uf_fold(void* stream, const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
                     const float* var, float eps, int O, int I, void* wout, float* bout);
 int gyre_op_uf_taps(void* stream, const float* w, int C, int T, float* out);
+
+/* The kernels of the BAE normal-map decoder (kernels_bae.hip), one launch each; a refused call writes nothing.
+ * bae_refine: one refinement stage, out NCHW [B][4][2 Hs][2 Ws] fp32 = MLP(bilinear x2, align_corners=True, of [x | p]) per pixel,
+ * through norm_normalize (min_kappa 0.01) when normalize != 0.  x NHWC [B][Hs][Ws] of CF channels in storage, pixel stride ldx >= CF
+ * (CF % 32 == 0, ldx % 8 == 0); p NCHW [B][4][Hs][Ws] fp32, rounded to storage as it is read.  w1 [128][CF + 32] storage: columns
+ * [0, CF) the feature map's, [CF, CF + 4) the prediction's, the rest zero; w2 / w3 [128][128] storage; w4 [4][128], b1 .. b3 [128],
+ * b4 [4] fp32; all 16-byte aligned.  Layer 1 runs on the coarse map and its result is interpolated in fp32; the two hidden activations
+ * that feed layers 2 and 3 are rounded to storage once each; layer 4 and the epilogue are fp32.  out overlapping x or p:
+ * GYRE_ERR_INVALID; outside the domain: GYRE_ERR_UNSUPPORTED.  bae_refine_tile: the fine tile of a workgroup, pixels (rows, columns).
+ * bae_up_concat: y [B][H][W][ldo] storage = (bilinear resize of x NHWC [B][Hs][Ws][C] (pixel stride ldx) to H x W with
+ * align_corners=True | skip NCHW [B][Cs][H][W] of skip_dtype | zeros up to ldo); fp32 lerp in PyTorch's form and coordinates, one
+ * rounding; C % 8 == 0, ldo % 8 == 0; C == 0 (x ignored): the NCHW -> NHWC entry alone. */
+int gyre_op_bae_refine(void* stream, const void* x, int ldx, const float* p, int B, int Hs, int Ws, int CF, const void* w1, const float* b1,
+                       const void* w2, const float* b2, const void* w3, const float* b3, const float* w4, const float* b4, int normalize,
+                       float* out);
+int gyre_op_bae_refine_tile(int32_t* rows, int32_t* cols);
+int gyre_op_bae_up_concat(void* stream, const void* x, int B, int Hs, int Ws, int C, int ldx, const void* skip, int skip_dtype, int Cs,
+                          int H, int W, void* y, int ldo);
 /* The kernels of the token-sequence T2I networks (StyleAdapter, CoAdapterFuser; kernels_seq.hip), one launch each.
  * seq_attn: multi-head self-attention over the packed in_proj output.  qkv [N L][ld_qkv] storage, sample-major rows (row n L + l), q / k
  * / v of head h at columns h D / heads D + h D / 2 heads D + h D; o [N L][ld_o], head h written at [h D, h D + D), every other element
